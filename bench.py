@@ -22,6 +22,12 @@ epoch, inside the timed region (BASELINE config 3's trajectory gather);
 value = all ranks' simulations / the max over ranks of the timed span;
 scaling "weak".
 
+A plain run (``bench.py --gpus 1 --steps K --warmup W``) sets up, warms up,
+times the K steps and prints the line; the CPU baseline (the oracle timed on
+this host's CPU share, ``cpu_baseline`` in the line) is measured only with
+``--full``.  ``--dump-outputs DIR`` writes the game records the last timed
+step left in its engine (what a caller of SelfPlay receives) as DIR/<field>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -35,6 +41,44 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "muzero-go_amd")]
 
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
+
+
+DUMP_BUDGET = 64 * 10**6 - 4096      # --dump-outputs: bytes of array data at most (64 MB less the .npy headers)
+
+
+def dump_records(eng, out_dir, budget=DUMP_BUDGET):
+    """--dump-outputs: the self-play records in ``eng`` after the last timed
+    step, as a caller reads them (Engine.record(g) of every game slot g: the
+    recorded positions, the searches' policies and root values, the actions,
+    rewards and results), one ``<field>.npy`` per field with the game slot as
+    the first axis, rows past a game's length zero.  Tower engines (config 5)
+    keep a game's earlier moves in the same record: the last step's moves are
+    its last rows.  float64 where the engine's field is float64, float32 for
+    the byte-sized fields.  Over ``budget`` bytes, a fixed seeded sample of the
+    game slots is written (``games.npy`` holds the slots, in order)."""
+    import numpy as np
+    G, M, A, CELLS = eng.G, eng.M, eng.A, eng.N * eng.N
+    per_game = M * (A * 8 + 2 * CELLS * 4 + 3 * 8 + 4) + 4 * 8
+    K = max(1, min(G, budget // per_game))
+    games = np.arange(G) if K == G else np.sort(np.random.default_rng(0).choice(G, K, replace=False))
+    out = {"games": games.astype(np.float64),
+           "length": np.zeros(K), "status": np.zeros(K), "final_reward": np.zeros(K),
+           "action": np.zeros((K, M)), "value": np.zeros((K, M)), "reward": np.zeros((K, M)),
+           "policy": np.zeros((K, M, A)),
+           "flags": np.zeros((K, M), np.float32),
+           "stones": np.zeros((K, M, CELLS), np.float32), "invd": np.zeros((K, M, CELLS), np.float32)}
+    for i, g in enumerate(games):
+        rec = eng.record(int(g))
+        L = rec["length"]
+        for k in ("length", "status", "final_reward"):
+            out[k][i] = rec[k]
+        for k in ("action", "value", "reward", "policy", "flags", "stones", "invd"):
+            out[k][i, :L] = rec[k]
+    assert sum(a.nbytes for a in out.values()) <= budget
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
 
 def mfma_per_conv(N, cin, cout):
     """16x16x4 f32 MFMAs of one 3x3 conv of one board (Winograd at 9x9 / 19x19)."""
@@ -398,6 +442,8 @@ def tower_main(args, world, rank, local, cpu_ref):
         dist.all_reduce(tmax[:1], op=dist.ReduceOp.MAX)
         dist.all_reduce(t[1:], op=dist.ReduceOp.SUM)
         dt, sims, moves = tmax[0].item(), t[1].item(), t[2].item()
+    if rank == 0 and args.dump_outputs:
+        dump_records(eng, args.dump_outputs)
     if rank == 0:
         workload = f"{N}x{N} Go self-play, {B}-block residual nets (C={C}), {G} parallel games/GPU, {S} sims/move"
         mps = args.moves_per_step
@@ -510,6 +556,8 @@ def refill_main(args, net, world, rank, local, cpu_ref):
         dist.all_reduce(tmax[:1], op=dist.ReduceOp.MAX)
         dist.all_reduce(t[1:], op=dist.ReduceOp.SUM)
         dt, sims, moves = tmax[0].item(), t[1].item(), t[2].item()
+    if rank == 0 and args.dump_outputs:
+        dump_records(sps[(step_no[0] - 1) % R].engine, args.dump_outputs)      # the last timed epoch's engine
     if rank == 0:
         workload = f"{N}x{N} Go self-play, {G} parallel games/GPU, {S} sims/move"
         counts = dict(launches=len(kern_ms), sims=sims / world, moves=moves / world, convs=convs, rows=rows)
@@ -582,8 +630,14 @@ def main():
                     help="R >= 2: a separate configuration (not the headline): R engines of G slots on R HIP "
                          "streams play consecutive epochs, so CUs a finished game frees start the next epoch's "
                          "games instead of idling while the epoch's slowest games finish (the epoch tail)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-budget", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (the oracle on this "
+                         "host's CPU share, before the GPU is touched; ``cpu_baseline`` in the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the game records of the last timed step as DIR/<field>.npy "
+                         "(dump_records; same arguments, same games)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="with --full: seconds per CPU baseline leg")
     ap.add_argument("--cpu-procs", type=int, default=None,
                     help="oracle processes for cpu_baseline (default: this host's CPU share, cpu_share())")
     args = ap.parse_args()
@@ -593,7 +647,9 @@ def main():
         if getattr(args, k) is None:
             setattr(args, k, v)
 
-    share, share_src = cpu_share()
+    # the CPU baseline: a --full run's extra (a plain run times its steps only)
+    want_cpu = args.full and not args.no_cpu_baseline
+    share, share_src = cpu_share() if want_cpu else (None, None)
     if args.cpu_procs is None:
         args.cpu_procs = share
     blocks = args.blocks if args.config == 5 else None
@@ -604,7 +660,7 @@ def main():
         # the line, this process exits with the ranks' status.  The CPU
         # baseline runs here first (this process never touches a GPU) and
         # reaches rank 0's line through the environment.
-        if not args.no_cpu_baseline:
+        if want_cpu:
             ref = cpu_baseline_procs(args.board_size, args.latent_dim, args.sims, args.cpu_budget, args.cpu_procs,
                                      blocks)
             ref["measured_in"] = "launcher process, before the ranks started (no GPU work running)"
@@ -625,7 +681,7 @@ def main():
     if os.environ.get("MZGO_SHARE_DEVICE") == "1":
         local = 0
     cpu_ref = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and want_cpu:
         if "MZGO_CPU_BASELINE" in os.environ:        # (bench.py --gpus N's own launcher measured it)
             cpu_ref = json.loads(os.environ["MZGO_CPU_BASELINE"])
         else:
@@ -755,6 +811,8 @@ def main():
         dist.all_reduce(t[1:], op=dist.ReduceOp.SUM)
         dt, sims, moves = tmax[0].item(), t[1].item(), t[2].item()
 
+    if rank == 0 and args.dump_outputs:
+        dump_records(eng, args.dump_outputs)
     if rank == 0:
         workload = f"{N}x{N} Go self-play, {G} parallel games/GPU, {S} sims/move"
         counts = dict(launches=launches, sims=sims / world, moves=moves / world,

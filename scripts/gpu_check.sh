@@ -18,5 +18,5 @@ run pytest_gpu 1100 python -m pytest tests -m gpu -q -rf --durations=15
 rc=$?
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
-run bench 400 python bench.py --steps 10 --warmup 2 --cpu-budget 8 || exit $?
+run bench 400 python bench.py --steps 10 --warmup 2 --full --cpu-budget 8 || exit $?
 cat gpurun_out/bench.log

@@ -61,7 +61,7 @@ def test_selfplay_cli_gpus_flag_starts_the_ranks(tmp_path):
 
 
 def test_bench_gpus_2_starts_two_ranks_and_gathers_every_epoch_once():
-    """``bench.py --gpus 2`` as the driver runs it (no launcher): two rank
+    """``bench.py --gpus 2 --full`` started alone (no launcher): two rank
     processes (here both on cuda:0 with gloo standing in for RCCL), every
     timed epoch's records staged and gathered in one collective at the end
     of the timed loop, n_gpus 2 in the rank-0 line, the CPU
@@ -71,7 +71,7 @@ def test_bench_gpus_2_starts_two_ranks_and_gathers_every_epoch_once():
     env = dict(os.environ, MZGO_SHARE_DEVICE="1", MZGO_DIST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MZGO_CPU_BASELINE"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                         "--cpu-budget", "2", "--cpu-procs", "2"], env=env, cwd=ROOT, capture_output=True, text=True,
                        timeout=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
