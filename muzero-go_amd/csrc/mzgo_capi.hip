@@ -827,6 +827,21 @@ static int launch_selfplay(mzgo_engine* e, const NetParams& np_b, const PlayPara
   return MZGO_OK;
 }
 
+// a launch's PlayParams: the engine's configuration, game generation and test hooks
+static PlayParams play_params(const mzgo_engine* e, int arena, int moves) {
+  PlayParams pp;
+  pp.temperature = e->cfg.temperature;
+  pp.temperature_moves = e->cfg.temperature_moves;
+  pp.komi = e->cfg.komi;
+  pp.game_base = e->cfg.game_base;
+  pp.epoch = e->epoch;
+  pp.noise = e->noise;
+  pp.noise_out = e->noise_out;
+  pp.arena = arena;
+  pp.moves = moves;
+  return pp;
+}
+
 int mzgo_selfplay_move(mzgo_engine* e, void* stream) { return mzgo_selfplay_moves(e, 1, stream); }
 
 int mzgo_selfplay_set_timing(mzgo_engine* e, int on) {
@@ -853,16 +868,7 @@ int mzgo_selfplay_moves(mzgo_engine* e, int moves, void* stream) {
   if (!e || e->C == 0 || moves < 1) return fail(MZGO_EINVAL, "bad argument");
   int rc = e->sync_weights();
   if (rc) return rc;
-  PlayParams pp;
-  pp.temperature = e->cfg.temperature;
-  pp.temperature_moves = e->cfg.temperature_moves;
-  pp.komi = e->cfg.komi;
-  pp.game_base = e->cfg.game_base;
-  pp.epoch = e->epoch;
-  pp.noise = e->noise;
-  pp.noise_out = e->noise_out;
-  pp.arena = 0;
-  pp.moves = moves;
+  const PlayParams pp = play_params(e, 0, moves);
   if (e->tower) {
     // one move of every game: observation + representation tower + root,
     // S x (select, dynamics tower, expand), action choice + board step
@@ -908,17 +914,7 @@ int mzgo_arena_moves(mzgo_engine* e, mzgo_engine* opponent, int moves, void* str
   if (rc) return rc;
   rc = opponent->sync_weights();
   if (rc) return rc;
-  PlayParams pp;
-  pp.temperature = e->cfg.temperature;
-  pp.temperature_moves = e->cfg.temperature_moves;
-  pp.komi = e->cfg.komi;
-  pp.game_base = e->cfg.game_base;
-  pp.epoch = e->epoch;
-  pp.noise = e->noise;
-  pp.noise_out = e->noise_out;
-  pp.arena = 1;
-  pp.moves = moves;
-  return launch_selfplay(e, opponent->np, pp, (hipStream_t)stream);
+  return launch_selfplay(e, opponent->np, play_params(e, 1, moves), (hipStream_t)stream);
 }
 
 int mzgo_dyn_conv_backward_workspace(int B, int C, int64_t* bytes_host) {

@@ -7,6 +7,7 @@
 #include "mzgo_board.hpp"
 #include "mzgo_conv.hpp"
 #include "mzgo_expand.hpp"
+#include "mzgo_move.hpp"
 #include "mzgo_search.hpp"
 #include "mzgo_wino.hpp"
 
@@ -77,51 +78,6 @@ __device__ __forceinline__ NetParams launder_params(const NetParams& n) {
 #undef MZGO_L
   return r;
 }
-
-constexpr int kCounters = 9;     // EngineArrays::counters
-
-// Per-slot device state of an engine (sizes fixed at engine creation).
-struct EngineArrays {
-  int S;                 // simulations per move this engine was sized for
-  int max_moves;
-  // search state
-  float* pool;           // [G][S+2][C*CS] per node: latent [C][CS] (direct dynamics) or conv
-                         // output Y [CELLS][C] (factored); slot S+1: scratch latent
-  float* prior;          // [G][S+1][A]
-  int* child;            // [G][S+1][A]
-  int* visits;           // [G][S+1]
-  double* wsum;          // [G][S+1]
-  double* root_prior;    // [G][A]
-  int* path;             // [G][S+2]
-  int* nodes;            // [G]  nodes used by the last search
-  int* nact;             // [G][S+1] action that created each node (factored: rebuilds its latent)
-  // boards
-  int8_t* stones;        // [G][CELLS]
-  uint8_t* invd;         // [G][CELLS]
-  int* meta;             // [G][4] BoardMeta
-  // self-play records
-  int8_t* rec_stones;    // [G][M][CELLS]
-  uint8_t* rec_invd;     // [G][M][CELLS]
-  uint8_t* rec_flags;    // [G][M]   bit0 turn, bit1 passed, bit2 done
-  int* rec_action;       // [G][M]
-  double* rec_value;     // [G][M]
-  double* rec_policy;    // [G][M][A]
-  double* rec_reward;    // [G][M]
-  int* game_len;         // [G]
-  double* final_reward;  // [G]
-  int* status;           // [G]  0 playing, 1 finished, >=16 error
-  unsigned char* jobs;   // [G][job_bytes(A)] batch-expansion jobs shared with helper workgroups
-  int* mpq;              // [2G + 1] move-parallel epoch (k_search_queue): per game (first move,
-                         // moves played) of k_selfplay_boards, then the queue head
-  unsigned long long* counters;  // [kCounters] 0: simulations run, 1: moves played, 2: games finished,
-                                 //     3: dynamics convs run (factored: one per new parent; tower
-                                 //     engines: towers evaluated, speculative ones included),
-                                 //     4: of those, tail conv jobs (conv_tail), 5: prior rows formed,
-                                 //     6: game workgroups started (k_selfplay_move), 7: tail helpers
-                                 //     whose bounded wait for a job expired (tail_help), 8: expired
-                                 //     mzgo_stream_wait_started gates (reported, then cleared)
-  unsigned long long* stamps;    // [G][kStampPhases] phase cycles (MZGO_STAMPS builds only)
-};
 
 __device__ __forceinline__ EngineArrays launder_arrays(const EngineArrays& e) {
   EngineArrays r = e;
@@ -278,11 +234,7 @@ __device__ __forceinline__ void latent_conv_rebuilt(Smem<G>& sm, const NetParams
 
 template <class G>
 __device__ __forceinline__ BoardLds<G> board_lds(Smem<G>& sm) {
-  BoardLds<G> b;
-  b.stone = sm.stone; b.invd = sm.invd;
-  b.label = sm.u.scr.label; b.libs = sm.u.scr.libs; b.gsize = sm.u.scr.gsize;
-  b.killed = sm.killed; b.misc = sm.misc;
-  return b;
+  return make_board_lds<G>(sm.stone, sm.invd, sm.u.scr.label, sm.u.scr.libs, sm.u.scr.gsize, sm.killed, sm.misc);
 }
 
 // ---------------------------------------------------------------------------
@@ -2209,10 +2161,7 @@ __device__ __forceinline__ void search_outputs(const EngineArrays& E, int g, int
     const int c = T.child[a];
     if (out_visits) out_visits[(size_t)g * G::A + a] = c >= 0 ? T.visits[c] : 0;
   }
-  if (tid_local() == 0 && out_value) {
-    const int n = T.visits[0];
-    out_value[g] = n > 0 ? T.wsum[0] / (double)n : 0.0;
-  }
+  if (tid_local() == 0 && out_value) out_value[g] = root_value(T);
 }
 
 // Form the priors of every lazily expanded node no select reached
@@ -2287,41 +2236,6 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
 // ---------------------------------------------------------------------------
 // Boards
 // ---------------------------------------------------------------------------
-template <class G>
-__device__ __forceinline__ void load_board(Smem<G>& sm, const EngineArrays& E, int g, BoardMeta& m) {
-  for (int c = tid_local(); c < G::CELLS; c += G::THREADS) {
-    sm.stone[c] = E.stones[(size_t)g * G::CELLS + c];
-    sm.invd[c] = E.invd[(size_t)g * G::CELLS + c];
-  }
-  const int* mm = E.meta + g * 4;
-  m.turn = mm[0]; m.passed = mm[1]; m.done = mm[2]; m.moves = mm[3];
-  __syncthreads();
-}
-
-template <class G>
-__device__ __forceinline__ void store_board(Smem<G>& sm, const EngineArrays& E, int g, const BoardMeta& m) {
-  for (int c = tid_local(); c < G::CELLS; c += G::THREADS) {
-    E.stones[(size_t)g * G::CELLS + c] = sm.stone[c];
-    E.invd[(size_t)g * G::CELLS + c] = sm.invd[c];
-  }
-  if (tid_local() == 0) {
-    int* mm = E.meta + g * 4;
-    mm[0] = m.turn; mm[1] = m.passed; mm[2] = m.done; mm[3] = m.moves;
-  }
-}
-
-template <class G>
-__device__ __forceinline__ float board_plane(const Smem<G>& sm, const BoardMeta& m, int c, int j) {
-  switch (c) {
-    case 0: return sm.stone[j] == 1 ? 1.f : 0.f;
-    case 1: return sm.stone[j] == 2 ? 1.f : 0.f;
-    case 2: return (float)m.turn;
-    case 3: return (float)sm.invd[j];
-    case 4: return (float)m.passed;
-    default: return (float)m.done;
-  }
-}
-
 template <int N, int C>
 __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_waves_per_eu(Geo<N, C>::WPE, Geo<N, C>::WPE))) k_board_reset(EngineArrays E) {
   typedef Geo<N, C> G;
@@ -2346,11 +2260,11 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
   const int a = actions[g];
   if (a < 0) return;
   BoardMeta m;
-  load_board<G>(sm, E, g, m);
+  board_load<G>(sm.stone, sm.invd, E, g, m);
   BoardLds<G> b = board_lds<G>(sm);
   const int st = board_step<G>(b, m, a);
   __syncthreads();
-  if (st == BOARD_OK) store_board<G>(sm, E, g, m);
+  if (st == BOARD_OK) board_store<G>(sm.stone, sm.invd, E, g, m);
   double w = 0.0;
   if (st == BOARD_OK && m.done) w = board_winning<G>(b, komi);
   if (tid_local() == 0) {
@@ -2375,175 +2289,10 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
 }
 
 // ---------------------------------------------------------------------------
-// Action choice (MuZeroAgent.select_action, self_play.py:357-402).  Wave 0.
-// Writes the policy target to pol[A]; returns the action.
-// ---------------------------------------------------------------------------
-// main.py's move rule (self-play :660-673 and the arena evaluator :552-565):
-// visit_counts = child visit counts where valid_mask > 0; argmax (first max)
-// with policy = counts / sum, else random.choice(valid actions) with a one-hot
-// policy.  Temperature plays no part.  Wave 0.
-template <class G>
-__device__ __forceinline__ int choose_action_main(TreeLds<G>& t, const TreeView& T, uint64_t key, double* pol) {
-  const int lane = lane_id_local();
-  double vc[G::AP];
-  double bv = -1.0, tot = 0.0;
-  int ba = 0x7fffffff, best_c = 0;
-#pragma unroll
-  for (int j = 0; j < G::AP; ++j) {
-    const int a = lane + 64 * j;
-    vc[j] = 0.0;
-    if (a < G::A && mask_of<G>(t, a) > 0) { const int c = T.child[a]; vc[j] = c >= 0 ? (double)T.visits[c] : 0.0; }
-    tot += vc[j];
-    if (a < G::A && (vc[j] > bv || (vc[j] == bv && a < ba))) { bv = vc[j]; ba = a; }
-  }
-  tot = wave_sum(tot);                          // integer counts: exact in any order
-  wave_argmax(bv, ba, best_c);
-  int action = ba;
-  if (!(tot > 0)) {                             // random.choice(valid actions)
-    uint64_t vb[G::AP];
-    int nvalid = 0;
-#pragma unroll
-    for (int j = 0; j < G::AP; ++j) {
-      const int a = lane + 64 * j;
-      vb[j] = __ballot(a < G::A && mask_of<G>(t, a) > 0);
-      nvalid += __popcll(vb[j]);
-    }
-    uint32_t k = randbelow(draw(key, TAG_ACTION, 0), (uint32_t)nvalid);
-    action = -1;
-#pragma unroll
-    for (int j = 0; j < G::AP; ++j) {
-      const uint32_t c = __popcll(vb[j]);
-      if (action < 0 && k < c) {
-        uint64_t mm = vb[j];
-        for (uint32_t i = 0; i < k; ++i) mm &= mm - 1;
-        action = 64 * j + __ffsll((long long)mm) - 1;
-      } else if (action < 0) {
-        k -= c;
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < G::AP; ++j) {
-    const int a = lane + 64 * j;
-    if (a < G::A) pol[a] = tot > 0 ? vc[j] / tot : (a == action ? 1.0 : 0.0);
-  }
-  return action;
-}
-
-template <class G>
-__device__ __forceinline__ int choose_action(TreeLds<G>& t, const TreeView& T, int compat, double temperature,
-                                    uint64_t key, double* pol) {
-  const int lane = lane_id_local();
-  // visit_counts * valid_mask (zeros under compat "reference", §0.6)
-  for (int a = lane; a < G::A; a += 64) {
-    double vc = 0.0;
-    if (compat == 1) { const int c = T.child[a]; vc = c >= 0 ? (double)T.visits[c] : 0.0; }
-    t.dbuf[a] = vc * mask_of<G>(t, a);
-  }
-  wave_lds_sync();
-  const double vsum = np_pairwise_sum<double, G::A>(t.dbuf);
-  double vcm[G::AP];
-#pragma unroll
-  for (int j = 0; j < G::AP; ++j) { const int a = lane + 64 * j; vcm[j] = a < G::A ? t.dbuf[a] : 0.0; }
-  wave_lds_sync();
-  for (int a = lane; a < G::A; a += 64) t.dbuf[a] = mask_of<G>(t, a);
-  wave_lds_sync();
-  const double msum = np_pairwise_sum<double, G::A>(t.dbuf);
-#pragma unroll
-  for (int j = 0; j < G::AP; ++j) {
-    const int a = lane + 64 * j;
-    if (a < G::A) pol[a] = vsum > 0 ? vcm[j] / vsum : mask_of<G>(t, a) / msum;
-  }
-  const uint64_t h = draw(key, TAG_ACTION, 0);
-  int action = 0;
-  if (temperature == 0.0) {
-    if (vsum > 0) {                                    // argmax, first max wins
-      double bv = -1.0; int ba = 0x7fffffff;
-#pragma unroll
-      for (int j = 0; j < G::AP; ++j) {
-        const int a = lane + 64 * j;
-        if (a < G::A && (vcm[j] > bv || (vcm[j] == bv && a < ba))) { bv = vcm[j]; ba = a; }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(bv, o); const int oa = __shfl_xor(ba, o);
-        if (ov > bv || (ov == bv && oa < ba)) { bv = ov; ba = oa; }
-      }
-      action = ba;
-    } else {                                           // random.choice(valid actions)
-      uint64_t vb[G::AP];
-      int nvalid = 0;
-#pragma unroll
-      for (int j = 0; j < G::AP; ++j) {
-        const int a = lane + 64 * j;
-        vb[j] = __ballot(a < G::A && mask_of<G>(t, a) > 0);
-        nvalid += __popcll(vb[j]);
-      }
-      uint32_t k = randbelow(h, (uint32_t)nvalid);
-      action = -1;
-#pragma unroll
-      for (int j = 0; j < G::AP; ++j) {
-        const uint32_t c = __popcll(vb[j]);
-        if (action < 0 && k < c) {
-          uint64_t mm = vb[j];
-          for (uint32_t i = 0; i < k; ++i) mm &= mm - 1;
-          action = 64 * j + __ffsll((long long)mm) - 1;
-        } else if (action < 0) {
-          k -= c;
-        }
-      }
-    }
-  } else {
-    // probabilities = (vc**(1/T) * mask) / sum, or mask / sum(mask); then
-    // np.random.choice's inverse CDF on a cumulative sum
-    const double e = 1.0 / temperature;
-#pragma unroll
-    for (int j = 0; j < G::AP; ++j) {
-      const int a = lane + 64 * j;
-      if (a < G::A) t.dbuf[a] = (e == 1.0 ? vcm[j] : pow(vcm[j], e)) * mask_of<G>(t, a);
-    }
-    wave_lds_sync();
-    const double ts = np_pairwise_sum<double, G::A>(t.dbuf);
-    wave_lds_sync();
-    for (int a = lane; a < G::A; a += 64) t.dbuf[a] = ts > 0 ? t.dbuf[a] / ts : mask_of<G>(t, a) / msum;
-    wave_lds_sync();
-    if (lane == 0) {
-      double cdf = 0.0;
-      for (int a = 0; a < G::A; ++a) cdf += t.dbuf[a];
-      const double total = cdf;
-      const double u = u01(h);
-      double run = 0.0;
-      int idx = 0;
-      for (int a = 0; a < G::A; ++a) {
-        run += t.dbuf[a];
-        if (run / total <= u) idx = a + 1;
-      }
-      t.bcast = idx;
-    }
-    wave_lds_sync();
-    action = t.bcast;
-  }
-  return action;
-}
-
-// ---------------------------------------------------------------------------
 // One self-play move for every unfinished slot (run_self_play_game's loop
 // body, self_play.py:465-507): record the observation, search, choose, step
 // the board, record the result; finish the game on double pass or N*N moves.
 // ---------------------------------------------------------------------------
-struct PlayParams {
-  double temperature;     // 1.0
-  int temperature_moves;  // 15
-  double komi;            // 0
-  int game_base;          // global id of slot 0 (multi-GPU sharding)
-  int epoch;              // game generation (slot restarts), part of the RNG key
-  const double* noise;    // test hook: injected Dirichlet samples [G][M][A], or null
-  double* noise_out;      // test hook: every root's normalised Dirichlet sample [G][M][A], or null
-  int arena;              // 0: one network; 1: main.py's evaluator -- game i's first
-                          // mover is network (i % 2), then the networks alternate
-  int moves;              // moves per game in this launch (each game stops at its end)
-};
-
 template <int N, int C>
 __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_waves_per_eu(Geo<N, C>::WPE, Geo<N, C>::WPE))) k_selfplay_move(NetParams np_a_arg, NetParams np_b_arg,
                                                              SearchParams sp, PlayParams pp, EngineArrays E_arg) {
@@ -2606,7 +2355,7 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
     __hip_atomic_store(job_of<G>(E_arg, g).started(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if constexpr (G::WINO) wino_raw_zero<G>(sm.raw);        // zero halo of the conv input planes
   BoardMeta m;
-  load_board<G>(sm, E, g, m);
+  board_load<G>(sm.stone, sm.invd, E, g, m);
   // pp.moves moves of this game in one launch (the board stays in LDS between
   // them): a game's moves run back to back on its CU instead of every move of
   // every game waiting for the slowest game's move at a launch boundary
@@ -2628,14 +2377,8 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
   // arguments would copy both to scratch)
   const NetParams np = select_params(pp.arena && (((pp.game_base + g) + mv) & 1), np_b, np_a);
   const size_t rec = (size_t)g * E.max_moves + mv;
-  for (int c = tid_local(); c < G::CELLS; c += G::THREADS) {
-    E.rec_stones[rec * G::CELLS + c] = sm.stone[c];
-    E.rec_invd[rec * G::CELLS + c] = sm.invd[c];
-  }
-  if (tid_local() == 0) E.rec_flags[rec] = (uint8_t)(m.turn | (m.passed << 1) | (m.done << 2));
-
-  const uint32_t gid = (uint32_t)(pp.game_base + g) ^ ((uint32_t)pp.epoch << 24);
-  const uint64_t key = stream_key(sp.seed, gid, (uint32_t)mv);
+  record_observation<G>(E, rec, sm.stone, sm.invd, m);
+  const uint64_t key = move_key(sp, pp, g, mv);
   const BoardMeta m0 = m;
   const double* noise = pp.noise ? pp.noise + ((size_t)g * E.max_moves + mv) * G::A : nullptr;
   double* noise_out = pp.noise_out ? pp.noise_out + ((size_t)g * E.max_moves + mv) * G::A : nullptr;
@@ -2644,32 +2387,25 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
 #endif
   SearchParams spm = launder_search(sp);
   spm.net = (pp.arena && (((pp.game_base + g) + mv) & 1)) ? 1 : 0;
-  run_search<G>(sm, np, spm, E, g, [&](int c, int j) { return board_plane<G>(sm, m0, c, j); }, noise, key,
-                tm ? tm + 2 : nullptr, noise_out);
+  run_search<G>(sm, np, spm, E, g, [&](int c, int j) { return board_plane<G>(sm.stone, sm.invd, m0, c, j); },
+                noise, key, tm ? tm + 2 : nullptr, noise_out);
 #ifdef MZGO_STAMPS
   tm[4] = __builtin_amdgcn_s_memtime();
 #endif
 
   const TreeView T = TreeViewOf<G>::make(E, g);
   if (wave_id() == 0) {
-    const double temp = mv < pp.temperature_moves ? pp.temperature : 0.0;
-    const int a = sp.variant == 1 ? choose_action_main<G>(sm.t, T, key, E.rec_policy + rec * G::A)
-                                  : choose_action<G>(sm.t, T, sp.compat, temp, key, E.rec_policy + rec * G::A);
+    const int a = choose_move_action<G>(sm.t, T, sp, pp, mv, key, E.rec_policy + rec * G::A);
     if (lane_id_local() == 0) {
       sm.bc[0] = a;
       E.rec_action[rec] = a;
-      const int n = T.visits[0];
-      E.rec_value[rec] = n > 0 ? T.wsum[0] / (double)n : 0.0;
+      E.rec_value[rec] = root_value(T);
     }
   }
   __syncthreads();
-  const int action = sm.bc[0];
   BoardLds<G> b = board_lds<G>(sm);
-  const int st = board_step<G>(b, m, action);
-  __syncthreads();
-  double w = 0.0;
-  if (st == BOARD_OK && m.done) w = board_winning<G>(b, pp.komi);
-  store_board<G>(sm, E, g, m);
+  double w;
+  const int st = play_action<G>(E, g, b, m, sm.bc[0], pp.komi, w);
 #ifdef MZGO_STAMPS
   // move phases (slots 83-87): board load + record, representation, root
   // priors, the simulations, action choice + board step
@@ -2686,21 +2422,7 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
     sl[90] += tm[2] - tm[6];                     //   conv3 + heads
   }
 #endif
-  const bool over = st != BOARD_OK || m.done || m.moves >= E.max_moves;
-  if (tid_local() == 0) {
-    E.rec_reward[rec] = w;
-    atomicAdd(&E.counters[0], (unsigned long long)sp.num_simulations);
-    atomicAdd(&E.counters[1], 1ull);
-    if (st != BOARD_OK) {
-      E.status[g] = 16 + st;
-    } else if (m.done || m.moves >= E.max_moves) {
-      E.status[g] = 1;
-      E.game_len[g] = m.moves;
-      E.final_reward[g] = m.done ? w : 0.0;      // env.winner() is 0 unless ended
-      atomicAdd(&E.counters[2], 1ull);
-    }
-  }
-  if (over) break;
+  if (finish_move<G>(E, sp, g, rec, st, m, w)) break;
   __syncthreads();                               // this move's LDS reads before the next move's writes
   }
   release_helpers();
@@ -2714,9 +2436,7 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
 // rounds with a barrier apiece, so the step's latency is
 // the launch's: a workgroup of BoardsGeo::THREADS (one cell per lane, 2 waves
 // at 9x9) with a few KB of LDS instead of k_selfplay_move's 12 waves and 159
-// KB.  Same operations as k_selfplay_move's move (build_mask, choose_action,
-// board_step, board_winning with this workgroup as the team), so the records
-// are the same.
+// KB.  The move is mzgo_move.hpp's, with this workgroup as the team.
 // ---------------------------------------------------------------------------
 template <class G>
 struct BoardsGeo {
@@ -2746,7 +2466,6 @@ __global__ void __launch_bounds__((BoardsGeo<Geo<N, C>>::THREADS)) k_selfplay_bo
                                                                                     EngineArrays E) {
   typedef Geo<N, C> G;
   typedef BoardsTeam<G> T;
-  constexpr int BT = BoardsGeo<G>::THREADS;
   __shared__ BoardsSmem<G> sm;
   const int g = blockIdx.x;
   const int tid = tid_local();
@@ -2755,81 +2474,31 @@ __global__ void __launch_bounds__((BoardsGeo<Geo<N, C>>::THREADS)) k_selfplay_bo
     E.mpq[2 * g + 1] = 0;
   }
   if (E.status[g] != 0) return;
-  for (int c = tid; c < G::CELLS; c += BT) {
-    sm.stone[c] = E.stones[(size_t)g * G::CELLS + c];
-    sm.invd[c] = E.invd[(size_t)g * G::CELLS + c];
-  }
   BoardMeta m;
-  {
-    const int* mm = E.meta + g * 4;
-    m.turn = mm[0]; m.passed = mm[1]; m.done = mm[2]; m.moves = mm[3];
-  }
-  __syncthreads();
-  BoardLds<G> b;
-  b.stone = sm.stone; b.invd = sm.invd;
-  b.label = sm.label; b.libs = sm.libs; b.gsize = sm.gsize;
-  b.killed = sm.killed; b.misc = sm.misc;
+  board_load<G, T>(sm.stone, sm.invd, E, g, m);
+  BoardLds<G> b = make_board_lds<G>(sm.stone, sm.invd, sm.label, sm.libs, sm.gsize, sm.killed, sm.misc);
   const int mv_first = m.moves;
   int played = 0;
   const TreeView TV = TreeViewOf<G>::make(E, g);         // (compat "reference" reads no tree)
   for (int step = 0; step < pp.moves; ++step) {
     const int mv = m.moves;
     const size_t rec = (size_t)g * E.max_moves + mv;
-    for (int c = tid; c < G::CELLS; c += BT) {
-      E.rec_stones[rec * G::CELLS + c] = sm.stone[c];
-      E.rec_invd[rec * G::CELLS + c] = sm.invd[c];
-    }
-    if (tid == 0) E.rec_flags[rec] = (uint8_t)(m.turn | (m.passed << 1) | (m.done << 2));
+    record_observation<G, T>(E, rec, sm.stone, sm.invd, m);
     ++played;
-    const uint32_t gid = (uint32_t)(pp.game_base + g) ^ ((uint32_t)pp.epoch << 24);
-    const uint64_t key = stream_key(sp.seed, gid, (uint32_t)mv);
-    // build_mask (self_play.py:152, :363) with this workgroup's stride
-    {
-      int any = 0;
-      for (int a = tid; a < G::A; a += BT) {
-        const uint8_t v = a < G::CELLS ? (sm.invd[a] == 0 ? 1 : 0) : 1;
-        sm.t.valid[a] = v;
-        any |= (a < G::CELLS) && v;
-      }
-      any = __syncthreads_or(any);
-      if (tid == 0) sm.t.pass_prior = any ? sp.pass_epsilon : 1.0;
-      __syncthreads();
-    }
+    const uint64_t key = move_key(sp, pp, g, mv);
+    build_mask<G, T>(sm.t, sp.pass_epsilon, [&](int a) { return sm.invd[a]; });
     if (wave_id() == 0) {
-      const double temp = mv < pp.temperature_moves ? pp.temperature : 0.0;
-      const int a = choose_action<G>(sm.t, TV, sp.compat, temp, key, E.rec_policy + rec * G::A);
+      // (the host launches this schedule for search variant 0 only: choose_move_action's self_play.py arm)
+      const int a = choose_action<G>(sm.t, TV, sp.compat, move_temperature(pp, mv), key, E.rec_policy + rec * G::A);
       if (lane_id_local() == 0) {
         sm.bc[0] = a;
         E.rec_action[rec] = a;
       }
     }
     __syncthreads();
-    const int action = sm.bc[0];
-    const int st = board_step<G, T>(b, m, action);
-    __syncthreads();
-    double w = 0.0;
-    if (st == BOARD_OK && m.done) w = board_winning<G, T>(b, pp.komi);
-    for (int c = tid; c < G::CELLS; c += BT) {
-      E.stones[(size_t)g * G::CELLS + c] = sm.stone[c];
-      E.invd[(size_t)g * G::CELLS + c] = sm.invd[c];
-    }
-    const bool over = st != BOARD_OK || m.done || m.moves >= E.max_moves;
-    if (tid == 0) {
-      int* mm = E.meta + g * 4;
-      mm[0] = m.turn; mm[1] = m.passed; mm[2] = m.done; mm[3] = m.moves;
-      E.rec_reward[rec] = w;
-      atomicAdd(&E.counters[0], (unsigned long long)sp.num_simulations);
-      atomicAdd(&E.counters[1], 1ull);
-      if (st != BOARD_OK) {
-        E.status[g] = 16 + st;
-      } else if (m.done || m.moves >= E.max_moves) {
-        E.status[g] = 1;
-        E.game_len[g] = m.moves;
-        E.final_reward[g] = m.done ? w : 0.0;
-        atomicAdd(&E.counters[2], 1ull);
-      }
-    }
-    if (over) break;
+    double w;
+    const int st = play_action<G, T>(E, g, b, m, sm.bc[0], pp.komi, w);
+    if (finish_move<G, T>(E, sp, g, rec, st, m, w)) break;
     __syncthreads();                               // this move's LDS reads before the next move's writes
   }
   if (tid == 0) {
@@ -2884,27 +2553,20 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
     const EngineArrays E = launder_arrays(E_arg);
     const NetParams np = launder_params(np_arg);
     const size_t rec = (size_t)g * E.max_moves + mv;
-    for (int c = tid_local(); c < G::CELLS; c += G::THREADS) {
+    for (int c = tid_local(); c < G::CELLS; c += G::THREADS) {   // record_observation's inverse
       sm.stone[c] = E.rec_stones[rec * G::CELLS + c];
       sm.invd[c] = E.rec_invd[rec * G::CELLS + c];
     }
-    const int fl = E.rec_flags[rec];
-    BoardMeta m0;
-    m0.turn = fl & 1; m0.passed = (fl >> 1) & 1; m0.done = (fl >> 2) & 1; m0.moves = mv;
+    const BoardMeta m0 = flags_unpack(E.rec_flags[rec], mv);
     __syncthreads();
-    const uint32_t gid = (uint32_t)(pp.game_base + g) ^ ((uint32_t)pp.epoch << 24);
-    const uint64_t key = stream_key(sp.seed, gid, (uint32_t)mv);
+    const uint64_t key = move_key(sp, pp, g, mv);
     const double* noise = pp.noise ? pp.noise + rec * G::A : nullptr;
     double* noise_out = pp.noise_out ? pp.noise_out + rec * G::A : nullptr;
     SearchParams spm = launder_search(sp);
     spm.net = 0;
-    run_search<G>(sm, np, spm, E, slot, [&](int c, int jj) { return board_plane<G>(sm, m0, c, jj); }, noise, key,
-                  nullptr, noise_out);
-    if (tid_local() == 0) {
-      const TreeView T = TreeViewOf<G>::make(E, slot);
-      const int n = T.visits[0];
-      E.rec_value[rec] = n > 0 ? T.wsum[0] / (double)n : 0.0;
-    }
+    run_search<G>(sm, np, spm, E, slot, [&](int c, int jj) { return board_plane<G>(sm.stone, sm.invd, m0, c, jj); },
+                  noise, key, nullptr, noise_out);
+    if (tid_local() == 0) E.rec_value[rec] = root_value(TreeViewOf<G>::make(E, slot));
     __syncthreads();                               // this search's LDS reads before the next board
   }
   if (sp.helpers > 0 && tid_local() == 0)

@@ -6,7 +6,7 @@
 //   select_leaf       self_play.py:239-335  (unexpanded-first, min-max-Q PUCT)
 //   expand + backup   self_play.py:198-230, :337-343
 //   root_priors       self_play.py:151-182  (mask, normalise, Dirichlet, re-mask)
-//   choose_action     self_play.py:357-402  (compat "reference" and "fixed")
+//   choose_action     self_play.py:357-402  (compat "reference" and "fixed"; mzgo_move.hpp)
 //
 // Numerics follow numpy's dtype chain: root priors float64,
 // child priors float32 (softmax * root mask / numpy-ordered f32 sum), Q, U
@@ -162,19 +162,7 @@ __device__ __forceinline__ double mask_of(const TreeLds<G>& t, int a) {
   return a < G::CELLS ? (t.valid[a] ? 1.0 : 0.0) : t.pass_prior;
 }
 
-// valid_mask from the INVD plane (self_play.py:152-158); call with all threads
-template <class G, class InvdFn>
-__device__ __forceinline__ void build_mask(TreeLds<G>& t, double pass_epsilon, InvdFn invd) {
-  int any = 0;
-  for (int a = tid_local(); a < G::A; a += G::THREADS) {
-    uint8_t v = a < G::CELLS ? (invd(a) == 0 ? 1 : 0) : 1;
-    t.valid[a] = v;
-    any |= (a < G::CELLS) && v;
-  }
-  any = __syncthreads_or(any);
-  if (tid_local() == 0) t.pass_prior = any ? pass_epsilon : 1.0;
-  __syncthreads();
-}
+// (t.valid and t.pass_prior are filled by build_mask, mzgo_move.hpp)
 
 // softmax of a lane's logits x[j] (a = lane + 64*j; entries a >= A ignored)
 // -> p[j], torch CPU order: exp(x - max) * (1/sum), the per-lane partial sums

@@ -787,19 +787,8 @@ __device__ __forceinline__ void tsum_heads(const TowerArrays& T, int b, float* h
   wave_lds_sync();
 }
 
-template <class G>
-__device__ __forceinline__ float tplane(const int8_t* stone, const uint8_t* invd, const BoardMeta& m, int c, int j) {
-  switch (c) {
-    case 0: return stone[j] == 1 ? 1.f : 0.f;
-    case 1: return stone[j] == 2 ? 1.f : 0.f;
-    case 2: return (float)m.turn;
-    case 3: return (float)invd[j];
-    case 4: return (float)m.passed;
-    default: return (float)m.done;
-  }
-}
-
 // representation input board + root mask from 6 observation planes plane(c, cell)
+// (the mask is build_mask's, mzgo_move.hpp, written to global memory by one wave)
 template <class G, class PlaneFn>
 __device__ __forceinline__ void tstage_root(const TowerArrays& T, int g, double pass_epsilon, PlaneFn plane) {
   bf16* dst = T.rep_in + (size_t)g * G::P * 64;
@@ -830,26 +819,15 @@ __global__ void __launch_bounds__(64) k_tobs(TowerArrays T, SearchParams sp, Pla
   __shared__ int8_t stone[G::CELLS];
   __shared__ uint8_t invd[G::CELLS];
   if (E.status[g] != 0) { if (threadIdx.x == 0) T.playing[g] = 0; return; }
-  for (int c = threadIdx.x; c < G::CELLS; c += 64) {
-    stone[c] = E.stones[(size_t)g * G::CELLS + c];
-    invd[c] = E.invd[(size_t)g * G::CELLS + c];
-  }
   BoardMeta m;
-  const int* mm = E.meta + g * 4;
-  m.turn = mm[0]; m.passed = mm[1]; m.done = mm[2]; m.moves = mm[3];
-  wave_lds_sync();
+  board_load<G>(stone, invd, E, g, m);
   const size_t rec = (size_t)g * E.max_moves + m.moves;
-  for (int c = threadIdx.x; c < G::CELLS; c += 64) {
-    E.rec_stones[rec * G::CELLS + c] = stone[c];
-    E.rec_invd[rec * G::CELLS + c] = invd[c];
-  }
+  record_observation<G>(E, rec, stone, invd, m);
   if (threadIdx.x == 0) {
-    E.rec_flags[rec] = (uint8_t)(m.turn | (m.passed << 1) | (m.done << 2));
     T.playing[g] = 1;
-    const uint32_t gid = (uint32_t)(pp.game_base + g) ^ ((uint32_t)pp.epoch << 24);
-    T.key[g] = stream_key(sp.seed, gid, (uint32_t)m.moves);
+    T.key[g] = move_key(sp, pp, g, m.moves);
   }
-  tstage_root<G>(T, g, sp.pass_epsilon, [&](int c, int j) { return tplane<G>(stone, invd, m, c, j); });
+  tstage_root<G>(T, g, sp.pass_epsilon, [&](int c, int j) { return board_plane<G>(stone, invd, m, c, j); });
 }
 
 // search API start: root observations f32 [G][6][N][N]
@@ -1287,7 +1265,7 @@ __global__ void __launch_bounds__(64) k_tbexpand(TowerArrays T, SearchParams sp,
   }
 }
 
-// action choice, record, board step (self_play.py:465-507), as k_selfplay_move's tail
+// action choice, record, board step (self_play.py:465-507): the end of mzgo_move.hpp's move
 template <int N>
 __global__ void __launch_bounds__(64) k_tchoose(TowerArrays T, SearchParams sp, PlayParams pp, EngineArrays E) {
   typedef TGeo<N> G;
@@ -1299,52 +1277,20 @@ __global__ void __launch_bounds__(64) k_tchoose(TowerArrays T, SearchParams sp, 
   __shared__ int label[G::CELLS], libs[G::CELLS], gsize[G::CELLS];
   __shared__ int killed[4], misc[8];
   tload_mask<G>(t, T, g);
-  for (int c = threadIdx.x; c < G::CELLS; c += 64) {
-    stone[c] = E.stones[(size_t)g * G::CELLS + c];
-    invd[c] = E.invd[(size_t)g * G::CELLS + c];
-  }
   BoardMeta m;
-  const int* mm = E.meta + g * 4;
-  m.turn = mm[0]; m.passed = mm[1]; m.done = mm[2]; m.moves = mm[3];
-  const int mv = m.moves;
-  const size_t rec = (size_t)g * E.max_moves + mv;
+  board_load<G>(stone, invd, E, g, m);
+  const size_t rec = (size_t)g * E.max_moves + m.moves;
   const TreeView TV = TreeViewOf<G>::make(E, g);
-  const uint64_t key = T.key[g];
-  const double temp = mv < pp.temperature_moves ? pp.temperature : 0.0;
-  const int a = sp.variant == 1 ? choose_action_main<G>(t, TV, key, E.rec_policy + rec * G::A)
-                                : choose_action<G>(t, TV, sp.compat, temp, key, E.rec_policy + rec * G::A);
+  const int a = choose_move_action<G>(t, TV, sp, pp, m.moves, T.key[g], E.rec_policy + rec * G::A);
   if (threadIdx.x == 0) {
     E.rec_action[rec] = a;
-    const int n = TV.visits[0];
-    E.rec_value[rec] = n > 0 ? TV.wsum[0] / (double)n : 0.0;
+    E.rec_value[rec] = root_value(TV);
   }
   __syncthreads();
-  BoardLds<G> bl;
-  bl.stone = stone; bl.invd = invd; bl.label = label; bl.libs = libs; bl.gsize = gsize;
-  bl.killed = killed; bl.misc = misc;
-  const int st = board_step<G>(bl, m, a);
-  __syncthreads();
-  double w = 0.0;
-  if (st == BOARD_OK && m.done) w = board_winning<G>(bl, pp.komi);
-  for (int c = threadIdx.x; c < G::CELLS; c += 64) {
-    E.stones[(size_t)g * G::CELLS + c] = stone[c];
-    E.invd[(size_t)g * G::CELLS + c] = invd[c];
-  }
-  if (threadIdx.x == 0) {
-    int* mw = E.meta + g * 4;
-    mw[0] = m.turn; mw[1] = m.passed; mw[2] = m.done; mw[3] = m.moves;
-    E.rec_reward[rec] = w;
-    atomicAdd(&E.counters[0], (unsigned long long)sp.num_simulations);
-    atomicAdd(&E.counters[1], 1ull);
-    if (st != BOARD_OK) {
-      E.status[g] = 16 + st;
-    } else if (m.done || m.moves >= E.max_moves) {
-      E.status[g] = 1;
-      E.game_len[g] = m.moves;
-      E.final_reward[g] = m.done ? w : 0.0;
-      atomicAdd(&E.counters[2], 1ull);
-    }
-  }
+  BoardLds<G> bl = make_board_lds<G>(stone, invd, label, libs, gsize, killed, misc);
+  double w;
+  const int st = play_action<G>(E, g, bl, m, a, pp.komi, w);
+  finish_move<G>(E, sp, g, rec, st, m, w);
 }
 
 // search API end: every prior row a select never reached (lazy, k_texpand)

@@ -276,3 +276,34 @@ def test_helper_workgroups_do_not_change_records(helpers, monkeypatch):
         assert a["length"] == b["length"]
         for k in ("stones", "invd", "flags", "action", "value", "policy", "reward"):
             assert a[k].tobytes() == b[k].tobytes(), (g, k)
+
+
+def test_tower_and_reference_engines_play_the_same_boards():
+    """Compat "reference", search variant 0: a game's actions and policy
+    targets never read the search (the action is a keyed draw over the legal
+    moves, the target is mask / sum), so the residual-tower engine and the
+    reference-network engine -- different networks, different kernels, one
+    record protocol -- play the same boards from the same seed and epoch.
+    Everything recorded except the root values is equal byte for byte, and
+    the move counters advance alike."""
+    import mzgo
+    N, G, S, seed, epoch = 5, 8, 4, 4321, 2
+    A = N * N + 1
+    tower = mzgo.ResMuZeroNet(64, A, 1).to("cuda").eval()
+    tower.load_state_dict(mzgo.deterministic_res_state_dict(64, A, 1, 0))
+    recs, cnts = [], []
+    for net in (tower, _net(N, 96)):
+        sp = mzgo.SelfPlay(net, G, S, seed=seed)
+        c0 = sp.engine.counters()
+        sp.reset(epoch=epoch)
+        sp.move(sp.max_moves)
+        c1 = sp.engine.counters()
+        assert c1["playing"] == 0
+        cnts.append({k: c1[k] - c0[k] for k in ("moves", "simulations", "games_finished")})
+        recs.append([sp.engine.record(g) for g in range(G)])
+    assert cnts[0] == cnts[1]
+    for g, (a, b) in enumerate(zip(*recs)):
+        assert a["length"] == b["length"] and a["status"] == b["status"], g
+        assert a["final_reward"] == b["final_reward"], g
+        for k in ("stones", "invd", "flags", "action", "policy", "reward"):
+            assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), (g, k)
