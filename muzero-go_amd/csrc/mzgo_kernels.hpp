@@ -2,240 +2,13 @@
 // latent_dim C and instantiated per (N, C) in mzgo_kernels_N*.hip.
 //
 // Every kernel runs one workgroup (4 waves) per game / batch element; games
-// never talk to each other, so there is no inter-workgroup synchronisation.
+// never talk to each other, so the only inter-workgroup synchronisation is a
+// game's with its helper workgroups: the job protocol, mzgo_jobs.hpp (which
+// brings in Smem and the conv wrappers, mzgo_smem.hpp).
 #pragma once
-#include "mzgo_board.hpp"
-#include "mzgo_conv.hpp"
-#include "mzgo_expand.hpp"
-#include "mzgo_move.hpp"
-#include "mzgo_search.hpp"
-#include "mzgo_wino.hpp"
+#include "mzgo_jobs.hpp"
 
 namespace mzgo {
-
-// Network parameters on the device (packed by mzgo_capi.cpp).
-struct NetParams {
-  const float* w_conv1; const float* b_conv1;   // representation.conv1 (6 -> 64)
-  const float* w_conv2; const float* b_conv2;   // representation.conv2 (64 -> 64)
-  const float* w_conv3; const float* b_conv3;   // representation.conv3 (64 -> C)
-  const float* w_dyn;   const float* b_dyn;     // dynamics.conv (C -> C)
-  const float* emb;                             // dynamics.action_embedding [A][C]
-  const float* head_w;                          // [3][C]: reward_conv, value_conv, policy_conv
-  const float* etab;                            // [A][9][C] action-tap table (mzgo_expand.hpp)
-  HeadScalars hs;
-};
-
-// b ? x : y, field by field (kernel-argument pointers stay known-global, so
-// their loads are global loads, not flat ones)
-__device__ __forceinline__ NetParams select_params(bool b, const NetParams& x, const NetParams& y) {
-  NetParams n;
-#define MZGO_SEL(f) n.f = b ? x.f : y.f;
-  MZGO_SEL(w_conv1) MZGO_SEL(b_conv1) MZGO_SEL(w_conv2) MZGO_SEL(b_conv2) MZGO_SEL(w_conv3) MZGO_SEL(b_conv3)
-  MZGO_SEL(w_dyn) MZGO_SEL(b_dyn) MZGO_SEL(emb) MZGO_SEL(head_w) MZGO_SEL(etab)
-  MZGO_SEL(hs.reward_b) MZGO_SEL(hs.fc1_w) MZGO_SEL(hs.fc1_b) MZGO_SEL(hs.fc2_w) MZGO_SEL(hs.fc2_b)
-  MZGO_SEL(hs.value_b) MZGO_SEL(hs.vfc_w) MZGO_SEL(hs.vfc_b) MZGO_SEL(hs.policy_b) MZGO_SEL(hs.pass_logit)
-#undef MZGO_SEL
-  return n;
-}
-
-// A kernel-argument pointer made opaque to the optimizer at this point of the
-// program (an empty asm on its SGPR pair) and re-marked global: address
-// arithmetic derived from it cannot be hoisted above the point.  The
-// whole-game k_selfplay_move launders its arguments at the head of every move,
-// so per-lane addresses are formed per move instead of once at the kernel
-// entry and kept (spilled) across the whole game.
-template <class T>
-__device__ __forceinline__ T* launder_global(T* p) {
-  unsigned long long x = reinterpret_cast<unsigned long long>(p);
-  asm volatile("" : "+s"(x));
-  return (T*)reinterpret_cast<__attribute__((address_space(1))) T*>(x);
-}
-// The search's f64 parameters made opaque per move as well: the constants
-// derived from them (the Gamma sampler's d and 1 / sqrt(9 d), f32 1 - eps)
-// are then formed per move instead of being hoisted to the kernel entry and
-// kept (spilled, k_selfplay_move<19,96>) across the whole game
-__device__ __forceinline__ double launder_f64(double v) {
-  unsigned long long x = (unsigned long long)__double_as_longlong(v);
-  asm volatile("" : "+s"(x));
-  return __longlong_as_double((long long)x);
-}
-__device__ __forceinline__ SearchParams launder_search(const SearchParams& p) {
-  SearchParams r = p;
-  r.c_puct = launder_f64(p.c_puct);
-  r.discount = launder_f64(p.discount);
-  r.dirichlet_alpha = launder_f64(p.dirichlet_alpha);
-  r.dirichlet_epsilon = launder_f64(p.dirichlet_epsilon);
-  r.pass_epsilon = launder_f64(p.pass_epsilon);
-  return r;
-}
-__device__ __forceinline__ NetParams launder_params(const NetParams& n) {
-  NetParams r;
-#define MZGO_L(f) r.f = launder_global(n.f);
-  MZGO_L(w_conv1) MZGO_L(b_conv1) MZGO_L(w_conv2) MZGO_L(b_conv2) MZGO_L(w_conv3) MZGO_L(b_conv3)
-  MZGO_L(w_dyn) MZGO_L(b_dyn) MZGO_L(emb) MZGO_L(head_w) MZGO_L(etab)
-  MZGO_L(hs.reward_b) MZGO_L(hs.fc1_w) MZGO_L(hs.fc1_b) MZGO_L(hs.fc2_w) MZGO_L(hs.fc2_b)
-  MZGO_L(hs.value_b) MZGO_L(hs.vfc_w) MZGO_L(hs.vfc_b) MZGO_L(hs.policy_b) MZGO_L(hs.pass_logit)
-#undef MZGO_L
-  return r;
-}
-
-__device__ __forceinline__ EngineArrays launder_arrays(const EngineArrays& e) {
-  EngineArrays r = e;
-#define MZGO_L(f) r.f = launder_global(e.f);
-  MZGO_L(pool) MZGO_L(prior) MZGO_L(child) MZGO_L(visits) MZGO_L(wsum) MZGO_L(root_prior) MZGO_L(path)
-  MZGO_L(nodes) MZGO_L(nact) MZGO_L(stones) MZGO_L(invd) MZGO_L(meta) MZGO_L(rec_stones) MZGO_L(rec_invd)
-  MZGO_L(rec_flags) MZGO_L(rec_action) MZGO_L(rec_value) MZGO_L(rec_policy) MZGO_L(rec_reward) MZGO_L(game_len)
-  MZGO_L(final_reward) MZGO_L(status) MZGO_L(jobs) MZGO_L(mpq) MZGO_L(counters) MZGO_L(stamps)
-#undef MZGO_L
-  return r;
-}
-
-template <class G>
-struct TreeViewOf {
-  __device__ __forceinline__ static TreeView make(const EngineArrays& E, int g) {
-    const size_t n1 = (size_t)E.S + 1;
-    TreeView T;
-    T.prior = E.prior + (size_t)g * n1 * G::A;
-    T.child = E.child + (size_t)g * n1 * G::A;
-    T.visits = E.visits + (size_t)g * n1;
-    T.wsum = E.wsum + (size_t)g * n1;
-    T.root_prior = E.root_prior + (size_t)g * G::A;
-    T.path = E.path + (size_t)g * (n1 + 1);
-    return T;
-  }
-};
-
-// LDS of one game's workgroup: direct-conv boards (weight DMA rings) ...
-template <class G, bool W = G::WINO>
-struct Smem {
-  union alignas(16) {
-    float in[G::CINMAX * G::CPAD];                       // conv staging
-    float hp[2 * 3 * G::CS];                             // head partials (after the conv loop)
-    struct { int label[G::CELLS], libs[G::CELLS], gsize[G::CELLS]; } scr;  // board step
-    ExpandLds<G, G::CINMAX * G::CPAD> f;   // factored expansion
-  } u;
-  alignas(16) float ring[RingBytes<G>::value / 4];       // weight DMA ring
-  TreeLds<G> t;
-  int8_t stone[G::CELLS];
-  uint8_t invd[G::CELLS];
-  int killed[4];
-  int misc[8];
-  int bc[8];                                             // broadcast slots
-  // a batching configuration's buffers were sized to the union's budget
-  // a batching configuration's buffers were sized to the union's budget (a
-  // non-batching one may grow the union: the kernels assert the whole Smem
-  // fits one CU's LDS)
-  static_assert(!ExpandLds<G, G::CINMAX * G::CPAD>::BATCH ||
-                    sizeof(ExpandLds<G, G::CINMAX * G::CPAD>) <= sizeof(float) * G::CINMAX * G::CPAD,
-                "the batched expansion's LDS must fit the conv staging it overlays");
-  __device__ float* heads() { return u.hp; }
-  __device__ float* ulds() { return u.in; }             // the union as scratch
-  static constexpr bool GLOBAL_Y = ExpandLds<G, G::CINMAX * G::CPAD>::GLOBAL_Y;
-  static constexpr int HEAD_PARTS = ConvShape<G::C>::NCOG;
-};
-
-// ... and Winograd boards (transformed input; exchange buffer + head partials)
-template <class G>
-struct Smem<G, true> {
-  union alignas(16) {
-    float in[8 * G::CPAD];                               // conv1 input (6 planes + 2 zero)
-    float v[Wino<G>::template v_floats<G::CINMAX>()];    // transformed conv input
-    struct {
-      float red[Wino<G>::template red_floats<G::C>()];
-      float hp[(G::C / 16) * 3 * Wino<G>::HS];   // head partials of one strip
-      alignas(16) float outs[G::C * Wino<G>::OUT_STRIDE];   // conv output staging
-    } x;
-    struct { int label[G::CELLS], libs[G::CELLS], gsize[G::CELLS]; } scr;  // board step
-    ExpandLds<G, Wino<G>::template v_floats<G::CINMAX>()> f;
-  } u;
-  alignas(16) float raw[WinoRaw<G>::FLOATS];              // per-wave staging of conv input rows
-  static constexpr bool STRIPS = Wino<G>::NSTRIP > 1;
-  alignas(16) float hfin[STRIPS ? 3 * G::CS : 4];         // strip boards: summed head partials
-  TreeLds<G> t;
-  int8_t stone[G::CELLS];
-  uint8_t invd[G::CELLS];
-  int killed[4];
-  int misc[8];
-  int bc[8];
-  static_assert(!ExpandLds<G, Wino<G>::template v_floats<G::CINMAX>()>::BATCH ||
-                    sizeof(ExpandLds<G, Wino<G>::template v_floats<G::CINMAX>()>) <=
-                        sizeof(float) * Wino<G>::template v_floats<G::CINMAX>(),
-                "the batched expansion's LDS must fit the Winograd input it overlays");
-  __device__ float* heads() { return STRIPS ? hfin : u.x.hp; }
-  __device__ float* ulds() { return u.v; }              // the union as scratch
-  static constexpr bool GLOBAL_Y = ExpandLds<G, Wino<G>::template v_floats<G::CINMAX>()>::GLOBAL_Y;
-  static constexpr int HEAD_PARTS = STRIPS ? 1 : G::C / 16;
-};
-
-// One latent conv: src ([CIN][src_stride], global) (+ emb per channel) ->
-// dst ([COUT][dst_stride], cells < out_cells), NH fused 1x1 head partials left
-// in sm.heads().  All threads; returns synchronised.
-// Factored Y of a conv (YM) written to LDS too, as the expansion's copy L.yc
-// (CACHE boards, one strip): yc overlays only the exchange buffer, which is
-// dead when the epilogue stores (wino_conv's YM store loop reads outs).
-template <class G>
-__device__ __forceinline__ float* y_lds_target(Smem<G>& sm) {
-  if constexpr (G::WINO && decltype(sm.u.f)::CACHE && Wino<G>::NSTRIP == 1) {
-    static_assert(sizeof(sm.u.f.yc) <= sizeof(sm.u.x.red), "the LDS Y copy overlays only the exchange buffer");
-    return sm.u.f.yc;
-  } else {
-    return nullptr;
-  }
-}
-// the head weights of the expansion (the rest of load_y, after a conv that
-// left Y in L.yc)
-template <class G>
-__device__ __forceinline__ void load_hw(Smem<G>& sm, const float* head_w) {
-  for (int i = tid_local(); i < 3 * G::C; i += G::THREADS) sm.u.f.hw[i] = head_w[i];
-}
-
-template <class G, int CIN, int COUT, int NH, bool YM = false>
-__device__ __forceinline__ void latent_conv(Smem<G>& sm, const float* __restrict__ w, const float* __restrict__ b,
-                                            const float* src, int src_stride, const float* emb, float* dst,
-                                            int dst_stride, int out_cells, const float* head_w,
-                                            Stamp* st = nullptr, float* ylds = nullptr) {
-  if constexpr (G::WINO) {
-    // row strips (19x19): strip s reads rows s*SROWS-1 .. (s+1)*SROWS of src,
-    // so src must not alias dst (representation ping-pongs through scratch)
-    for (int s = 0; s < Wino<G>::NSTRIP; ++s) {
-      wino_input<G, CIN>(sm.u.v, sm.raw, src, src_stride, emb, s, st);
-      if (st) st->lap(1);
-      wino_conv<G, CIN, COUT, NH, YM>(sm.u.v, sm.u.x.red, sm.u.x.hp, sm.u.x.outs, sm.hfin, w, b, dst, dst_stride,
-                                  out_cells, head_w, s, st, ylds);
-    }
-    if constexpr (Wino<G>::NSTRIP > 1) __syncthreads();   // hfin complete
-  } else {
-    stage_board<G>(sm.u.in, src, src_stride, CIN, emb);
-    __syncthreads();
-    if (st) st->lap(1);
-    conv3x3_ring<G, CIN, COUT, NH, YM>(sm.u.in, sm.ring, w, b, dst, dst_stride, out_cells, head_w, sm.u.hp, st);
-  }
-}
-
-// The dynamics conv of a node whose latent is rebuilt from its parent's Y
-// and E[a] (Winograd boards): latent_conv with wino_input_rebuilt as the
-// input transform -- no materialized copy of the latent.  All threads;
-// returns synchronised (strip boards) / with the stores issued (one strip).
-template <class G>
-__device__ __forceinline__ void latent_conv_rebuilt(Smem<G>& sm, const NetParams& np, const float* ypar,
-                                                    const float* ea, float* dst, Stamp* st = nullptr,
-                                                    float* ylds = nullptr, bool par_in_lds = false) {
-  if constexpr (G::WINO && Wino<G>::NSTRIP == 1) {
-    // (the second channel slab transformed under the GEMM's first K half)
-    wino_conv_rebuilt<G>(sm.u.v, sm.raw, sm.u.x.red, sm.u.x.hp, sm.u.x.outs, sm.hfin, ypar, ea, np.w_dyn, np.b_dyn,
-                         dst, st, ylds, par_in_lds ? ylds : nullptr);
-  } else if constexpr (G::WINO) {
-    for (int s = 0; s < Wino<G>::NSTRIP; ++s)
-      wino_conv_rebuilt<G>(sm.u.v, sm.raw, sm.u.x.red, sm.u.x.hp, sm.u.x.outs, sm.hfin, ypar, ea, np.w_dyn,
-                           np.b_dyn, dst, st, ylds, par_in_lds ? ylds : nullptr, s);
-    if constexpr (Wino<G>::NSTRIP > 1) __syncthreads();
-  }
-}
-
-template <class G>
-__device__ __forceinline__ BoardLds<G> board_lds(Smem<G>& sm) {
-  return make_board_lds<G>(sm.stone, sm.invd, sm.u.scr.label, sm.u.scr.libs, sm.u.scr.gsize, sm.killed, sm.misc);
-}
 
 // ---------------------------------------------------------------------------
 // representation (self_play.py:70-74) + prediction heads (:104-113).
@@ -348,12 +121,6 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
 // ---------------------------------------------------------------------------
 // One full MCTS.run (self_play.py:148-237) for game slot g.
 // ---------------------------------------------------------------------------
-// Game g's node slots: S+1 nodes + one scratch latent (slot S+1).
-template <class G>
-__device__ __forceinline__ float* pool_of(const EngineArrays& E, int g) {
-  return E.pool + (size_t)g * ((size_t)E.S + 2) * G::C * G::CS;
-}
-
 // Batch expansion (factored dynamics): children i < B of one parent whose Y
 // is in L.yc (and the head weights in L.hw), child i = node nid0 + i via
 // action L.acts[i]; one wave per child: E[a] into LDS, heads, the child's
@@ -524,437 +291,6 @@ __device__ __forceinline__ void batch_expand(Smem<G>& sm, const NetParams& np, c
   }
 }
 
-// Node n's Y (global, [CELLS][C]) and the head weights into the LDS copies
-// (GLOBAL_Y boards: the head weights and expand_wave's region-offset table
-// only).  All threads; the caller synchronises.
-template <class G>
-__device__ __forceinline__ void load_y(Smem<G>& sm, const float* y, const float* head_w) {
-  auto& L = sm.u.f;
-  typedef decltype(sm.u.f) XL;
-  if constexpr (XL::CACHE) {
-    const f32x4* src = reinterpret_cast<const f32x4*>(y);
-    f32x4* dst = reinterpret_cast<f32x4*>(L.yc);
-    for (int i = tid_local(); i < G::CELLS * G::C / 4; i += G::THREADS) dst[i] = src[i];
-  }
-  if constexpr (XL::CACHE || XL::BATCH)
-    for (int i = tid_local(); i < 3 * G::C; i += G::THREADS) L.hw[i] = head_w[i];
-  if constexpr (XL::GLOBAL_Y)
-    for (int i = tid_local(); i < XL::RPAIRS; i += G::THREADS) L.rpair[i] = ExpandPlan<G>::pair_entry(i >> 3, i & 7);
-}
-
-// ---------------------------------------------------------------------------
-// Batch expansions shared with helper workgroups (GLOBAL_Y boards, 19x19).
-// A 19x19 game has one workgroup, so with 64 games 192 CUs would idle; the
-// self-play launch adds sp.helpers workgroups (3 per game), and a game's
-// batch expansion (up to A children, each an L2 stream of its leaf's Y)
-// becomes a job that its workgroup and its helpers share: the game's
-// workgroup publishes the job (the actions, the leaf, the children's node
-// ids), every workgroup claims children a round of WAVES at a time, computes
-// them exactly as batch_expand does (the same function per child) and writes
-// the rows and backup values to HBM; the game's workgroup waits until all B
-// are done, then continues.  It never waits for a helper to START (it claims
-// children itself until none are left), so nothing depends on helpers being
-// resident.  Hand-offs: agent-scope release / relaxed flag / agent-scope
-// acquire (cdna_hip_programming.md Guideline 16); claims: a CAS on one
-// 64-bit word (batch number << 32 | next child), so a claim of a finished
-// batch fails.
-// ---------------------------------------------------------------------------
-__host__ __device__ constexpr int job_bytes(int A) {
-  return 512 + 2 * ((A * 8 + 255) / 256 * 256) + (A + 255) / 256 * 256 + ((A - 1 + 15) / 16 * 16 * 12 + 255) / 256 * 256;
-}
-constexpr unsigned kJobExit = 0xFFFFFFFFu;
-// s_sleep units (64 clocks) between polls: a game waiting for its job's units,
-// a helper waiting for the next job ((1, 2) measured the same)
-constexpr int kJobWaitSleep = 4, kJobPollSleep = 8;
-struct JobView {
-  unsigned char* base;
-  __device__ unsigned long long* claim() const { return reinterpret_cast<unsigned long long*>(base); }
-  __device__ unsigned* seq() const { return reinterpret_cast<unsigned*>(base + 64); }
-  __device__ unsigned* done() const { return reinterpret_cast<unsigned*>(base + 128); }
-  // B, nid0 (conv: the parent), leaf, net, kind (0 batch, 1 conv of src, 2 conv of a rebuilt latent,
-  // 3 replay checks), action (3: the root action), depth, batch size
-  __device__ int* info() const { return reinterpret_cast<int*>(base + 192); }
-  __device__ double* pass_prior() const { return reinterpret_cast<double*>(base + 224); }
-  // replay checks: the failing simulations found by every workgroup (bit i)
-  __device__ unsigned long long* failm() const { return reinterpret_cast<unsigned long long*>(base + 256); }
-  // 1 once the game's workgroup runs (zeroed by the host before the launch):
-  // tail helpers join only started games -- one not yet dispatched may be
-  // waiting for the very CU a helper holds
-  __device__ unsigned* started() const { return reinterpret_cast<unsigned*>(base + 384); }
-  // tail helpers registered with this game (9x9 whole-game launches, tail_help)
-  __device__ unsigned* nhelp() const { return reinterpret_cast<unsigned*>(base + 448); }
-  // the actions, tagged: batch number << 32 | action (an entry is valid for
-  // the batch whose number it carries: no separate progress counter)
-  __device__ unsigned long long* acts() const { return reinterpret_cast<unsigned long long*>(base + 512); }
-  __device__ double* bv(int A) const { return reinterpret_cast<double*>(base + 512 + (A * 8 + 255) / 256 * 256); }
-  // the root's valid mask (child_priors reads it)
-  __device__ uint8_t* valid(int A) const {
-    return base + 512 + 2 * ((A * 8 + 255) / 256 * 256);
-  }
-  // representation conv3: the head sums per cell [3][CS] of every strip
-  __device__ float* hfin(int A) const {
-    return reinterpret_cast<float*>(base + 512 + 2 * ((A * 8 + 255) / 256 * 256) + (A + 255) / 256 * 256);
-  }
-};
-template <class G>
-__device__ __forceinline__ JobView job_of(const EngineArrays& E, int g) {
-  return JobView{E.jobs + (size_t)g * job_bytes(G::A)};
-}
-
-// the parent convs and batch expansions go through jobs: 19x19 (Y streamed
-// from L2, strip convs) with helper workgroups in the launch
-template <class G>
-__device__ __forceinline__ bool shared_jobs(const SearchParams& sp) {
-  if constexpr (Smem<G>::GLOBAL_Y && G::WINO) return Wino<G>::NSTRIP > 1 && sp.helpers > 0;
-  else return false;
-}
-
-// A job's batch number (unique within a launch: the host zeroes the jobs
-// before it) with the claim word and the done counter reset for it.  Thread 0.
-//
-// The claim word is batch << 32 | total << 16 | next: a claim is decided by
-// the word alone, never by the job's info block.  A helper that acquired
-// batch s can read info rows the game's workgroup is already rewriting for
-// s + 1 (the game claims every unit of s itself when no helper comes, waits
-// for them and begins s + 1 at once); its CAS on the word of s then fails
-// whatever total that info says, because s's word is exhausted (next >=
-// total) before the game can begin s + 1, and the new word carries s + 1.
-// A successful claim of s therefore means s is still open, so every info
-// row the helper read belongs to s, and no stale done add can reach s + 1.
-__device__ __forceinline__ unsigned job_begin(const JobView& J, int total, unsigned first = 0) {
-  const unsigned bseq = __hip_atomic_load(J.seq(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-  if (tid_local() == 0) {
-    __hip_atomic_store(J.done(), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(J.claim(), (unsigned long long)bseq << 32 | (unsigned)total << 16 | first, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  }
-  return bseq;
-}
-// every store of the workgroup drained, then (release) the batch number.  All threads.
-__device__ __forceinline__ void job_publish(const JobView& J, unsigned bseq) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid_local() == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (ROCm 7.2 may drop the fence's own wait)
-    __hip_atomic_store(J.seq(), bseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-// this workgroup's `mine` units added; wait until all `total` are done
-// (every helper adds after its release), then acquire.  All threads.
-__device__ __forceinline__ void job_wait(const JobView& J, int mine, int total) {
-  if (tid_local() == 0) {
-    unsigned d = __hip_atomic_fetch_add(J.done(), (unsigned)mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + mine;
-    while (d < (unsigned)total) {
-      __builtin_amdgcn_s_sleep(kJobWaitSleep);
-      d = __hip_atomic_load(J.done(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __syncthreads();
-}
-// claim the next unit of batch bseq (of total): -1 when none is left.  Thread 0
-// claims, the workgroup gets it through LDS.  All threads.
-template <class G>
-__device__ __forceinline__ int job_claim(Smem<G>& sm, const JobView& J, unsigned bseq, int total, int step) {
-  if (tid_local() == 0) {
-    int c0 = -1;
-    unsigned long long c = __hip_atomic_load(J.claim(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (;;) {                                       // (a failed CAS means another claim succeeded)
-      // (the word's own total decides: see job_begin; `total` is the caller's copy)
-      if ((unsigned)(c >> 32) != bseq || (int)(c & 0xFFFFu) >= (int)((c >> 16) & 0xFFFFu)) break;
-      if (__hip_atomic_compare_exchange_strong(J.claim(), &c, c + step, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT)) {
-        c0 = (int)(c & 0xFFFFu);
-        break;
-      }
-    }
-    sm.bc[1] = c0;
-  }
-  __syncthreads();
-  const int c0 = sm.bc[1];
-  __syncthreads();                                   // (bc[1] is rewritten by the next claim)
-  return c0;
-}
-
-// The dynamics conv of a parent as a job (19x19: 5 row strips, each strip
-// independent given the input): its input -- src ([C][CS], the root's
-// latent) or, with ypar, the latent rebuilt from the parent's Y and E[a]
-// (wino_input_rebuilt: no materialized copy) -- -> dst (its Y, [CELLS][C]);
-// strips claimed one at a time.  Returns this workgroup's strips.  All threads.
-template <class G>
-__device__ __forceinline__ int conv_strips(Smem<G>& sm, const NetParams& np, const JobView& J, unsigned bseq,
-                                           const float* src, float* dst, const float* ypar = nullptr,
-                                           const float* ea = nullptr) {
-  int mine = 0;
-  if constexpr (G::WINO) {
-    for (int s; (s = job_claim(sm, J, bseq, Wino<G>::NSTRIP, 1)) >= 0; ++mine) {
-      if (ypar) {
-        // (the second channel slab transformed under the GEMM's first K half)
-        wino_conv_rebuilt<G>(sm.u.v, sm.raw, sm.u.x.red, sm.u.x.hp, sm.u.x.outs, sm.hfin, ypar, ea, np.w_dyn,
-                             np.b_dyn, dst, nullptr, nullptr, nullptr, s);
-      } else {
-        wino_input<G, G::C>(sm.u.v, sm.raw, src, G::CS, nullptr, s);
-        wino_conv<G, G::C, G::C, 0, true>(sm.u.v, sm.u.x.red, sm.u.x.hp, sm.u.x.outs, sm.hfin, np.w_dyn, np.b_dyn,
-                                           dst, G::CS, G::CS, nullptr, s);
-      }
-    }
-  }
-  __syncthreads();
-  return mine;
-}
-
-// The game's workgroup: the conv of node `leaf` over the job machinery
-// (dst = its pool slot).  Input: src (HBM, par < 0) or the latent rebuilt
-// from parent par's Y and action act's E rows.  All threads; returns
-// synchronised with dst complete and acquired.
-// pre(bseq): work of the game's workgroup between the publish and its
-// first strip claim (the next batch's picks: pick_all, wave 0), while the
-// helpers start on the strips.
-struct NoPre {
-  __device__ void operator()(unsigned) const {}
-};
-template <class G, class Pre = NoPre>
-__device__ __forceinline__ void conv_shared(Smem<G>& sm, const NetParams& np, const EngineArrays& E, int g,
-                                            int leaf, int net, const float* src, float* dst,
-                                            Stamp* st = nullptr, int par = -1, int act = 0, Pre pre = Pre{}) {
-  const JobView J = job_of<G>(E, g);
-  const unsigned bseq = job_begin(J, Wino<G>::NSTRIP);
-  if (tid_local() == 0) {
-    int* info = J.info();
-    info[0] = Wino<G>::NSTRIP; info[1] = par; info[2] = leaf; info[3] = net; info[4] = par >= 0 ? 2 : 1;
-    info[5] = act;
-  }
-  job_publish(J, bseq);                              // (src / the parent's Y reach the helpers)
-  pre(bseq);
-  if (st) st->lap(52);
-  const float* ypar = par >= 0 ? pool_of<G>(E, g) + (size_t)par * G::C * G::CS : nullptr;
-  const int mine = conv_strips<G>(sm, np, J, bseq, src, dst, ypar, np.etab + (size_t)act * 9 * G::C);
-  if (st) st->lap(53);
-  job_wait(J, mine, Wino<G>::NSTRIP);
-  if (st) st->lap(54);
-}
-
-// ---------------------------------------------------------------------------
-// The epoch tail at 9x9 (one-strip Winograd boards, the tree in LDS): in a
-// whole-game launch the games end at different moves, and the last ones
-// finish alone on their CUs (~29 % of an epoch's CU-time idle).  A workgroup
-// whose game has ended registers (JobView::nhelp) with a running game that
-// has fewer than kTailHelpers helpers and serves its parent convs: a game
-// that sees a helper registered publishes its next parent conv as a job of
-// kTailUnits units -- unit u = cout tiles 2u, 2u + 1 (wino_conv's m0 / nm) --
-// claims units itself too (it never waits for a helper to start), waits for
-// all, and loads the whole Y from L2 into its LDS copy.  Every workgroup
-// computes the full Winograd input (from the parent's Y in the pool; the
-// second slab under its first unit's GEMM, wino_conv_rebuilt) once per job and
-// each unit's tiles' GEMM + epilogue exactly as the whole conv does,
-// so the records do not depend on who computed what (MZGO_TAIL_HELPERS=0 A/B).
-// Hand-offs: the job machinery above (release / relaxed flag / acquire).
-// ---------------------------------------------------------------------------
-constexpr int kTailUnits = 3;           // (granularity measured)
-constexpr unsigned kTailHelpers = 2;
-constexpr int kTailTiles = 6 / kTailUnits;     // cout tiles per unit
-constexpr int kJobTailConv = 6;        // JobView info[4] of a tail conv job
-
-template <class G>
-struct TailConvs {
-  static constexpr bool value = [] {
-    if constexpr (G::WINO) return Wino<G>::NSTRIP == 1 && !Smem<G>::GLOBAL_Y && G::C == 6 * 16;
-    else return false;
-  }();
-};
-
-// Units of tail conv job bseq of game E/g claimed by this workgroup: V from
-// the parent's Y once, then each unit's two cout tiles (red in the raw planes,
-// whose zero halo is restored afterwards); Y stores drained.  All threads.
-template <class G>
-__device__ __forceinline__ int tail_conv_units(Smem<G>& sm, const NetParams& np, const JobView& J, unsigned bseq,
-                                               const float* ypar, const float* ea, float* dst,
-                                               const float* ylds_par = nullptr) {
-  int mine = 0;
-  if constexpr (TailConvs<G>::value) {
-    for (int u; (u = job_claim(sm, J, bseq, kTailUnits, 1)) >= 0; ++mine) {
-      if (mine == 0)   // (the second slab transformed under the first unit's GEMM, by every wave)
-        wino_conv_rebuilt<G>(sm.u.v, sm.raw, sm.raw, sm.u.x.hp, sm.u.x.outs, sm.hfin, ypar, ea, np.w_dyn, np.b_dyn,
-                             dst, nullptr, nullptr, ylds_par, 0, kTailTiles * u, kTailTiles);
-      else
-        wino_conv<G, G::C, G::C, 0, true>(sm.u.v, sm.raw, sm.u.x.hp, sm.u.x.outs, sm.hfin, np.w_dyn, np.b_dyn, dst,
-                                          G::CS, G::CS, nullptr, 0, nullptr, nullptr, kTailTiles * u, kTailTiles);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this workgroup's Y stores done
-    __syncthreads();
-    if (mine > 0) wino_raw_zero<G>(sm.raw);
-  }
-  return mine;
-}
-
-// The game's workgroup: the parent conv of node `leaf` (its latent rebuilt
-// from parent par's Y and action act's E rows) as a tail job; returns with
-// Y in the pool slot and, when ylds, in the expansion's LDS copy.  All threads.
-template <class G>
-__device__ __forceinline__ void conv_tail(Smem<G>& sm, const NetParams& np, const EngineArrays& E, int g, int leaf,
-                                          int par, int act, int net, float* dst, float* ylds, bool par_in_lds,
-                                          Stamp* st = nullptr) {
-  if constexpr (TailConvs<G>::value) {
-    const JobView J = job_of<G>(E, g);
-    const unsigned bseq = job_begin(J, kTailUnits);
-    if (tid_local() == 0) {
-      int* info = J.info();
-      info[0] = kTailUnits; info[1] = par; info[2] = leaf; info[3] = net; info[4] = kJobTailConv; info[5] = act;
-    }
-    job_publish(J, bseq);                            // (the parent's Y in the pool reaches the helpers)
-    if (st) st->lap(52);
-    const float* ypar = pool_of<G>(E, g) + (size_t)par * G::C * G::CS;
-    const int mine = tail_conv_units<G>(sm, np, J, bseq, ypar, np.etab + (size_t)act * 9 * G::C, dst,
-                                        par_in_lds ? ylds : nullptr);
-    if (st) st->lap(53);
-    job_wait(J, mine, kTailUnits);
-    if (st) st->lap(54);
-    if (tid_local() == 0) atomicAdd(&E.counters[4], 1ull);
-    if (ylds) {
-      const f32x4* src = reinterpret_cast<const f32x4*>(dst);
-      f32x4* d = reinterpret_cast<f32x4*>(ylds);
-      for (int i = tid_local(); i < G::CELLS * G::C / 4; i += G::THREADS) d[i] = src[i];
-    }
-    __syncthreads();
-  }
-}
-
-// A workgroup whose game has ended: serve running games' tail conv jobs until
-// none is left to register with.  All threads.
-template <class G>
-__device__ __forceinline__ void tail_help(Smem<G>& sm, const NetParams& np_a, const NetParams& np_b,
-                                          const EngineArrays& E, int self, int games) {
-  if constexpr (TailConvs<G>::value) {
-    wino_raw_zero<G>(sm.raw);                          // (an ended slot's workgroup never zeroed its planes)
-    for (;;) {
-      // a running game (its seq not kJobExit) with fewer than kTailHelpers
-      // helpers, the nearest after this one
-      if (tid_local() == 0) {
-        int pick = -1;
-        for (int k = 1; k < games && pick < 0; ++k) {
-          const int t = (self + k) % games;
-          const JobView Jt = job_of<G>(E, t);
-          if (__hip_atomic_load(Jt.started(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 ||
-              __hip_atomic_load(Jt.seq(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == kJobExit)
-            continue;
-          unsigned c = __hip_atomic_load(Jt.nhelp(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          while (c < kTailHelpers &&
-                 !__hip_atomic_compare_exchange_strong(Jt.nhelp(), &c, c + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT)) {
-          }
-          if (c < kTailHelpers) pick = t;
-        }
-        sm.bc[2] = pick;
-      }
-      __syncthreads();
-      const int t = sm.bc[2];
-      __syncthreads();
-      if (t < 0) return;
-      const JobView J = job_of<G>(E, t);
-      float* pool = pool_of<G>(E, t);
-      unsigned last = 0;
-      for (;;) {
-        if (tid_local() == 0) {
-          unsigned s = __hip_atomic_load(J.seq(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          for (long long spins = 0; (s == last || s == 0) && spins < (1ll << 24); ++spins) {
-            __builtin_amdgcn_s_sleep(kJobPollSleep);
-            s = __hip_atomic_load(J.seq(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          int expired = 0;
-          if (s == last || s == 0) {                   // (bounded wait: leave, and exit -- no re-registering)
-            __hip_atomic_fetch_sub(J.nhelp(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            atomicAdd(&E.counters[7], 1ull);           // (counted: bench lines report expiries)
-            s = kJobExit;
-            expired = 1;
-          }
-          if (s != kJobExit) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          sm.bc[2] = (int)s;
-          sm.bc[4] = expired;
-        }
-        __syncthreads();
-        const unsigned s = (unsigned)sm.bc[2];
-        const int expired = sm.bc[4];
-        __syncthreads();
-        if (expired) return;
-        if (s == kJobExit) break;
-        last = s;
-        const int* info = J.info();
-        const int par = info[1], leaf = info[2], net = info[3], kind = info[4], act = info[5];
-        if (kind != kJobTailConv) continue;
-        const NetParams np = select_params(net != 0, np_b, np_a);
-#ifdef MZGO_STAMPS
-        const unsigned long long tu = __builtin_amdgcn_s_memtime();
-#endif
-        const int mine = tail_conv_units<G>(sm, np, J, s, pool + (size_t)par * G::C * G::CS,
-                                            np.etab + (size_t)act * 9 * G::C, pool + (size_t)leaf * G::C * G::CS);
-#ifdef MZGO_STAMPS
-        // slots 44-46: a helper's cycles computing tail units, units, jobs served
-        if (tid_local() == 0 && E.stamps) {
-          unsigned long long* sl = E.stamps + (size_t)blockIdx.x * kStampPhases;
-          sl[44] += __builtin_amdgcn_s_memtime() - tu;
-          sl[45] += (unsigned long long)mine;
-          sl[46] += mine > 0 ? 1ull : 0ull;
-        }
-#endif
-        if (tid_local() == 0 && mine > 0) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (ROCm 7.2 may drop the fence's own wait)
-          __hip_atomic_fetch_add(J.done(), (unsigned)mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-    }
-  }
-}
-
-// The representation's conv2 (CIN 64 -> 64) and conv3 (64 -> C, value and
-// policy head sums per cell into hfin) of a 19x19 root as strip jobs (kinds
-// 4, 5): src -> dst, both [CIN][CS] / [COUT][CS] in HBM (factored search:
-// the scratch slot and node 0's slot).  Returns this workgroup's strips.
-template <class G, int CIN, int COUT, int NH>
-__device__ __forceinline__ int rep_strips(Smem<G>& sm, const JobView& J, unsigned bseq, const float* w,
-                                          const float* b, const float* src, float* dst, const float* head_w,
-                                          float* hfin) {
-  int mine = 0;
-  if constexpr (G::WINO) {
-    for (int s; (s = job_claim(sm, J, bseq, Wino<G>::NSTRIP, 1)) >= 0; ++mine) {
-      wino_input<G, CIN>(sm.u.v, sm.raw, src, G::CS, nullptr, s);
-      wino_conv<G, CIN, COUT, NH>(sm.u.v, sm.u.x.red, sm.u.x.hp, sm.u.x.outs, hfin, w, b, dst, G::CS, G::CS,
-                                  head_w, s);
-    }
-  }
-  __syncthreads();
-  return mine;
-}
-
-// The game's workgroup: representation conv k (2 or 3) over the job
-// machinery; conv3's head sums come back into sm.hfin.  All threads;
-// returns synchronised.
-template <class G>
-__device__ __forceinline__ void rep_shared(Smem<G>& sm, const NetParams& np, const EngineArrays& E, int g, int net,
-                                           int k) {
-  if constexpr (G::WINO && Wino<G>::NSTRIP > 1) {
-  const JobView J = job_of<G>(E, g);
-  float* pool = pool_of<G>(E, g);
-  float* lat = pool + (size_t)(E.S + 1) * G::C * G::CS;
-  const unsigned bseq = job_begin(J, Wino<G>::NSTRIP);
-  if (tid_local() == 0) {
-    int* info = J.info();
-    info[0] = Wino<G>::NSTRIP; info[1] = 0; info[2] = 0; info[3] = net; info[4] = k == 2 ? 4 : 5;
-  }
-  job_publish(J, bseq);                              // (conv k's input reaches the helpers)
-  const int mine = k == 2 ? rep_strips<G, 64, 64, 0>(sm, J, bseq, np.w_conv2, np.b_conv2, lat, pool, nullptr, sm.hfin)
-                          : rep_strips<G, 64, G::C, 2>(sm, J, bseq, np.w_conv3, np.b_conv3, pool, lat,
-                                                       np.head_w + G::C, J.hfin(G::A));
-  job_wait(J, mine, Wino<G>::NSTRIP);
-  if (k == 3)
-    for (int i = tid_local(); i < 2 * G::CS; i += G::THREADS) sm.hfin[i] = J.hfin(G::A)[i];
-  __syncthreads();
-  }
-}
-
 // One child of a batch by ONE wave (batch_expand's per-child work): E[a]
 // into W.ew, expand_wave over Y, the heads, the child's prior row and child
 // row; returns the backup value r + discount * v (every lane).  Lazy policy
@@ -1006,10 +342,11 @@ __device__ __forceinline__ double expand_child(Smem<G>& sm, const NetParams& np,
 // The children of job J (batch bseq, B children, node ids nid0 + k, actions
 // in L.acts) a round of WAVES at a time, claimed by CAS; each child's backup
 // value goes to J.bv (HBM).  Returns this workgroup's count.  All threads.
-template <class G, bool LAZY, bool LAZYH = false>
+// (kJobBatch's share; declared with its defaults in mzgo_jobs.hpp)
+template <class G, bool LAZY, bool LAZYH>
 __device__ __forceinline__ int job_rounds(Smem<G>& sm, const NetParams& np, const SearchParams& sp,
                                           const TreeView& TV, const float* yg, const JobView& J, unsigned bseq,
-                                          int B, int nid0, bool helper = false, Stamp* st = nullptr) {
+                                          int B, int nid0, bool helper, Stamp* st) {
   auto& L = sm.u.f;
   const int wave = __builtin_amdgcn_readfirstlane(wave_id());
   ExpandPlan<G> plan;
@@ -1043,10 +380,7 @@ __device__ __forceinline__ int job_rounds(Smem<G>& sm, const NetParams& np, cons
 // The game's workgroup: batch_expand over the job machinery (B children of
 // leaf `leaf` whose Y is yg, actions in L.acts, node ids nid0 + k); L.bv
 // gets every child's backup value.
-struct NoWait {
-  __device__ void operator()() const {}
-};
-template <class G, bool LAZY, class Wait = NoWait>
+template <class G, bool LAZY, class Wait = NoExtra>
 __device__ __forceinline__ void batch_expand_shared(Smem<G>& sm, const NetParams& np, const SearchParams& sp,
                                                     const EngineArrays& E, int g, const TreeView& TV, int B,
                                                     int nid0, int leaf, int net, const float* yg,
@@ -1055,20 +389,19 @@ __device__ __forceinline__ void batch_expand_shared(Smem<G>& sm, const NetParams
                                                     Wait pre_wait = Wait{}) {
   auto& L = sm.u.f;
   const JobView J = job_of<G>(E, g);
-  const unsigned bseq = job_begin(J, B);
+  const JobInfo I = job_info(kJobBatch, B, nid0, leaf, net);
   // the job first (geometry, the root's mask, the actions known already:
   // i0 of them), then the picks (pick_all, wave 0; tagged entries: a helper
   // that claims a round before they are out waits for its entry)
-  for (int a = tid_local(); a < G::A; a += G::THREADS) J.valid(G::A)[a] = sm.t.valid[a];
-  if (tid_local() == 0) {
-    int* info = J.info();
-    info[0] = B; info[1] = nid0; info[2] = leaf; info[3] = net; info[4] = 0;
-    *J.pass_prior() = sm.t.pass_prior;
-    for (int k = 0; k < i0; ++k)
-      __hip_atomic_store(J.acts() + k, (unsigned long long)bseq << 32 | (unsigned)L.acts[k], __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-  }
-  job_publish(J, bseq);
+  const unsigned bseq = job_post(J, I, 0, [&](unsigned bs) {
+    for (int a = tid_local(); a < G::A; a += G::THREADS) J.valid(G::A)[a] = sm.t.valid[a];
+    if (tid_local() == 0) {
+      J.h->pass_prior = sm.t.pass_prior;
+      for (int k = 0; k < i0; ++k)
+        __hip_atomic_store(J.acts() + k, (unsigned long long)bs << 32 | (unsigned)L.acts[k], __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+  });
   if (st) st->lap(40);
   // (prepicked: the actions i0.. went out during the parent's conv job,
   // tagged for this batch; the workgroup reads them from the job like a
@@ -1082,7 +415,7 @@ __device__ __forceinline__ void batch_expand_shared(Smem<G>& sm, const NetParams
   if (prepicked)
     for (int k = tid_local(); k < B; k += G::THREADS)
       L.acts[k] = (int)(unsigned)__hip_atomic_load(J.acts() + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  pre_wait();                                        // (the replay checks' first level rows, verify_preload)
+  pre_wait(bseq);                                    // (the replay checks' first level rows, verify_preload)
   job_wait(J, mine, B);
   const double* bvg = J.bv(G::A);
   for (int k = tid_local(); k < B; k += G::THREADS) L.bv[k] = bvg[k];
@@ -1167,7 +500,7 @@ __device__ __forceinline__ int root_batch(Smem<G>& sm, const NetParams& np, cons
     // batch's LDS buffers are filled only after it.  (Shared jobs: the picks
     // go out while the helpers run the conv's strips.)
     if (shared_jobs<G>(sp)) {
-      conv_shared<G>(sm, np, E, g, 0, sp.net, scratch, pool, st, -1, 0, [&](unsigned cb) {
+      conv_shared<G>(sm, np, E, g, 0, sp.net, st, -1, 0, [&](unsigned cb) {
         if (wave_id() == 0) pick_all<G>(el, n, 0, K, key, 0, L.acts, st, job_of<G>(E, g).acts(), cb + 1);
       });
     } else {
@@ -1532,6 +865,44 @@ __device__ __forceinline__ void verify_preload(Smem<G>& sm, const SearchParams& 
   }
 }
 
+// kJobReplay's share: groups of I.group() levels of the depth-I.depth path,
+// claimed one at a time (preloaded: group 0 first, its level rows are in vl
+// and its unit was taken at the post); the failing simulations this
+// workgroup found are ORed into J.failm.  Returns its groups.  All threads.
+template <class G, class Acc>
+__device__ __forceinline__ int replay_share(Smem<G>& sm, const SearchParams& sp, const TreeView& TV, const Acc& T,
+                                            const int* nact, const JobView& J, const JobInfo& I, unsigned bseq,
+                                            Stamp* st = nullptr, bool preloaded = false) {
+  typedef VerifyLds<G, verify_depth<G>()> V;
+  V& vl = *reinterpret_cast<V*>(&sm.u.f.wv[0]);
+  const int gs = I.group(), D = I.depth;
+  int mine = 0;
+  if (preloaded) {
+    verify_levels<G, Acc>(sm, sp, TV, T, nact, D, I.batch, 0, min(gs, D), I.act, false, st, true);
+    ++mine;
+  }
+  for (int grp; (grp = job_claim(sm, J, bseq, I.units, 1)) >= 0; ++mine)
+    verify_levels<G, Acc>(sm, sp, TV, T, nact, D, I.batch, grp * gs, min(gs, D - grp * gs), I.act, false, st);
+  if (mine > 0 && tid_local() < G::AP && vl.failm[tid_local()])
+    __hip_atomic_fetch_or(J.h->failm + tid_local(), (unsigned long long)vl.failm[tid_local()], __ATOMIC_RELAXED,
+                          __HIP_MEMORY_SCOPE_AGENT);
+  return mine;
+}
+// A helper's share (declared in mzgo_jobs.hpp): the batch's values and an
+// empty fail mask into its LDS first.
+template <class G>
+__device__ __forceinline__ int replay_help(Smem<G>& sm, const SearchParams& sp, const EngineArrays& E, int g,
+                                           const TreeView& TV, const JobView& J, const JobInfo& I, unsigned bseq) {
+  typedef VerifyLds<G, verify_depth<G>()> V;
+  V& vl = *reinterpret_cast<V*>(&sm.u.f.wv[0]);
+  const double* bvg = J.bv(G::A);
+  for (int k = tid_local(); k < I.batch; k += G::THREADS) sm.u.f.bv[k] = bvg[k];
+  if (tid_local() < G::AP) vl.failm[tid_local()] = 0;
+  __syncthreads();
+  const TreeAcc<G, false> T(TV, sm.t);
+  return replay_share<G, TreeAcc<G, false>>(sm, sp, TV, T, E.nact + (size_t)g * ((size_t)E.S + 1), J, I, bseq);
+}
+
 template <class G, class Acc>
 __device__ __forceinline__ int verify_batch(Smem<G>& sm, const SearchParams& sp, const EngineArrays& E, int g,
                                             const TreeView& TV, Acc& T, int* nact, int leaf, int D, int B, int nid,
@@ -1555,39 +926,25 @@ __device__ __forceinline__ int verify_batch(Smem<G>& sm, const SearchParams& sp,
   // (preloaded: group 0's level rows are in vl already -- the game's
   // workgroup checks group 0 itself, first)
   const VerifyPlan vp = verify_plan<G, Acc>(sp, D);
-  const int gs = vp.gs, ngroups = vp.ngroups;
-  const bool shared = vp.shared;
-  if (shared) {
+  if (vp.shared) {
     const JobView J = job_of<G>(E, g);
-    const unsigned bseq = job_begin(J, ngroups, preloaded ? 1u : 0u);
-    if (tid_local() == 0) {
-      int* info = J.info();
-      info[0] = ngroups; info[1] = nid; info[2] = leaf; info[3] = gs; info[4] = 3;
-      info[5] = sm.t.ract; info[6] = D; info[7] = B;
-    }
-    if (tid_local() < G::AP) __hip_atomic_store(J.failm() + tid_local(), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    job_publish(J, bseq);                          // (J.bv holds the batch's values already)
-    int mine = 0;
-    if (preloaded) {
-      verify_levels<G, Acc>(sm, sp, TV, T, nact, D, B, 0, vp.g0, sm.t.ract, false, st, true);
-      ++mine;
-    }
-    for (int grp; (grp = job_claim(sm, J, bseq, ngroups, 1)) >= 0; ++mine)
-      verify_levels<G, Acc>(sm, sp, TV, T, nact, D, B, grp * gs, min(gs, D - grp * gs), sm.t.ract, false, st);
-    if (mine > 0 && tid_local() < G::AP && vl.failm[tid_local()])
-      __hip_atomic_fetch_or(J.failm() + tid_local(), (unsigned long long)vl.failm[tid_local()], __ATOMIC_RELAXED,
-                            __HIP_MEMORY_SCOPE_AGENT);
+    const JobInfo I = job_info(kJobReplay, vp.ngroups, nid, leaf, vp.gs, sm.t.ract, D, B);
+    const unsigned bseq = job_post(J, I, preloaded ? 1u : 0u, [&](unsigned) {   // (J.bv holds the values already)
+      if (tid_local() < G::AP)
+        __hip_atomic_store(J.h->failm + tid_local(), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    });
+    const int mine = replay_share<G, Acc>(sm, sp, TV, T, nact, J, I, bseq, st, preloaded);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    job_wait(J, mine, ngroups);
+    job_wait(J, mine, I.units);
     if (tid_local() < G::AP)
-      vl.failm[tid_local()] = __hip_atomic_load(J.failm() + tid_local(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      vl.failm[tid_local()] = __hip_atomic_load(J.h->failm + tid_local(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   } else {
     for (int l0 = 0; l0 < D; l0 += DV)
       verify_levels<G, Acc>(sm, sp, TV, T, nact, D, B, l0, D - l0 < DV ? D - l0 : DV, sm.t.ract, l0 == 0, st,
                             preloaded && l0 == 0);
   }
-  if ((D == 0 || shared) && tid_local() == 0) prefix_sums<G>(T.ws(0), bv, B, alt && ((D + 1) & 1), vl.wroot);
+  if ((D == 0 || vp.shared) && tid_local() == 0) prefix_sums<G>(T.ws(0), bv, B, alt && ((D + 1) & 1), vl.wroot);
   if (tid_local() == 0) {
     int f = B;
 #pragma unroll
@@ -1635,151 +992,6 @@ __device__ __forceinline__ int verify_batch(Smem<G>& sm, const SearchParams& sp,
   if (st) st->lap(74);
   return m;
   }
-}
-
-// A helper workgroup of game g (k_selfplay_move's blocks past the games):
-// jobs until the game's workgroup posts kJobExit (or none comes for ~seconds):
-// batch expansions, parent convs and replay checks.
-template <class G>
-__device__ __forceinline__ void helper_loop(Smem<G>& sm, const NetParams& np_a, const NetParams& np_b,
-                                            const SearchParams& sp, const EngineArrays& E, int g) {
-  const JobView J = job_of<G>(E, g);
-  const TreeView TV = TreeViewOf<G>::make(E, g);
-  float* pool = pool_of<G>(E, g);
-  unsigned last = 0;
-  for (;;) {
-    if (tid_local() == 0) {
-      unsigned s = __hip_atomic_load(J.seq(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (long long spins = 0; (s == last || s == 0) && spins < (1ll << 26); ++spins) {
-        __builtin_amdgcn_s_sleep(kJobPollSleep);
-        s = __hip_atomic_load(J.seq(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (s == last || s == 0) s = kJobExit;           // (bounded wait: give up)
-      if (s != kJobExit) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      sm.bc[2] = (int)s;
-    }
-    __syncthreads();
-    const unsigned s = (unsigned)sm.bc[2];
-    if (s == kJobExit) return;
-    last = s;
-    const int* info = J.info();
-    const int B = info[0], nid0 = info[1], leaf = info[2], net = info[3], kind = info[4];
-    const NetParams np = select_params(net != 0, np_b, np_a);
-    if (kind == 3) {                                   // replay checks of a batch (verify_batch)
-      constexpr int DV = verify_depth<G>();
-      typedef VerifyLds<G, DV> V;
-      V& vl = *reinterpret_cast<V*>(&sm.u.f.wv[0]);
-      const int ngroups = B, gs = info[3], ract = info[5], D = info[6], nb = info[7];
-      const double* bvg = J.bv(G::A);
-      for (int k = tid_local(); k < nb; k += G::THREADS) sm.u.f.bv[k] = bvg[k];
-      if (tid_local() < G::AP) vl.failm[tid_local()] = 0;
-      __syncthreads();
-      const TreeAcc<G, false> T(TV, sm.t);
-      const int* nact = E.nact + (size_t)g * ((size_t)E.S + 1);
-      int mine = 0;
-      for (int grp; (grp = job_claim(sm, J, s, ngroups, 1)) >= 0; ++mine)
-        verify_levels<G, TreeAcc<G, false>>(sm, sp, TV, T, nact, D, nb, grp * gs, min(gs, D - grp * gs), ract,
-                                            false);
-      if (mine > 0 && tid_local() < G::AP && vl.failm[tid_local()])
-        __hip_atomic_fetch_or(J.failm() + tid_local(), (unsigned long long)vl.failm[tid_local()], __ATOMIC_RELAXED,
-                              __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid_local() == 0 && mine > 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (ROCm 7.2 may drop the fence's own wait)
-        __hip_atomic_fetch_add(J.done(), (unsigned)mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      continue;
-    }
-    if (kind == 4 || kind == 5) {                      // the representation's conv2 / conv3
-      float* lat = pool + (size_t)(E.S + 1) * G::C * G::CS;
-      const int mine = kind == 4 ? rep_strips<G, 64, 64, 0>(sm, J, s, np.w_conv2, np.b_conv2, lat, pool, nullptr,
-                                                            sm.hfin)
-                                 : rep_strips<G, 64, G::C, 2>(sm, J, s, np.w_conv3, np.b_conv3, pool, lat,
-                                                              np.head_w + G::C, J.hfin(G::A));
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid_local() == 0 && mine > 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (ROCm 7.2 may drop the fence's own wait)
-        __hip_atomic_fetch_add(J.done(), (unsigned)mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      continue;
-    }
-    if (kind != 0) {                                   // a parent's conv
-      const int par = info[1], act = info[5];
-      const int mine = conv_strips<G>(sm, np, J, s, pool + (size_t)(E.S + 1) * G::C * G::CS,
-                                      pool + (size_t)leaf * G::C * G::CS,
-                                      kind == 2 ? pool + (size_t)par * G::C * G::CS : nullptr,
-                                      np.etab + (size_t)act * 9 * G::C);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid_local() == 0 && mine > 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (ROCm 7.2 may drop the fence's own wait)
-        __hip_atomic_fetch_add(J.done(), (unsigned)mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      continue;
-    }
-    for (int a = tid_local(); a < G::A; a += G::THREADS) sm.t.valid[a] = J.valid(G::A)[a];
-    if (tid_local() == 0) sm.t.pass_prior = *J.pass_prior();
-    stage_head_scalars(np.hs, sm.t.hsc);
-    load_y<G>(sm, nullptr, np.head_w);                 // (GLOBAL_Y: the head weights only)
-    __syncthreads();
-    const float* yg = pool + (size_t)leaf * G::C * G::CS;
-    const int mine = job_rounds<G, false, true>(sm, np, sp, TV, yg, J, s, B, nid0, true);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave's row and value stores
-    __syncthreads();
-    if (tid_local() == 0 && mine > 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (ROCm 7.2 may drop the fence's own wait)
-      __hip_atomic_fetch_add(J.done(), (unsigned)mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-// 19x19 epoch tail (sp.tail, whole-game launches): a helper workgroup whose
-// game has ended -- and the game's own workgroup -- move on to the running
-// game with the fewest re-assigned helpers (JobView::nhelp; the nearest after
-// `hint` among ties) and serve its jobs.  Every job kind takes any number of
-// workgroups (claims are dynamic), so this changes who computes, not what.
-// Returns the game or -1 when none is running.  All threads.
-template <class G>
-__device__ __forceinline__ int join_running_game(Smem<G>& sm, const EngineArrays& E, int games, int hint) {
-  if (wave_id() == 0) {
-    const int lane = lane_id_local();
-    unsigned best = 0xFFFFFFFFu;
-    int pick = -1;
-    for (int k0 = 1; k0 <= games; k0 += 64) {
-      const int k = k0 + lane;
-      const int t = (hint + k) % games;
-      unsigned key = 0xFFFFFFFFu;
-      if (k <= games) {
-        const JobView Jt = job_of<G>(E, t);
-        if (__hip_atomic_load(Jt.started(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 &&
-            __hip_atomic_load(Jt.seq(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kJobExit)
-          key = __hip_atomic_load(Jt.nhelp(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      // (helpers, distance) lexicographic: the fewest helpers, then the nearest
-      unsigned long long v = (unsigned long long)key << 32 | (unsigned)k;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o);
-        v = w < v ? w : v;
-      }
-      if ((unsigned)(v >> 32) < best) { best = (unsigned)(v >> 32); pick = (hint + (int)(v & 0xFFFFFFFFu)) % games; }
-    }
-    if (lane == 0) {
-      if (pick >= 0) __hip_atomic_fetch_add(job_of<G>(E, pick).nhelp(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      sm.bc[2] = pick;
-    }
-  }
-  __syncthreads();
-  const int t = sm.bc[2];
-  __syncthreads();
-  return t;
 }
 
 // The simulations of one search with the tree accessor Acc (LDS or HBM stats).
@@ -1897,7 +1109,7 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
           // picks are made while the helpers start on them)
           const int nun0 = sm.t.nunexp, B0 = BATCH ? (nun0 < S - sim ? nun0 : S - sim) : 1;
           prepicked = BATCH && B0 >= 2;
-          conv_shared<G>(sm, np, E, g, leaf, sp.net, scratch, yleaf, &st, leaf != 0 ? T.path(depth - 1) : -1,
+          conv_shared<G>(sm, np, E, g, leaf, sp.net, &st, leaf != 0 ? T.path(depth - 1) : -1,
                          leaf != 0 ? nact[leaf] : 0, [&](unsigned cb) {
                            if (prepicked && wave_id() == 0) {
                              uint64_t um0[G::AP];
@@ -1919,13 +1131,13 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
           if constexpr (TailConvs<G>::value) {
             if (sp.tail) {
               if (tid_local() == 0)
-                sm.bc[3] = __hip_atomic_load(job_of<G>(E, g).nhelp(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0;
+                sm.bc[3] = __hip_atomic_load(&job_of<G>(E, g).h->nhelp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0;
               __syncthreads();
               tail = sm.bc[3] != 0;
             }
           }
           if (tail) {
-            conv_tail<G>(sm, np, E, g, leaf, par, nact[leaf], sp.net, yleaf, y_lds_target<G>(sm),
+            conv_tail<G>(sm, np, E, g, leaf, par, nact[leaf], sp.net, y_lds_target<G>(sm),
                          y_lds_target<G>(sm) != nullptr && yc == par, &st);
           } else {
             latent_conv_rebuilt<G>(sm, np, pool + (size_t)par * node_floats, np.etab + (size_t)nact[leaf] * 9 * G::C,
@@ -1981,7 +1193,7 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
           if ((a >> 6) == j) um[j] &= ~(1ull << (a & 63));
         if (shared_jobs<G>(sp)) {
           batch_expand_shared<G, Acc::LDS>(sm, np, sp, E, g, TV, B, nid, leaf, sp.net, yleaf, um, nun - 1, 1, key,
-                                           sim + 1, &st, prepicked, [&]() {
+                                           sim + 1, &st, prepicked, [&](unsigned) {
                                              if (replay_parallel(true, B, depth))
                                                verify_preload<G, Acc>(sm, sp, TV, T, nact, depth);
                                            });
@@ -2323,8 +1535,7 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
   // (every game workgroup counts itself resident: mzgo_stream_wait_started)
   if (tid_local() == 0) atomicAdd(&E_arg.counters[6], 1ull);
   auto release_helpers = [&]() {
-    if ((sp.helpers > 0 || sp.tail) && tid_local() == 0)
-      __hip_atomic_store(job_of<G>(E_arg, g).seq(), kJobExit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((sp.helpers > 0 || sp.tail) && tid_local() == 0) job_exit(job_of<G>(E_arg, g));
   };
   // an ended game's workgroup serves running games: their parent convs (9x9)
   // or all their jobs as one more helper (19x19)
@@ -2351,8 +1562,7 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
       }
   };
   if (E.status[g] != 0) { release_helpers(); tail_phase(); return; }
-  if ((sp.helpers > 0 || sp.tail) && tid_local() == 0)
-    __hip_atomic_store(job_of<G>(E_arg, g).started(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if ((sp.helpers > 0 || sp.tail) && tid_local() == 0) job_mark_started(job_of<G>(E_arg, g));
   if constexpr (G::WINO) wino_raw_zero<G>(sm.raw);        // zero halo of the conv input planes
   BoardMeta m;
   board_load<G>(sm.stone, sm.invd, E, g, m);
@@ -2569,8 +1779,7 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
     if (tid_local() == 0) E.rec_value[rec] = root_value(TreeViewOf<G>::make(E, slot));
     __syncthreads();                               // this search's LDS reads before the next board
   }
-  if (sp.helpers > 0 && tid_local() == 0)
-    __hip_atomic_store(job_of<G>(E_arg, slot).seq(), kJobExit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (sp.helpers > 0 && tid_local() == 0) job_exit(job_of<G>(E_arg, slot));
 }
 
 }  // namespace mzgo

@@ -52,7 +52,8 @@ struct EngineArrays {
   int* game_len;         // [G]
   double* final_reward;  // [G]
   int* status;           // [G]  0 playing, 1 finished, >=16 error
-  unsigned char* jobs;   // [G][job_bytes(A)] batch-expansion jobs shared with helper workgroups
+  unsigned char* jobs;   // [G][job_bytes(A)] a job slot per game (mzgo_jobs.hpp: JobHeader + regions): the
+                         // work a game's workgroup shares with helper workgroups
   int* mpq;              // [2G + 1] move-parallel epoch (k_search_queue): per game (first move,
                          // moves played) of k_selfplay_boards, then the queue head
   unsigned long long* counters;  // [kCounters] 0: simulations run, 1: moves played, 2: games finished,

@@ -254,12 +254,17 @@ def test_multi_move_launches_equal_single_moves(chunks):
 
 @pytest.mark.parametrize("helpers", ["1", "3"])
 def test_helper_workgroups_do_not_change_records(helpers, monkeypatch):
-    """19x19: the helper workgroups that share each game's batch expansions
-    and parent convs (batch_expand_shared / conv_shared) leave every record
-    byte for byte as the game's workgroup alone produces it."""
+    """19x19, the game-per-workgroup launch (k_selfplay_move, 12 moves in one
+    launch; MZGO_MOVE_PARALLEL=0 -- the move-parallel epoch has no per-game
+    helpers): the helper workgroups that share each game's batch expansions,
+    parent convs and replay checks (the job protocol, mzgo_jobs.hpp), and
+    that join a running game once their own has played its moves
+    (join_running_game), leave every record byte for byte as the game's
+    workgroup alone produces it (0 helpers)."""
     import mzgo
     from mzgo import distributed as mdist
     N, G, S, M = 19, 16, 96, 12
+    monkeypatch.setenv("MZGO_MOVE_PARALLEL", "0")   # (read when the engine is created: it sizes the tree slots)
     net = _net(N)
 
     def packed(h):
