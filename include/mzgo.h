@@ -113,6 +113,40 @@ int mzgo_check_inference_errors(mzgo_engine* eng, void* stream);
  * tree stays on the device for mzgo_tree_export. */
 int mzgo_search(mzgo_engine* eng, const float* root_obs, const double* noise, int G, int move_index,
                 int32_t* root_child_visits, double* root_value, void* stream);
+/* Reanalysis (MuZero Reanalyse; no reference counterpart): search n stored
+ * positions -- any n >= 1, not bounded by num_games -- under the engine's
+ * current weights and search parameters.  All pointers are device pointers.
+ * Position i is given in the self-play record format (mzgo_records_export):
+ * stones i8 [n][N*N] (0 / 1 black / 2 white), invd u8 [n][N*N], flags u8 [n]
+ * (bit0 turn, bit1 passed, bit2 done), and ids i32 [n][2] = (key game id, move
+ * index): the search's RNG streams are keyed by (seed, ids[i][0], ids[i][1]).
+ * The key game id of a self-play record is (game_base + g) ^ (epoch << 24);
+ * with it and the record's move index the search is the record's own.  noise
+ * f64 [n][A]: injected Dirichlet samples, or NULL (sampled from the counter
+ * RNG).  Outputs: visits i32 [n][A], the root's true child visit counts;
+ * value f64 [n], the root value; policy f64 [n][A] (may be NULL), the policy
+ * target the engine's move rule records under compat "fixed" -- search_variant
+ * 0: visits * mask / sum, or mask / sum(mask) when that sum is 0;
+ * search_variant 1: counts / sum over the legal actions, and an ALL-ZERO row
+ * when no legal child was visited (self-play draws a random action there and
+ * records it one-hot; reanalysis draws no action).
+ * The call enqueues a memset of the engine's queue-head word and one launch
+ * (k_reanalyse_queue) on ``stream``: min(n, CU count, tree slots) persistent
+ * workgroups claim items from one queue, each searching in its own tree slot.
+ * So the concurrency is bounded by the engine's tree slots (num_games; the CU
+ * count on 19x19 compat "reference" engines, see the move-parallel note): an
+ * engine made for reanalysis wants num_games >= the CU count.  Afterwards the
+ * slot trees belong to whatever items ran last in each slot (the move-parallel
+ * note's caveat); boards, records and job slots are untouched, the search
+ * counters of mzgo_selfplay_counters ([4], [6]) advance.  Calls on one engine
+ * must be ordered (one stream, or synchronised): they share the slots and the
+ * queue head.
+ * MZGO_EINVAL: null engine or required pointer, n < 1, a board-only engine
+ * (latent_dim 0), a tower engine (tower = 1: not supported).  MZGO_ENOWEIGHTS
+ * as mzgo_search. */
+int mzgo_reanalyse(mzgo_engine* eng, const int8_t* stones, const uint8_t* invd, const uint8_t* flags,
+                   const int32_t* ids, const double* noise, int n, int32_t* visits, double* value,
+                   double* policy, void* stream);
 /* Copy slot g's last search tree to host buffers (synchronises ``stream``):
  * n_nodes; child i32 [n][A]; visits i32 [n]; value_sum f64 [n]; prior f32 [n][A]
  * (row 0 unused); root_prior f64 [A].  Buffers must hold S+1 nodes; NULL skips.

@@ -220,6 +220,7 @@ struct mzgo_engine {
   NetParams np{};
   EngineArrays E{};
   int* d_err = nullptr;
+  unsigned* rq_head = nullptr;  // mzgo_reanalyse's queue head (k_reanalyse_queue)
   float* d_scr = nullptr;      // initial_inference scratch (strip boards), grown on demand
   size_t scr_floats = 0;
   std::vector<void*> allocs;
@@ -528,6 +529,7 @@ int mzgo_engine_create(const mzgo_config* cfg, mzgo_engine** out) {
   chk(e->alloc(&E.status, G));
   chk(e->alloc(&E.counters, kCounters));
   chk(e->alloc(&e->d_err, 1));
+  chk(e->alloc(&e->rq_head, 1));
 #ifdef MZGO_STAMPS
   chk(e->alloc(&E.stamps, TSL * kStampPhases));
   if (E.stamps) (void)hipMemset(E.stamps, 0, TSL * kStampPhases * 8);
@@ -676,6 +678,29 @@ int mzgo_search(mzgo_engine* e, const float* root_obs, const double* noise, int 
   sp.lazy_rows = 0;                                   // every row of an exported tree formed
   HIPCHK(e->ks->search(e->np, sp, e->E, root_obs, noise, G, e->cfg.game_base, move_index, visits, value,
                        (hipStream_t)stream));
+  return MZGO_OK;
+}
+
+int mzgo_reanalyse(mzgo_engine* e, const int8_t* stones, const uint8_t* invd, const uint8_t* flags,
+                   const int32_t* ids, const double* noise, int n, int32_t* visits, double* value, double* policy,
+                   void* stream) {
+  if (!e) return fail(MZGO_EINVAL, "mzgo_reanalyse: null engine");
+  if (n < 1) return fail(MZGO_EINVAL, "mzgo_reanalyse: n must be >= 1, got %d", n);
+  if (!stones || !invd || !flags || !ids || !visits || !value)
+    return fail(MZGO_EINVAL, "mzgo_reanalyse: null %s",
+                !stones ? "stones" : !invd ? "invd" : !flags ? "flags" : !ids ? "ids" : !visits ? "visits" : "value");
+  if (e->C == 0) return fail(MZGO_EINVAL, "mzgo_reanalyse: board-only engine (latent_dim 0) has no network");
+  if (e->tower) return fail(MZGO_EINVAL, "mzgo_reanalyse: tower engines (tower = 1) are not supported");
+  int rc = e->sync_weights();
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const SearchParams sp = e->search_params();          // (self-play's row laziness; no helpers, network 0)
+  const int ncu = device_cus();
+  int wg = ncu > 0 && ncu < e->TS ? ncu : e->TS;       // one tree slot per workgroup
+  if (n < wg) wg = n;
+  const ReanalyseArgs ra{stones, invd, flags, ids, noise, n, e->rq_head, visits, value, policy};
+  HIPCHK(hipMemsetAsync(e->rq_head, 0, sizeof(unsigned), s));
+  HIPCHK(e->ks->reanalyse(e->np, sp, e->E, ra, wg, s));
   return MZGO_OK;
 }
 

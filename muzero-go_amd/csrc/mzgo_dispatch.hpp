@@ -28,6 +28,8 @@ struct KernelSet {
   hipError_t (*selfplay_boards)(const SearchParams&, const PlayParams&, const EngineArrays&, int G, hipStream_t);
   hipError_t (*search_queue)(const NetParams& np, const SearchParams&, const PlayParams&, const EngineArrays&,
                              int G, int workgroups, hipStream_t);
+  hipError_t (*reanalyse)(const NetParams& np, const SearchParams&, const EngineArrays&, const ReanalyseArgs&,
+                          int workgroups, hipStream_t);
 };
 
 const KernelSet* find_kernels(int N, int C);
@@ -81,12 +83,17 @@ struct Launch {
     hipLaunchKernelGGL((k_search_queue<N, C>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, pp, E, G);
     return hipGetLastError();
   }
+  static hipError_t reanalyse(const NetParams& np, const SearchParams& sp, const EngineArrays& E,
+                              const ReanalyseArgs& ra, int workgroups, hipStream_t s) {
+    hipLaunchKernelGGL((k_reanalyse_queue<N, C>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, E, ra);
+    return hipGetLastError();
+  }
   static KernelSet table() {
     typedef Geo<N, C> G;
     return KernelSet{N, C, sizeof(Smem<G>), rep_needs_scratch<G>() ? 64 * N * N : 0,
                      Smem<G>::GLOBAL_Y ? 1 : 0, TailConvs<G>::value ? 1 : 0, &ii, &ri, &search, &breset, &bstep,
                      &bplanes,
-                     &move, &boards, &queue};
+                     &move, &boards, &queue, &reanalyse};
   }
 };
 

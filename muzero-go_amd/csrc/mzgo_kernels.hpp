@@ -1782,4 +1782,82 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
   if (sp.helpers > 0 && tid_local() == 0) job_exit(job_of<G>(E_arg, slot));
 }
 
+// ---------------------------------------------------------------------------
+// Reanalysis (MuZero Reanalyse; no reference counterpart): search n stored
+// positions -- any n, not the engine's games -- from one queue and return what
+// a trainer consumes.  The schedule is k_search_queue's: a persistent grid,
+// workgroup b owns tree slot b and claims the next item until the queue is
+// empty.  The items are caller buffers in the record format
+// (record_observation), the key of item i is (seed, ids[i][0], ids[i][1]) --
+// a self-play record's own search when ids[i] = (move_key's game id, move) --
+// and the outputs are indexed by item: the root's true child visit counts
+// (search_outputs' rule), the root value and, when asked for, the policy
+// target the engine's move rule records under compat "fixed" (visit_policy;
+// main.py's rule draws no action here, so a search whose legal children have
+// no visits gives an all-zero row, not choose_action_main's one-hot).  The
+// engine's boards, records, mpq and job slots are neither read nor written;
+// the counters run_search advances advance.
+// ---------------------------------------------------------------------------
+struct ReanalyseArgs {
+  const int8_t* stones;    // [n][CELLS] 0 / 1 black / 2 white
+  const uint8_t* invd;     // [n][CELLS]
+  const uint8_t* flags;    // [n] flags_pack
+  const int* ids;          // [n][2] key game id, move index
+  const double* noise;     // [n][A] injected Dirichlet samples, or null
+  int n;
+  unsigned* head;          // the queue head (zeroed before the launch)
+  int* visits;             // [n][A]
+  double* value;           // [n]
+  double* policy;          // [n][A], or null
+};
+
+template <int N, int C>
+__global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_waves_per_eu(Geo<N, C>::WPE, Geo<N, C>::WPE))) k_reanalyse_queue(NetParams np_arg, SearchParams sp,
+                                                               EngineArrays E_arg, ReanalyseArgs ra) {
+  typedef Geo<N, C> G;
+  __shared__ Smem<G> sm;
+  static_assert(sizeof(Smem<G>) <= 160 * 1024, "one workgroup per CU: the whole LDS at most");
+  if constexpr (G::WINO) wino_raw_zero<G>(sm.raw);        // zero halo of the conv input planes
+  const int slot = blockIdx.x;
+  for (;;) {
+    if (tid_local() == 0) sm.bc[0] = (int)atomicAdd(ra.head, 1u);
+    __syncthreads();
+    const int i = sm.bc[0];
+    __syncthreads();                               // (sm.bc is the search's scratch too)
+    if (i >= ra.n) break;
+    // (as k_search_queue: this item's view of the arguments, no address
+    // arithmetic kept live across the searches)
+    const EngineArrays E = launder_arrays(E_arg);
+    const NetParams np = launder_params(np_arg);
+    const int8_t* st = launder_global(ra.stones) + (size_t)i * G::CELLS;
+    const uint8_t* iv = launder_global(ra.invd) + (size_t)i * G::CELLS;
+    for (int c = tid_local(); c < G::CELLS; c += G::THREADS) {   // record_observation's inverse
+      sm.stone[c] = st[c];
+      sm.invd[c] = iv[c];
+    }
+    const int* id = launder_global(ra.ids) + 2 * (size_t)i;
+    const BoardMeta m0 = flags_unpack(launder_global(ra.flags)[i], id[1]);
+    __syncthreads();
+    const uint64_t key = stream_key(sp.seed, (uint32_t)id[0], (uint32_t)id[1]);
+    const double* noise = ra.noise ? launder_global(ra.noise) + (size_t)i * G::A : nullptr;
+    SearchParams spm = launder_search(sp);
+    spm.net = 0;
+    spm.helpers = 0;
+    run_search<G>(sm, np, spm, E, slot, [&](int c, int jj) { return board_plane<G>(sm.stone, sm.invd, m0, c, jj); },
+                  noise, key);
+    const TreeView T = TreeViewOf<G>::make(E, slot);
+    int* ov = launder_global(ra.visits) + (size_t)i * G::A;
+    for (int a = tid_local(); a < G::A; a += G::THREADS) {
+      const int c = T.child[a];
+      ov[a] = c >= 0 ? T.visits[c] : 0;
+    }
+    if (tid_local() == 0) launder_global(ra.value)[i] = root_value(T);
+    if (ra.policy && wave_id() == 0) {
+      double vc[G::AP], msum;
+      visit_policy<G>(sm.t, T, sp.variant, 1, launder_global(ra.policy) + (size_t)i * G::A, vc, msum);
+    }
+    __syncthreads();                               // this search's LDS reads before the next board
+  }
+}
+
 }  // namespace mzgo

@@ -217,6 +217,60 @@ __device__ __forceinline__ int argmax_action(const double (&v)[G::AP]) {
   return ba;
 }
 
+// The visit-count policy target of a finished search, by the engine's move
+// rule (variant: SearchParams::variant).  One wave; writes pol[A].
+//   0, self_play.py: visit_counts * valid_mask / sum (np.sum's pairwise order),
+//      or mask / sum(mask) when that sum is 0 -- always under compat
+//      "reference", whose visit counts are zeros;
+//   1, main.py: counts / sum of the child visit counts where valid_mask > 0;
+//      when the sum is 0 the row is all zeros (choose_action_main then draws
+//      an action and makes the row one-hot; reanalysis draws none).
+// vc[j] = the masked count of action lane + 64 j; msum = sum(mask) (variant 0);
+// returns the counts' sum.
+template <class G>
+__device__ __forceinline__ double visit_policy(TreeLds<G>& t, const TreeView& T, int variant, int compat,
+                                               double* pol, double (&vc)[G::AP], double& msum) {
+  const int lane = lane_id_local();
+  if (variant == 1) {
+    double tot = 0.0;
+#pragma unroll
+    for (int j = 0; j < G::AP; ++j) {
+      const int a = lane + 64 * j;
+      vc[j] = 0.0;
+      if (a < G::A && mask_of<G>(t, a) > 0) { const int c = T.child[a]; vc[j] = c >= 0 ? (double)T.visits[c] : 0.0; }
+      tot += vc[j];
+    }
+    tot = wave_sum(tot);                          // integer counts: exact in any order
+#pragma unroll
+    for (int j = 0; j < G::AP; ++j) {
+      const int a = lane + 64 * j;
+      if (a < G::A) pol[a] = tot > 0 ? vc[j] / tot : 0.0;
+    }
+    msum = 0.0;
+    return tot;
+  }
+  // visit_counts * valid_mask (zeros under compat "reference", §0.6)
+  for (int a = lane; a < G::A; a += 64) {
+    double v = 0.0;
+    if (compat == 1) { const int c = T.child[a]; v = c >= 0 ? (double)T.visits[c] : 0.0; }
+    t.dbuf[a] = v * mask_of<G>(t, a);
+  }
+  wave_lds_sync();
+  const double vsum = np_pairwise_sum<double, G::A>(t.dbuf);
+#pragma unroll
+  for (int j = 0; j < G::AP; ++j) { const int a = lane + 64 * j; vc[j] = a < G::A ? t.dbuf[a] : 0.0; }
+  wave_lds_sync();
+  for (int a = lane; a < G::A; a += 64) t.dbuf[a] = mask_of<G>(t, a);
+  wave_lds_sync();
+  msum = np_pairwise_sum<double, G::A>(t.dbuf);
+#pragma unroll
+  for (int j = 0; j < G::AP; ++j) {
+    const int a = lane + 64 * j;
+    if (a < G::A) pol[a] = vsum > 0 ? vc[j] / vsum : mask_of<G>(t, a) / msum;
+  }
+  return vsum;
+}
+
 // main.py's move rule (self-play :660-673 and the arena evaluator :552-565):
 // visit_counts = child visit counts where valid_mask > 0; argmax (first max)
 // with policy = counts / sum, else random.choice(valid actions) with a one-hot
@@ -224,21 +278,14 @@ __device__ __forceinline__ int argmax_action(const double (&v)[G::AP]) {
 template <class G>
 __device__ __forceinline__ int choose_action_main(TreeLds<G>& t, const TreeView& T, uint64_t key, double* pol) {
   const int lane = lane_id_local();
-  double vc[G::AP];
-  double tot = 0.0;
+  double vc[G::AP], msum;
+  const double tot = visit_policy<G>(t, T, 1, 1, pol, vc, msum);
+  if (tot > 0) return argmax_action<G>(vc);
+  const int action = pick_valid<G>(t, draw(key, TAG_ACTION, 0));
 #pragma unroll
   for (int j = 0; j < G::AP; ++j) {
     const int a = lane + 64 * j;
-    vc[j] = 0.0;
-    if (a < G::A && mask_of<G>(t, a) > 0) { const int c = T.child[a]; vc[j] = c >= 0 ? (double)T.visits[c] : 0.0; }
-    tot += vc[j];
-  }
-  tot = wave_sum(tot);                          // integer counts: exact in any order
-  const int action = tot > 0 ? argmax_action<G>(vc) : pick_valid<G>(t, draw(key, TAG_ACTION, 0));
-#pragma unroll
-  for (int j = 0; j < G::AP; ++j) {
-    const int a = lane + 64 * j;
-    if (a < G::A) pol[a] = tot > 0 ? vc[j] / tot : (a == action ? 1.0 : 0.0);
+    if (a < G::A) pol[a] = a == action ? 1.0 : 0.0;
   }
   return action;
 }
@@ -247,26 +294,8 @@ template <class G>
 __device__ __forceinline__ int choose_action(TreeLds<G>& t, const TreeView& T, int compat, double temperature,
                                     uint64_t key, double* pol) {
   const int lane = lane_id_local();
-  // visit_counts * valid_mask (zeros under compat "reference", §0.6)
-  for (int a = lane; a < G::A; a += 64) {
-    double vc = 0.0;
-    if (compat == 1) { const int c = T.child[a]; vc = c >= 0 ? (double)T.visits[c] : 0.0; }
-    t.dbuf[a] = vc * mask_of<G>(t, a);
-  }
-  wave_lds_sync();
-  const double vsum = np_pairwise_sum<double, G::A>(t.dbuf);
-  double vcm[G::AP];
-#pragma unroll
-  for (int j = 0; j < G::AP; ++j) { const int a = lane + 64 * j; vcm[j] = a < G::A ? t.dbuf[a] : 0.0; }
-  wave_lds_sync();
-  for (int a = lane; a < G::A; a += 64) t.dbuf[a] = mask_of<G>(t, a);
-  wave_lds_sync();
-  const double msum = np_pairwise_sum<double, G::A>(t.dbuf);
-#pragma unroll
-  for (int j = 0; j < G::AP; ++j) {
-    const int a = lane + 64 * j;
-    if (a < G::A) pol[a] = vsum > 0 ? vcm[j] / vsum : mask_of<G>(t, a) / msum;
-  }
+  double vcm[G::AP], msum;
+  const double vsum = visit_policy<G>(t, T, 0, compat, pol, vcm, msum);
   const uint64_t h = draw(key, TAG_ACTION, 0);
   if (temperature == 0.0) return vsum > 0 ? argmax_action<G>(vcm) : pick_valid<G>(t, h);
   // probabilities = (vc**(1/T) * mask) / sum, or mask / sum(mask); then

@@ -11,6 +11,8 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
 * ``SelfPlay``    -- G concurrent games per GPU, one fused kernel step per move
 * ``SelfPlayEvaluator`` -- main.py's arena (two networks, all games at once)
 * ``GameHistory``, ``save_batches`` -- the reference's record / pickle format
+* ``Reanalyser``, ``Engine.reanalyse`` -- stored positions searched again under the
+  current weights, from one device work queue (fresh policy targets for a trainer)
 * ``mzgo.play`` -- play.py's interactive human-vs-agent loop (``python -m mzgo.play weights.pth``)
 """
 from ._lib import MzgoError
@@ -18,6 +20,7 @@ from .arena import SelfPlayEvaluator
 from .engine import Engine, EngineConfig
 from .env import GoEnv
 from .net import MuZeroNet
+from .reanalyse import Reanalyser, positions_from_planes, record_ids
 from .resnet import ResMuZeroNet
 from .search import MCTS, MainMCTS, MuZeroAgent
 from .selfplay import GameHistory, SelfPlay, history_from_device, save_batches
@@ -25,4 +28,5 @@ from .weights import deterministic_res_state_dict, deterministic_state_dict
 
 __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "MuZeroAgent", "SelfPlay",
            "GameHistory", "history_from_device", "save_batches", "deterministic_state_dict", "SelfPlayEvaluator",
-           "ResMuZeroNet", "deterministic_res_state_dict", "MzgoError"]
+           "ResMuZeroNet", "deterministic_res_state_dict", "MzgoError", "Reanalyser",
+           "positions_from_planes", "record_ids"]

@@ -60,6 +60,7 @@ SIGNATURES = {
     "mzgo_recurrent_inference": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "mzgo_check_inference_errors": (_I, [_P, _P]),
     "mzgo_search": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
+    "mzgo_reanalyse": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "mzgo_tree_export": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mzgo_board_reset": (_I, [_P, _P]),
     "mzgo_board_step": (_I, [_P, _P, _P, _P, _P]),

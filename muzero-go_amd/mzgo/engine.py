@@ -151,6 +151,34 @@ class Engine:
                               ptr(value), stream_of(self.device)))
         return visits, value
 
+    def reanalyse(self, stones, invd, flags, ids, noise=None, want_policy=True):
+        """Search n stored positions (any n >= 1) from one device work queue
+        under the current weights (mzgo_reanalyse).
+
+        ``stones`` int8 [n, N*N] (0 / 1 black / 2 white), ``invd`` uint8
+        [n, N*N], ``flags`` uint8 [n] (bit0 turn, bit1 passed, bit2 done) -- the
+        record format, see ``mzgo.reanalyse.positions_from_planes`` -- and
+        ``ids`` int32 [n, 2] = (key game id, move index), the searches' RNG
+        keys (``mzgo.reanalyse.record_ids``).  ``noise``: injected Dirichlet
+        samples float64 [n, A], or None (sampled).  Returns (root child visits
+        int32 [n, A], root value float64 [n], policy target float64 [n, A] or
+        None) on the GPU.  At most ``num_games`` searches run at once."""
+        stones = torch.as_tensor(stones).to(self.device, torch.int8)
+        n = stones.shape[0] if stones.dim() > 0 else 0
+        cells = self.N * self.N
+        stones = stones.reshape(n, cells).contiguous()
+        invd = torch.as_tensor(invd).to(self.device, torch.uint8).reshape(n, cells).contiguous()
+        flags = torch.as_tensor(flags).to(self.device, torch.uint8).reshape(n).contiguous()
+        ids = torch.as_tensor(ids).to(self.device, torch.int32).reshape(n, 2).contiguous()
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float64).to(self.device).reshape(n, self.A).contiguous()
+        visits = torch.empty(n, self.A, dtype=torch.int32, device=self.device)
+        value = torch.empty(n, dtype=torch.float64, device=self.device)
+        policy = torch.empty(n, self.A, dtype=torch.float64, device=self.device) if want_policy else None
+        check(lib.mzgo_reanalyse(self._h, ptr(stones), ptr(invd), ptr(flags), ptr(ids), ptr(noise), n,
+                                 ptr(visits), ptr(value), ptr(policy), stream_of(self.device)))
+        return visits, value, policy
+
     def tree(self, g=0):
         """Host copy of slot g's last search tree (dict of numpy arrays)."""
         n1 = self.S + 1

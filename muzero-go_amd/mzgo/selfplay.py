@@ -116,11 +116,14 @@ class SelfPlay:
                                  search_variant=search_variant, dynamics=dynamics)
         self.max_moves = self.engine.M
         self.epoch = 0
+        self.game_base = game_base
+        self._record_epoch = 0      # the generation of the games in the slots (reset())
 
     def reset(self, epoch=None):
         if epoch is not None:
             self.epoch = epoch
         self.engine.selfplay_reset(self.epoch)
+        self._record_epoch = self.epoch
 
     def move(self, moves=1):
         """Enqueue ``moves`` moves for every unfinished game, one launch
@@ -142,6 +145,42 @@ class SelfPlay:
 
     def histories(self):
         return [history_from_device(self.engine.record(g), self.N, self.discount) for g in range(self.G)]
+
+    def reanalyse(self, want_policy=True):
+        """Search every recorded move of the games now in the slots again, with
+        the records' own RNG keys (``mzgo.reanalyse.record_ids``), from the
+        engine's reanalysis queue: under unchanged weights the searches are the
+        records' own.  Returns per game ``(visits int32 [L, A], value float64
+        [L], policy float64 [L, A] or None)`` as numpy arrays cut to the game's
+        length L.  The policy is the visit-count target of compat "fixed"
+        whatever the engine's compat -- what a compat "reference" record, whose
+        policy is mask / sum(mask), lacks.  The records stay as they are."""
+        from .reanalyse import latest_first, record_ids
+        eng = self.engine
+        recs = [eng.record(g) for g in range(self.G)]
+        lens = [int(r["length"]) for r in recs]
+        A = eng.A
+        if sum(lens) == 0:
+            return [(np.zeros((0, A), np.int32), np.zeros(0), np.zeros((0, A)) if want_policy else None)
+                    for _ in recs]
+        ids = np.concatenate([record_ids(self.game_base, g, self._record_epoch, np.arange(L))
+                              for g, L in enumerate(lens)])
+        order = latest_first(ids)                    # longest searches first, as the epoch's own queue
+        back = np.argsort(order)
+        noise = getattr(eng, "_noise", None)         # injected samples (a test hook) were the records' too
+        if noise is not None:
+            noise = torch.cat([noise[g, :L] for g, L in enumerate(lens)])[torch.from_numpy(order).to(noise.device)]
+        visits, value, policy = eng.reanalyse(np.concatenate([r["stones"] for r in recs])[order],
+                                              np.concatenate([r["invd"] for r in recs])[order],
+                                              np.concatenate([r["flags"] for r in recs])[order], ids[order],
+                                              noise=noise, want_policy=want_policy)
+        visits, value = visits.cpu().numpy()[back], value.cpu().numpy()[back]
+        policy = policy.cpu().numpy()[back] if want_policy else None
+        out, at = [], 0
+        for L in lens:
+            out.append((visits[at:at + L], value[at:at + L], policy[at:at + L] if want_policy else None))
+            at += L
+        return out
 
 
 def save_batches(histories, output_dir, save_interval=10):
