@@ -326,6 +326,113 @@ int mzgo_records_export(mzgo_engine* eng, int g, int32_t* length_host, int32_t* 
 int mzgo_records_pack(mzgo_engine* eng, uint8_t* dst, int64_t capacity, int64_t* bytes_needed,
                       void* stream);
 
+/* Device replay store (no reference counterpart in storage; the semantics are
+ * main.py:158-184's PrioritizedReplayBuffer, the targets main.py:381-522's).
+ * A FIFO ring of ``capacity`` game slots in HBM, in the self-play record
+ * format.  With M = max_moves, C = N*N, A = C + 1 a slot holds
+ *   stones i8 [M+1][C], invd u8 [M+1][C], flags u8 [M+1]  the L searched
+ *                              positions, then the board after the last move
+ *   action i32 [M], policy f64 [M][A], root_value f64 [M]
+ *   reward f64 [M+1]           main.py's T+1 rewards, the winner last
+ *   length i32, key_gid i32    L, and the game's RNG key id (mzgo_reanalyse's)
+ * Logical game i (0 = oldest) lives in slot (head + i) % capacity; a game
+ * added to a full store evicts game 0.  The host mirrors only the lengths and
+ * key ids (mzgo_replay_info); priorities and sampling are the caller's
+ * (mzgo.DeviceReplay keeps main.py's np.random sequence).  Calls on one store
+ * must be ordered (one stream, or synchronised): they share index staging.
+ * A store is not thread-safe.  Every failure below is reported through
+ * mzgo_last_error().
+ *
+ * mzgo_replay_create: MZGO_EINVAL for a null ``out``, board_size outside
+ * 2..19, capacity < 1, max_moves < 1. */
+typedef struct mzgo_replay mzgo_replay;
+int mzgo_replay_create(int board_size, int capacity, int max_moves, int device, mzgo_replay** out);
+void mzgo_replay_destroy(mzgo_replay* replay);
+/* Host mirrors: the number of games held, the ring's head slot, and per
+ * logical game its length and key id (buffers of ``capacity`` values; any
+ * pointer may be NULL).  No device work. */
+int mzgo_replay_info(const mzgo_replay* replay, int32_t* size_host, int32_t* head_host, int32_t* lengths_host,
+                     int32_t* key_gid_host);
+/* Ingest every slot's finished game of ``eng``, device to device, in one
+ * launch (k_replay_ingest, a workgroup per game), as G adds in slot order.
+ * Reads the records (stones, invd, flags, action, policy, reward, value) up to
+ * the game's length (the board's move count, = game_len once the game has
+ * ended), the board slot as the final position and final_reward, and applies
+ * main.py:699-713's two rules: -0.5 on the last reward when the game hit the
+ * move cap without ending; winner = final_reward if the game ended, else 0.
+ * key_gid = (game_base + g) ^ (epoch << 24), the record's own search key.
+ * The caller makes sure no game is still playing (mzgo_selfplay_counters [3]).
+ * Synchronises ``stream`` (the G lengths come back to the host mirror).
+ * MZGO_EINVAL: null replay or engine; a board-only engine (latent_dim 0); a
+ * tower engine (tower = 1); the engine's board_size or max_moves differs from
+ * the store's. */
+int mzgo_replay_add_games(mzgo_replay* replay, mzgo_engine* eng, void* stream);
+/* Add one game from host buffers (synchronises ``stream``): stones i8
+ * [L+1][C], invd u8 [L+1][C], flags u8 [L+1], action i32 [L], policy f64
+ * [L][A], reward f64 [L+1], root_value f64 [L] (NULL = zeros).
+ * MZGO_EINVAL: null replay or required buffer; length outside 0..max_moves. */
+int mzgo_replay_add(mzgo_replay* replay, int length, const int8_t* stones_host, const uint8_t* invd_host,
+                    const uint8_t* flags_host, const int32_t* action_host, const double* policy_host,
+                    const double* reward_host, const double* root_value_host, int32_t key_gid, void* stream);
+/* Copy logical game i to host buffers sized for max_moves (the shapes of
+ * mzgo_replay_add with L = max_moves; NULL pointers are skipped; synchronises
+ * ``stream``).  MZGO_EINVAL: null replay; i outside 0..size-1. */
+int mzgo_replay_export(mzgo_replay* replay, int i, int32_t* length_host, int32_t* key_gid_host, int8_t* stones_host,
+                       uint8_t* invd_host, uint8_t* flags_host, int32_t* action_host, double* policy_host,
+                       double* reward_host, double* root_value_host, void* stream);
+/* Batch assembly, one launch (k_replay_batch, a workgroup per sample): the
+ * trainer's targets (mzgo.trainer batch_targets; main.py:395-470, :503-515)
+ * for B samples (logical game, start move, symmetry) given on the HOST, with
+ * K = unroll_steps.  Device outputs:
+ *   obs0 f32 [B][6][N][N]          the observation at ``start``
+ *   boot_obs f32 [B][K+1][6][N][N] the observation at start+k+K where the value
+ *                                  target of unroll step k has a bootstrap
+ *                                  position (start+k+K <= L), zeros elsewhere
+ *   acts i64 [B][K]                the actions from ``start``; pass (A-1) past the end
+ *   t_rew f32 [B][K]               the rewards from ``start``; 0 past the winner
+ *   t_pol f32 [B][K+1][A]          the stored f64 rows rounded to f32;
+ *                                  (float)(1.0 / A) past the end
+ *   val, factor f64 [B][K+1]       compute_target_value's reward part and the
+ *                                  bootstrap's weight: target += factor * r;
+ *                                  factor *= discount, in that order in f64,
+ *                                  stopping at the rewards' end
+ *   has_boot u8 [B][K+1]
+ * Symmetry s (0..7; symmetries_host NULL = identity) gives the sample as if
+ * its whole trajectory had been transformed: every plane and the first N*N
+ * policy entries as [N][N] become np.rot90(x, s & 3), then np.flip(axis=-1)
+ * if s & 4; an action below N*N moves where its one-hot would; the pass entry
+ * and the pass action stay.
+ * The value targets are finished with mzgo_initial_inference over boot_obs's
+ * B*(K+1) rows and mzgo_replay_finish_values.
+ * MZGO_EINVAL: null replay or any required pointer; B < 1; unroll_steps
+ * outside 1..63; an index outside 0..size-1; a start outside 0..L-1 of its
+ * game; a symmetry outside 0..7. */
+int mzgo_replay_batch(mzgo_replay* replay, const int32_t* indices_host, const int32_t* starts_host,
+                      const int32_t* symmetries_host, int B, int unroll_steps, double discount, float* obs0,
+                      float* boot_obs, int64_t* acts, float* t_rew, float* t_pol, double* val, double* factor,
+                      uint8_t* has_boot, void* stream);
+/* t_val[i] = (float)(val[i] + factor[i] * (double)value[i]) where has_boot[i],
+ * (float)val[i] elsewhere, for n entries (device pointers; value f32 [n]: the
+ * network's values of the boot_obs rows).  MZGO_EINVAL: a null pointer; n < 1. */
+int mzgo_replay_finish_values(const double* val, const double* factor, const uint8_t* has_boot, const float* value,
+                              int n, float* t_val, void* stream);
+/* Reanalysis in place: search the L stored positions of the given logical
+ * games (games_host NULL: every game) under ``eng``'s weights and search
+ * parameters, position t of a game keyed (key_gid, t), queued latest move
+ * first; the fresh policy rows and root values replace the stored ones.  The
+ * positions are gathered into staging the store owns, searched by
+ * mzgo_reanalyse (whose conditions and errors apply) and scattered back:
+ * nothing but the item list (slot, move) crosses the bus.
+ * MZGO_EINVAL: null replay or engine; board-size mismatch; a game outside
+ * 0..size-1; n_games < 0. */
+int mzgo_replay_reanalyse(mzgo_replay* replay, mzgo_engine* eng, const int32_t* games_host, int n_games,
+                          void* stream);
+/* The index maps k_replay_batch applies for symmetry s on an N x N board
+ * (host buffers, no device work): src i32 [N*N], output cell c shows input
+ * cell src[c]; dst i32 [N*N+1], action a becomes dst[a] (dst[N*N] = N*N).
+ * MZGO_EINVAL: board_size outside 2..19; symmetry outside 0..7. */
+int mzgo_replay_symmetry_table(int board_size, int symmetry, int32_t* src_host, int32_t* dst_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@
 
 #include "../../include/mzgo.h"
 #include "mzgo_dispatch.hpp"
+#include "mzgo_replay.hpp"
 #include "mzgo_tower_host.hpp"
 
 namespace mzgo {
@@ -41,6 +42,17 @@ using namespace mzgo;
 static thread_local std::string g_err;
 
 static int fail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+
+// (for the units that do not see g_err: mzgo_replay.hip)
+int mzgo::set_error(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -362,6 +374,14 @@ struct mzgo_engine {
     return sp;
   }
 };
+
+// the device replay store's view of an engine's finished games (mzgo_replay.hip)
+void mzgo::replay_engine_view(const mzgo_engine* e, ReplayEngineView* v) {
+  const EngineArrays& E = e->E;
+  *v = ReplayEngineView{e->N, e->G, e->M, e->C, e->tower ? 1 : 0, e->cfg.game_base, e->epoch,
+                        E.stones, E.invd, E.meta, E.rec_stones, E.rec_invd, E.rec_flags, E.rec_action,
+                        E.rec_value, E.rec_policy, E.rec_reward, E.final_reward};
+}
 
 extern "C" {
 

@@ -1,0 +1,544 @@
+// mzgo_replay.hip -- the device replay store (mzgo.h: mzgo_replay_*).
+//
+// Finished games stay in HBM in the self-play record format (stones i8, invd
+// u8, flags u8: 2 N^2 + 1 bytes per position) in a FIFO ring of game slots;
+// the trainer's targets (main.py:381-522, mzgo.trainer's batched step) are
+// assembled from them by one launch per batch, k_replay_batch, which also
+// applies one of the eight board symmetries as an index permutation.  The
+// host keeps only each game's length and key id (and, in Python, its
+// priority): sampling stays main.py's np.random sequence.
+//
+// Kernels here use plain vector loads and stores only; workgroups never
+// communicate.  Compiled with -ffp-contract=off like every unit: the value
+// targets repeat the host's f64 operations one by one (no fused multiply-add).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "../../include/mzgo.h"
+#include "mzgo_replay.hpp"
+
+using namespace mzgo;
+
+#define RHIPCHK(expr)                                                                              \
+  do {                                                                                             \
+    hipError_t e_ = (expr);                                                                        \
+    if (e_ != hipSuccess) return set_error(MZGO_EHIP, "%s: %s", #expr, hipGetErrorString(e_));     \
+  } while (0)
+
+namespace {
+
+constexpr int kThreads = 256;      // k_replay_batch / k_replay_ingest workgroup
+constexpr int kMaxBoard = 19;
+constexpr int kMaxUnroll = 63;     // wave 0 of k_replay_batch holds the K + 1 value targets
+
+// The ring's arrays (device), one allocation per field over all slots.
+// M = max_moves, CELLS = N^2, A = CELLS + 1; a game of length L uses position
+// rows 0..L (the L searched positions, then the final board), L actions,
+// policy rows and root values, and L + 1 rewards (the winner last).
+struct Store {
+  int N, CELLS, A, M, cap;
+  int8_t* stones;      // [cap][M+1][CELLS]
+  uint8_t* invd;       // [cap][M+1][CELLS]
+  uint8_t* flags;      // [cap][M+1]
+  int* action;         // [cap][M]
+  double* policy;      // [cap][M][A]
+  double* reward;      // [cap][M+1]
+  double* root_value;  // [cap][M]
+  int* length;         // [cap]
+  int* key_gid;        // [cap]
+};
+
+// ---------------------------------------------------------------------------
+// Ingest: engine slots g0 .. g0+n-1 -> ring slots (first + i) % cap, one
+// workgroup per game (trajectory_from_record's rules, mzgo/trainer.py).
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) k_replay_ingest(Store R, ReplayEngineView E, int g0, int first) {
+  const int g = g0 + blockIdx.x, slot = (first + blockIdx.x) % R.cap, tid = threadIdx.x;
+  const int* mm = E.meta + (size_t)g * 4;
+  const int done = mm[2] != 0;
+  int L = mm[3];
+  L = L < 0 ? 0 : L > R.M ? R.M : L;
+  const int CELLS = R.CELLS, A = R.A;
+  const size_t src = (size_t)g * E.M, pos = (size_t)slot * (R.M + 1), mv = (size_t)slot * R.M;
+  for (int i = tid; i < L * CELLS; i += kThreads) {
+    R.stones[pos * CELLS + i] = E.rec_stones[src * CELLS + i];
+    R.invd[pos * CELLS + i] = E.rec_invd[src * CELLS + i];
+  }
+  for (int c = tid; c < CELLS; c += kThreads) {           // the board after the last move
+    R.stones[(pos + L) * CELLS + c] = E.stones[(size_t)g * CELLS + c];
+    R.invd[(pos + L) * CELLS + c] = E.invd[(size_t)g * CELLS + c];
+  }
+  for (int i = tid; i < L * A; i += kThreads) R.policy[mv * A + i] = E.rec_policy[src * A + i];
+  // -0.5 on the last move of a game that hit the move cap (main.py:699-702)
+  const bool capped = !done && L >= E.M && L > 0;
+  for (int t = tid; t < L; t += kThreads) {
+    R.flags[pos + t] = E.rec_flags[src + t];
+    R.action[mv + t] = E.rec_action[src + t];
+    R.root_value[mv + t] = E.rec_value[src + t];
+    const double r = E.rec_reward[src + t];
+    R.reward[pos + t] = capped && t == L - 1 ? r + -0.5 : r;
+  }
+  if (tid == 0) {
+    R.flags[pos + L] = (uint8_t)((mm[0] & 1) | ((mm[1] & 1) << 1) | (done << 2));
+    R.reward[pos + L] = done ? E.final_reward[g] : 0.0;       // env.winner(): 0 unless ended
+    R.length[slot] = L;
+    R.key_gid[slot] = (int)((uint32_t)(E.game_base + g) ^ ((uint32_t)E.epoch << 24));
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Batch assembly: one workgroup per sample (slot, start, symmetry).
+//   wave 0     the K + 1 value targets, a thread each (_discounted's loop: at
+//              most K multiply-adds in f64, in its order)
+//   wave 1     the K actions and rewards
+//   all waves  the (K + 2) x 6 planes and the (K + 1) policy rows, element e
+//              of the sample's output on thread e % 256: every store is
+//              contiguous across the workgroup; the symmetry is a gather
+//              through the cell permutation in LDS
+// ---------------------------------------------------------------------------
+struct BatchOut {
+  float* obs0;        // [B][6][CELLS]
+  float* boot_obs;    // [B][K+1][6][CELLS]
+  int64_t* acts;      // [B][K]
+  float* t_rew;       // [B][K]
+  float* t_pol;       // [B][K+1][A]
+  double* val;        // [B][K+1]
+  double* factor;     // [B][K+1]
+  uint8_t* has_boot;  // [B][K+1]
+};
+
+__global__ void __launch_bounds__(kThreads) k_replay_batch(Store R, const int* items, int K, double discount,
+                                                           BatchOut O) {
+  __shared__ int perm[kMaxBoard * kMaxBoard];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int slot = items[3 * b], start = items[3 * b + 1], sym = items[3 * b + 2];
+  const int CELLS = R.CELLS, A = R.A, N = R.N;
+  const int L = R.length[slot];
+  const int T = L + 1;                                     // rewards
+  const size_t pos = (size_t)slot * (R.M + 1), mv = (size_t)slot * R.M;
+  for (int c = tid; c < CELLS; c += kThreads) perm[c] = sym_src(N, sym, c);
+
+  if (tid <= K) {                                          // wave 0 (K <= 63)
+    const int index = start + tid;
+    double target = 0.0, factor = 1.0;
+    for (int k = 0; k < K; ++k) {
+      const int j = index + k;
+      if (j >= T) break;
+      target += factor * R.reward[pos + j];
+      factor *= discount;
+    }
+    const size_t o = (size_t)b * (K + 1) + tid;
+    O.val[o] = target;
+    O.factor[o] = factor;
+    O.has_boot[o] = index + K < T;
+  } else if (tid >= 64 && tid - 64 < K) {                  // wave 1
+    const int k = tid - 64, j = start + k;
+    const size_t o = (size_t)b * K + k;
+    O.acts[o] = j < L ? sym_dst(N, sym, R.action[mv + j]) : A - 1;     // pass past the end
+    O.t_rew[o] = j < T ? (float)R.reward[pos + j] : 0.f;
+  }
+  __syncthreads();
+
+  const int plane = 6 * CELLS;
+  for (int e = tid; e < (K + 2) * plane; e += kThreads) {
+    const int row = e / plane, rem = e - row * plane;
+    const int p = rem / CELLS, c = rem - p * CELLS;
+    // row 0: the start position; row k + 1: the bootstrap position of unroll step k
+    const int at = row == 0 ? start : start + row - 1 + K;
+    float v = 0.f;
+    if (at <= L) {
+      const size_t q = pos + at;
+      const int fl = R.flags[q];
+      switch (p) {
+        case 0: v = R.stones[q * CELLS + perm[c]] == 1; break;
+        case 1: v = R.stones[q * CELLS + perm[c]] == 2; break;
+        case 2: v = fl & 1; break;
+        case 3: v = R.invd[q * CELLS + perm[c]]; break;
+        case 4: v = (fl >> 1) & 1; break;
+        default: v = (fl >> 2) & 1; break;
+      }
+    }
+    if (row == 0) O.obs0[(size_t)b * plane + rem] = v;
+    else O.boot_obs[((size_t)b * (K + 1) + row - 1) * plane + rem] = v;
+  }
+
+  const float uniform = (float)(1.0 / A);
+  for (int e = tid; e < (K + 1) * A; e += kThreads) {
+    const int k = e / A, a = e - k * A, i = start + k;
+    float v = uniform;
+    if (i < L) v = (float)R.policy[(mv + i) * A + (a < CELLS ? perm[a] : a)];
+    O.t_pol[(size_t)b * (K + 1) * A + e] = v;
+  }
+}
+
+// t_val = (float)(val + factor * (double)v) where a bootstrap position exists
+__global__ void __launch_bounds__(kThreads) k_replay_finish(const double* val, const double* factor,
+                                                            const uint8_t* has_boot, const float* v, int n,
+                                                            float* t_val) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  t_val[i] = has_boot[i] ? (float)(val[i] + factor[i] * (double)v[i]) : (float)val[i];
+}
+
+// ---------------------------------------------------------------------------
+// Reanalysis in place: stored positions -> contiguous staging (mzgo_reanalyse's
+// inputs), and its policy rows and root values back.  items [n][2] = (slot,
+// move); one wave per item.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_replay_gather(Store R, const int* items, int8_t* stones, uint8_t* invd,
+                                                      uint8_t* flags, int* ids) {
+  const int i = blockIdx.x, slot = items[2 * i], t = items[2 * i + 1];
+  const size_t q = (size_t)slot * (R.M + 1) + t;
+  for (int c = threadIdx.x; c < R.CELLS; c += 64) {
+    stones[(size_t)i * R.CELLS + c] = R.stones[q * R.CELLS + c];
+    invd[(size_t)i * R.CELLS + c] = R.invd[q * R.CELLS + c];
+  }
+  if (threadIdx.x == 0) {
+    flags[i] = R.flags[q];
+    ids[2 * i] = R.key_gid[slot];
+    ids[2 * i + 1] = t;
+  }
+}
+
+__global__ void __launch_bounds__(64) k_replay_scatter(Store R, const int* items, const double* policy,
+                                                       const double* value) {
+  const int i = blockIdx.x, slot = items[2 * i], t = items[2 * i + 1];
+  const size_t q = (size_t)slot * R.M + t;
+  for (int a = threadIdx.x; a < R.A; a += 64) R.policy[q * R.A + a] = policy[(size_t)i * R.A + a];
+  if (threadIdx.x == 0) R.root_value[q] = value[i];
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// Host side
+// ---------------------------------------------------------------------------
+struct mzgo_replay {
+  Store R{};
+  int device = 0;
+  int head = 0, size = 0;                 // logical game i lives in slot (head + i) % cap
+  std::vector<int> len, gid;              // per SLOT: host mirrors of R.length / R.key_gid
+  std::vector<void*> allocs;
+  // batch / reanalysis index staging: pinned host words -> device words
+  int* h_items = nullptr;
+  int* d_items = nullptr;
+  size_t items_cap = 0;
+  hipEvent_t items_read = nullptr;        // the last upload from h_items has been read
+  // reanalysis staging (grown on demand)
+  void* stage = nullptr;
+  size_t stage_bytes = 0;
+
+  int slot_of(int i) const { return (head + i) % R.cap; }
+
+  template <class T>
+  int alloc(T** p, size_t n) {
+    void* v = nullptr;
+    hipError_t e = hipMalloc(&v, n * sizeof(T) + 256);
+    if (e != hipSuccess) return set_error(MZGO_EHIP, "hipMalloc(%zu): %s", n * sizeof(T), hipGetErrorString(e));
+    allocs.push_back(v);
+    *p = reinterpret_cast<T*>(v);
+    return MZGO_OK;
+  }
+  ~mzgo_replay() {
+    for (void* p : allocs) (void)hipFree(p);
+    if (d_items) (void)hipFree(d_items);
+    if (h_items) (void)hipHostFree(h_items);
+    if (stage) (void)hipFree(stage);
+    if (items_read) (void)hipEventDestroy(items_read);
+  }
+
+  // room for n index words on both sides; waits until the previous upload left h_items
+  int items_room(size_t n, hipStream_t s) {
+    RHIPCHK(hipEventSynchronize(items_read));
+    if (n <= items_cap) return MZGO_OK;
+    RHIPCHK(hipStreamSynchronize(s));                      // (a launch may still read d_items)
+    if (d_items) RHIPCHK(hipFree(d_items));
+    if (h_items) RHIPCHK(hipHostFree(h_items));
+    d_items = h_items = nullptr;
+    items_cap = 0;
+    const size_t cap = std::max<size_t>(n, 1024);
+    RHIPCHK(hipMalloc((void**)&d_items, cap * sizeof(int)));
+    RHIPCHK(hipHostMalloc((void**)&h_items, cap * sizeof(int), hipHostMallocDefault));
+    items_cap = cap;
+    return MZGO_OK;
+  }
+  int items_upload(size_t n, hipStream_t s) {
+    RHIPCHK(hipMemcpyAsync(d_items, h_items, n * sizeof(int), hipMemcpyHostToDevice, s));
+    RHIPCHK(hipEventRecord(items_read, s));
+    return MZGO_OK;
+  }
+  // make room for n more games at the ring's end (FIFO eviction); returns the first new slot
+  int push(int n) {
+    const int first = (head + size) % R.cap;
+    const int evict = std::max(0, size + n - R.cap);
+    head = (head + evict) % R.cap;
+    size = size + n - evict;
+    return first;
+  }
+};
+
+extern "C" {
+
+int mzgo_replay_create(int board_size, int capacity, int max_moves, int device, mzgo_replay** out) {
+  if (!out) return set_error(MZGO_EINVAL, "mzgo_replay_create: null out");
+  *out = nullptr;
+  if (board_size < 2 || board_size > kMaxBoard)
+    return set_error(MZGO_EINVAL, "mzgo_replay_create: board_size %d (2..%d)", board_size, kMaxBoard);
+  if (capacity < 1) return set_error(MZGO_EINVAL, "mzgo_replay_create: capacity must be >= 1, got %d", capacity);
+  if (max_moves < 1) return set_error(MZGO_EINVAL, "mzgo_replay_create: max_moves must be >= 1, got %d", max_moves);
+  RHIPCHK(hipSetDevice(device));
+  mzgo_replay* r = new mzgo_replay;
+  r->device = device;
+  Store& R = r->R;
+  R.N = board_size; R.CELLS = board_size * board_size; R.A = R.CELLS + 1; R.M = max_moves; R.cap = capacity;
+  const size_t cap = capacity, M = max_moves, C = R.CELLS, A = R.A;
+  int rc = MZGO_OK;
+  auto chk = [&](int x) { if (rc == MZGO_OK) rc = x; };
+  chk(r->alloc(&R.stones, cap * (M + 1) * C));
+  chk(r->alloc(&R.invd, cap * (M + 1) * C));
+  chk(r->alloc(&R.flags, cap * (M + 1)));
+  chk(r->alloc(&R.action, cap * M));
+  chk(r->alloc(&R.policy, cap * M * A));
+  chk(r->alloc(&R.reward, cap * (M + 1)));
+  chk(r->alloc(&R.root_value, cap * M));
+  chk(r->alloc(&R.length, cap));
+  chk(r->alloc(&R.key_gid, cap));
+  if (rc == MZGO_OK && hipMemset(R.length, 0, cap * sizeof(int)) != hipSuccess)
+    rc = set_error(MZGO_EHIP, "mzgo_replay_create: hipMemset failed");
+  if (rc == MZGO_OK && hipEventCreateWithFlags(&r->items_read, hipEventDisableTiming) != hipSuccess)
+    rc = set_error(MZGO_EHIP, "mzgo_replay_create: hipEventCreate failed");
+  if (rc != MZGO_OK) { delete r; return rc; }
+  r->len.assign(cap, 0);
+  r->gid.assign(cap, 0);
+  *out = r;
+  return MZGO_OK;
+}
+
+void mzgo_replay_destroy(mzgo_replay* r) { delete r; }
+
+int mzgo_replay_info(const mzgo_replay* r, int32_t* size_host, int32_t* head_host, int32_t* lengths_host,
+                     int32_t* key_gid_host) {
+  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_info: null replay");
+  if (size_host) *size_host = r->size;
+  if (head_host) *head_host = r->head;
+  for (int i = 0; i < r->size; ++i) {
+    if (lengths_host) lengths_host[i] = r->len[r->slot_of(i)];
+    if (key_gid_host) key_gid_host[i] = r->gid[r->slot_of(i)];
+  }
+  return MZGO_OK;
+}
+
+int mzgo_replay_add_games(mzgo_replay* r, mzgo_engine* eng, void* stream) {
+  if (!r || !eng) return set_error(MZGO_EINVAL, "mzgo_replay_add_games: null %s", !r ? "replay" : "engine");
+  ReplayEngineView E;
+  replay_engine_view(eng, &E);
+  if (E.latent_dim == 0)
+    return set_error(MZGO_EINVAL, "mzgo_replay_add_games: board-only engine (latent_dim 0) has no game records");
+  if (E.tower) return set_error(MZGO_EINVAL, "mzgo_replay_add_games: tower engines (tower = 1) are not supported");
+  if (E.N != r->R.N)
+    return set_error(MZGO_EINVAL, "mzgo_replay_add_games: board size mismatch (store %d, engine %d)", r->R.N, E.N);
+  if (E.M != r->R.M)
+    return set_error(MZGO_EINVAL, "mzgo_replay_add_games: max_moves mismatch (store %d, engine %d)", r->R.M, E.M);
+  hipStream_t s = (hipStream_t)stream;
+  // G games pushed one after another: when G exceeds the capacity only the
+  // last ``capacity`` survive, so only those are copied (no slot written twice)
+  const int n = std::min(E.G, r->R.cap), g0 = E.G - n;
+  r->push(g0);
+  const int first = r->push(n);
+  hipLaunchKernelGGL(k_replay_ingest, dim3(n), dim3(kThreads), 0, s, r->R, E, g0, first);
+  RHIPCHK(hipGetLastError());
+  std::vector<int> meta((size_t)E.G * 4);
+  RHIPCHK(hipMemcpyAsync(meta.data(), E.meta, meta.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  RHIPCHK(hipStreamSynchronize(s));
+  for (int i = 0; i < n; ++i) {
+    const int g = g0 + i, slot = (first + i) % r->R.cap;
+    r->len[slot] = std::min(std::max(meta[(size_t)g * 4 + 3], 0), r->R.M);
+    r->gid[slot] = (int)((uint32_t)(E.game_base + g) ^ ((uint32_t)E.epoch << 24));
+  }
+  return MZGO_OK;
+}
+
+int mzgo_replay_add(mzgo_replay* r, int length, const int8_t* stones_host, const uint8_t* invd_host,
+                    const uint8_t* flags_host, const int32_t* action_host, const double* policy_host,
+                    const double* reward_host, const double* root_value_host, int32_t key_gid, void* stream) {
+  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_add: null replay");
+  if (length < 0 || length > r->R.M)
+    return set_error(MZGO_EINVAL, "mzgo_replay_add: length %d out of range (0..max_moves = %d)", length, r->R.M);
+  if (!stones_host || !invd_host || !flags_host || !reward_host || (length > 0 && (!action_host || !policy_host)))
+    return set_error(MZGO_EINVAL, "mzgo_replay_add: null %s",
+                     !stones_host ? "stones" : !invd_host ? "invd" : !flags_host ? "flags" : !reward_host ? "reward"
+                     : !action_host ? "action" : "policy");
+  hipStream_t s = (hipStream_t)stream;
+  const Store& R = r->R;
+  const size_t L = length, C = R.CELLS, A = R.A;
+  const int slot = r->push(1);
+  const size_t pos = (size_t)slot * (R.M + 1), mv = (size_t)slot * R.M;
+  RHIPCHK(hipMemcpyAsync(R.stones + pos * C, stones_host, (L + 1) * C, hipMemcpyHostToDevice, s));
+  RHIPCHK(hipMemcpyAsync(R.invd + pos * C, invd_host, (L + 1) * C, hipMemcpyHostToDevice, s));
+  RHIPCHK(hipMemcpyAsync(R.flags + pos, flags_host, L + 1, hipMemcpyHostToDevice, s));
+  RHIPCHK(hipMemcpyAsync(R.reward + pos, reward_host, (L + 1) * 8, hipMemcpyHostToDevice, s));
+  if (L > 0) {
+    RHIPCHK(hipMemcpyAsync(R.action + mv, action_host, L * 4, hipMemcpyHostToDevice, s));
+    RHIPCHK(hipMemcpyAsync(R.policy + mv * A, policy_host, L * A * 8, hipMemcpyHostToDevice, s));
+    if (root_value_host) RHIPCHK(hipMemcpyAsync(R.root_value + mv, root_value_host, L * 8, hipMemcpyHostToDevice, s));
+    else RHIPCHK(hipMemsetAsync(R.root_value + mv, 0, L * 8, s));
+  }
+  RHIPCHK(hipMemcpyAsync(R.length + slot, &length, 4, hipMemcpyHostToDevice, s));
+  RHIPCHK(hipMemcpyAsync(R.key_gid + slot, &key_gid, 4, hipMemcpyHostToDevice, s));
+  RHIPCHK(hipStreamSynchronize(s));                         // (the host buffers are the caller's)
+  r->len[slot] = length;
+  r->gid[slot] = key_gid;
+  return MZGO_OK;
+}
+
+int mzgo_replay_export(mzgo_replay* r, int i, int32_t* length_host, int32_t* key_gid_host, int8_t* stones_host,
+                       uint8_t* invd_host, uint8_t* flags_host, int32_t* action_host, double* policy_host,
+                       double* reward_host, double* root_value_host, void* stream) {
+  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_export: null replay");
+  if (i < 0 || i >= r->size)
+    return set_error(MZGO_EINVAL, "mzgo_replay_export: game %d out of range (the store holds %d)", i, r->size);
+  hipStream_t s = (hipStream_t)stream;
+  const Store& R = r->R;
+  const int slot = r->slot_of(i);
+  const size_t L = r->len[slot], C = R.CELLS, A = R.A;
+  const size_t pos = (size_t)slot * (R.M + 1), mv = (size_t)slot * R.M;
+  if (length_host) *length_host = (int32_t)L;
+  if (key_gid_host) *key_gid_host = r->gid[slot];
+  if (stones_host) RHIPCHK(hipMemcpyAsync(stones_host, R.stones + pos * C, (L + 1) * C, hipMemcpyDeviceToHost, s));
+  if (invd_host) RHIPCHK(hipMemcpyAsync(invd_host, R.invd + pos * C, (L + 1) * C, hipMemcpyDeviceToHost, s));
+  if (flags_host) RHIPCHK(hipMemcpyAsync(flags_host, R.flags + pos, L + 1, hipMemcpyDeviceToHost, s));
+  if (reward_host) RHIPCHK(hipMemcpyAsync(reward_host, R.reward + pos, (L + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (L > 0) {
+    if (action_host) RHIPCHK(hipMemcpyAsync(action_host, R.action + mv, L * 4, hipMemcpyDeviceToHost, s));
+    if (policy_host) RHIPCHK(hipMemcpyAsync(policy_host, R.policy + mv * A, L * A * 8, hipMemcpyDeviceToHost, s));
+    if (root_value_host) RHIPCHK(hipMemcpyAsync(root_value_host, R.root_value + mv, L * 8, hipMemcpyDeviceToHost, s));
+  }
+  RHIPCHK(hipStreamSynchronize(s));
+  return MZGO_OK;
+}
+
+int mzgo_replay_batch(mzgo_replay* r, const int32_t* indices_host, const int32_t* starts_host,
+                      const int32_t* symmetries_host, int B, int unroll_steps, double discount, float* obs0,
+                      float* boot_obs, int64_t* acts, float* t_rew, float* t_pol, double* val, double* factor,
+                      uint8_t* has_boot, void* stream) {
+  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_batch: null replay");
+  if (B < 1) return set_error(MZGO_EINVAL, "mzgo_replay_batch: B must be >= 1, got %d", B);
+  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "mzgo_replay_batch: unroll_steps %d out of range (1..%d)", unroll_steps, kMaxUnroll);
+  if (!indices_host || !starts_host || !obs0 || !boot_obs || !acts || !t_rew || !t_pol || !val || !factor || !has_boot)
+    return set_error(MZGO_EINVAL, "mzgo_replay_batch: null %s",
+                     !indices_host ? "indices" : !starts_host ? "starts" : !obs0 ? "obs0" : !boot_obs ? "boot_obs"
+                     : !acts ? "acts" : !t_rew ? "t_rew" : !t_pol ? "t_pol" : !val ? "val" : !factor ? "factor"
+                     : "has_boot");
+  for (int b = 0; b < B; ++b) {
+    const int i = indices_host[b];
+    if (i < 0 || i >= r->size)
+      return set_error(MZGO_EINVAL, "mzgo_replay_batch: sample %d: game %d is not in the store (it holds %d)", b, i,
+                       r->size);
+    const int L = r->len[r->slot_of(i)];
+    if (starts_host[b] < 0 || starts_host[b] >= L)
+      return set_error(MZGO_EINVAL, "mzgo_replay_batch: sample %d: start %d outside game %d's %d moves", b,
+                       starts_host[b], i, L);
+    if (symmetries_host && (symmetries_host[b] < 0 || symmetries_host[b] > 7))
+      return set_error(MZGO_EINVAL, "mzgo_replay_batch: sample %d: symmetry %d (0..7)", b, symmetries_host[b]);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = r->items_room((size_t)B * 3, s)) return rc;
+  for (int b = 0; b < B; ++b) {
+    r->h_items[3 * b] = r->slot_of(indices_host[b]);
+    r->h_items[3 * b + 1] = starts_host[b];
+    r->h_items[3 * b + 2] = symmetries_host ? symmetries_host[b] : 0;
+  }
+  if (int rc = r->items_upload((size_t)B * 3, s)) return rc;
+  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot};
+  hipLaunchKernelGGL(k_replay_batch, dim3(B), dim3(kThreads), 0, s, r->R, r->d_items, unroll_steps, discount, O);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+int mzgo_replay_finish_values(const double* val, const double* factor, const uint8_t* has_boot, const float* value,
+                              int n, float* t_val, void* stream) {
+  if (n < 1) return set_error(MZGO_EINVAL, "mzgo_replay_finish_values: n must be >= 1, got %d", n);
+  if (!val || !factor || !has_boot || !value || !t_val)
+    return set_error(MZGO_EINVAL, "mzgo_replay_finish_values: null %s",
+                     !val ? "val" : !factor ? "factor" : !has_boot ? "has_boot" : !value ? "value" : "t_val");
+  hipLaunchKernelGGL(k_replay_finish, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, val,
+                     factor, has_boot, value, n, t_val);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+int mzgo_replay_reanalyse(mzgo_replay* r, mzgo_engine* eng, const int32_t* games_host, int n_games, void* stream) {
+  if (!r || !eng) return set_error(MZGO_EINVAL, "mzgo_replay_reanalyse: null %s", !r ? "replay" : "engine");
+  ReplayEngineView E;
+  replay_engine_view(eng, &E);
+  if (E.N != r->R.N)
+    return set_error(MZGO_EINVAL, "mzgo_replay_reanalyse: board size mismatch (store %d, engine %d)", r->R.N, E.N);
+  if (games_host && n_games < 0) return set_error(MZGO_EINVAL, "mzgo_replay_reanalyse: n_games %d", n_games);
+  const int ng = games_host ? n_games : r->size;
+  std::vector<int> items;                                   // (slot, move), the games' own order
+  for (int k = 0; k < ng; ++k) {
+    const int i = games_host ? games_host[k] : k;
+    if (i < 0 || i >= r->size)
+      return set_error(MZGO_EINVAL, "mzgo_replay_reanalyse: game %d is not in the store (it holds %d)", i, r->size);
+    const int slot = r->slot_of(i);
+    for (int t = 0; t < r->len[slot]; ++t) { items.push_back(slot); items.push_back(t); }
+  }
+  const size_t n = items.size() / 2;
+  if (n == 0) return MZGO_OK;
+  // latest move first (mzgo.reanalyse.latest_first): the queue's longest searches start first
+  std::vector<int> order(n);
+  for (size_t i = 0; i < n; ++i) order[i] = (int)i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return items[2 * a + 1] > items[2 * b + 1]; });
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = r->items_room(2 * n, s)) return rc;
+  for (size_t i = 0; i < n; ++i) {
+    r->h_items[2 * i] = items[2 * order[i]];
+    r->h_items[2 * i + 1] = items[2 * order[i] + 1];
+  }
+  if (int rc = r->items_upload(2 * n, s)) return rc;
+  // staging, each field on a 256-byte boundary
+  const size_t C = r->R.CELLS, A = r->R.A;
+  const size_t sizes[] = {n * C, n * C, n, n * 2 * 4, n * A * 4, n * 8, n * A * 8};
+  size_t off[8] = {0};
+  for (int i = 0; i < 7; ++i) off[i + 1] = off[i] + (sizes[i] + 255) / 256 * 256;
+  if (off[7] > r->stage_bytes) {
+    RHIPCHK(hipStreamSynchronize(s));
+    if (r->stage) RHIPCHK(hipFree(r->stage));
+    r->stage = nullptr;
+    r->stage_bytes = 0;
+    RHIPCHK(hipMalloc(&r->stage, off[7]));
+    r->stage_bytes = off[7];
+  }
+  uint8_t* base = (uint8_t*)r->stage;
+  int8_t* st = (int8_t*)(base + off[0]);
+  uint8_t* iv = base + off[1];
+  uint8_t* fl = base + off[2];
+  int* ids = (int*)(base + off[3]);
+  int32_t* visits = (int32_t*)(base + off[4]);
+  double* value = (double*)(base + off[5]);
+  double* policy = (double*)(base + off[6]);
+  hipLaunchKernelGGL(k_replay_gather, dim3((unsigned)n), dim3(64), 0, s, r->R, r->d_items, st, iv, fl, ids);
+  RHIPCHK(hipGetLastError());
+  if (int rc = mzgo_reanalyse(eng, st, iv, fl, ids, nullptr, (int)n, visits, value, policy, stream)) return rc;
+  hipLaunchKernelGGL(k_replay_scatter, dim3((unsigned)n), dim3(64), 0, s, r->R, r->d_items, policy, value);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+int mzgo_replay_symmetry_table(int board_size, int symmetry, int32_t* src_host, int32_t* dst_host) {
+  if (board_size < 2 || board_size > kMaxBoard || symmetry < 0 || symmetry > 7)
+    return set_error(MZGO_EINVAL, "mzgo_replay_symmetry_table: board_size %d (2..%d), symmetry %d (0..7)", board_size,
+                     kMaxBoard, symmetry);
+  const int cells = board_size * board_size;
+  for (int c = 0; c < cells; ++c)
+    if (src_host) src_host[c] = sym_src(board_size, symmetry, c);
+  for (int a = 0; a <= cells; ++a)
+    if (dst_host) dst_host[a] = sym_dst(board_size, symmetry, a);
+  return MZGO_OK;
+}
+
+}  // extern "C"

@@ -13,6 +13,8 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
 * ``GameHistory``, ``save_batches`` -- the reference's record / pickle format
 * ``Reanalyser``, ``Engine.reanalyse`` -- stored positions searched again under the
   current weights, from one device work queue (fresh policy targets for a trainer)
+* ``DeviceReplay`` -- finished games kept in HBM: the trainer's batches (with board
+  symmetries) and reanalysis in place, without the games visiting the host
 * ``mzgo.play`` -- play.py's interactive human-vs-agent loop (``python -m mzgo.play weights.pth``)
 """
 from ._lib import MzgoError
@@ -21,6 +23,7 @@ from .engine import Engine, EngineConfig
 from .env import GoEnv
 from .net import MuZeroNet
 from .reanalyse import Reanalyser, positions_from_planes, record_ids
+from .replay import DeviceReplay
 from .resnet import ResMuZeroNet
 from .search import MCTS, MainMCTS, MuZeroAgent
 from .selfplay import GameHistory, SelfPlay, history_from_device, save_batches
@@ -29,4 +32,4 @@ from .weights import deterministic_res_state_dict, deterministic_state_dict
 __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "MuZeroAgent", "SelfPlay",
            "GameHistory", "history_from_device", "save_batches", "deterministic_state_dict", "SelfPlayEvaluator",
            "ResMuZeroNet", "deterministic_res_state_dict", "MzgoError", "Reanalyser",
-           "positions_from_planes", "record_ids"]
+           "positions_from_planes", "record_ids", "DeviceReplay"]

@@ -86,6 +86,16 @@ SIGNATURES = {
     "mzgo_conv3x3_relu_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "mzgo_conv3x3_backward_workspace": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
     "mzgo_conv3x3_backward": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    "mzgo_replay_create": (_I, [_I, _I, _I, _I, ctypes.POINTER(_P)]),
+    "mzgo_replay_destroy": (None, [_P]),
+    "mzgo_replay_info": (_I, [_P, _P, _P, _P, _P]),
+    "mzgo_replay_add_games": (_I, [_P, _P, _P]),
+    "mzgo_replay_add": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int32, _P]),
+    "mzgo_replay_export": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mzgo_replay_batch": (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mzgo_replay_finish_values": (_I, [_P, _P, _P, _P, _I, _P, _P]),
+    "mzgo_replay_reanalyse": (_I, [_P, _P, _P, _I, _P]),
+    "mzgo_replay_symmetry_table": (_I, [_I, _I, _P, _P]),
 }
 
 

@@ -1,0 +1,278 @@
+"""Device replay store: finished games stay in HBM, from the self-play
+records to the trainer's batch.
+
+The reference keeps trajectories in Python lists (main.py:158-184,
+``PrioritizedReplayBuffer``) and builds every training target in a Python
+loop (main.py:381-522).  ``DeviceReplay`` keeps the same games in a FIFO ring
+of slots on the GPU, in the self-play record format (stones i8, invd u8,
+flags u8: 2 N^2 + 1 bytes per position against 48 N^2 for the f64 planes),
+and serves both consumers of stored games from there:
+
+* ``batch``     -- one launch (k_replay_batch) writes the trainer's targets for
+  B (game, start, symmetry) samples; ``finish_values`` adds the bootstrap;
+* ``reanalyse`` -- the stored positions searched again under a ``Reanalyser``'s
+  engine, the fresh policies and root values written into the store.
+
+Ingest is ``add_games(engine)`` (device to device, one launch; what
+``MainSelfPlay.play_into`` calls), or ``add(trajectory)`` for main.py-format
+dicts from files and tests; ``export(i)`` gives a game back as such a dict.
+
+Only the ledger crosses the bus: each game's length, key id and priority live
+on the host (``ReplayLedger``), and sampling is main.py's --
+``sample_indices`` draws exactly what ``PrioritizedReplayBuffer.sample`` draws
+from the same ``np.random`` state.  One store equals
+``MultiVersionReplayBuffer(num_versions=1)``.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from ._lib import check, lib, ptr, stream_of
+from .reanalyse import positions_from_planes
+
+
+def symmetry_tables(board_size, symmetry):
+    """The index maps the batch kernel applies for symmetry s = 0..7 on an
+    N x N board (mzgo_replay_symmetry_table: the kernel's own functions run on
+    the host): ``src`` int32 [N*N] -- output cell c shows input cell src[c],
+    i.e. ``y.flat = x.flat[src]`` for ``y = np.rot90(x, s & 3)``, then
+    ``np.flip(y, -1)`` if ``s & 4`` -- and ``dst`` int32 [N*N + 1] -- action a
+    becomes dst[a]; the pass action stays."""
+    cells = board_size * board_size
+    src = np.empty(cells, np.int32)
+    dst = np.empty(cells + 1, np.int32)
+    check(lib.mzgo_replay_symmetry_table(int(board_size), int(symmetry), ptr(src), ptr(dst)))
+    return src, dst
+
+
+class ReplayLedger:
+    """The host's side of the store: per game its priority, length and key
+    id, in logical (oldest first) order, with ``PrioritizedReplayBuffer``'s
+    semantics (main.py:158-184): FIFO eviction at ``capacity``, priority 1.0
+    for a new game, the same ``np.random.choice`` call."""
+
+    def __init__(self, capacity):
+        self.capacity = capacity
+        self.priorities = []
+        self.lengths = []
+        self.key_gids = []
+
+    def __len__(self):
+        return len(self.priorities)
+
+    def push(self, length, key_gid):
+        if len(self.priorities) >= self.capacity:
+            self.priorities.pop(0)
+            self.lengths.pop(0)
+            self.key_gids.pop(0)
+        self.priorities.append(1.0)
+        self.lengths.append(int(length))
+        self.key_gids.append(int(key_gid))
+
+    def sample_indices(self, batch_size):
+        priorities = np.array(self.priorities)
+        probs = priorities / priorities.sum()
+        return np.random.choice(len(self.priorities), batch_size, replace=False, p=probs)
+
+    def update_priorities(self, indices, new_priorities):
+        for i, p in zip(indices, new_priorities):
+            self.priorities[i] = p
+
+
+def finish_values(val, factor, has_boot, value):
+    """The value targets from ``batch``'s parts and the network's values of
+    its ``boot_obs`` rows (float32, B*(K+1) of them): float32 [B, K+1],
+    ``(float)(val + factor * (double)v)`` where a bootstrap position exists,
+    ``(float)val`` elsewhere -- the bits of the host path's float64 sum
+    (k_replay_finish)."""
+    n = val.numel()
+    value = value.to(val.device, torch.float32).reshape(n).contiguous()
+    t_val = torch.empty(val.shape, dtype=torch.float32, device=val.device)
+    check(lib.mzgo_replay_finish_values(ptr(val), ptr(factor), ptr(has_boot), ptr(value), n, ptr(t_val),
+                                        stream_of(val.device)))
+    return t_val
+
+
+class DeviceReplay:
+    """``DeviceReplay(board_size, capacity, max_moves, device)``: a ring of
+    ``capacity`` games of at most ``max_moves`` moves on ``device``.
+    ``max_moves`` must be the move cap of the engines that feed it
+    (``MainSelfPlay.max_moves``)."""
+
+    def __init__(self, board_size, capacity, max_moves, device="cuda"):
+        self.N = int(board_size)
+        self.A = self.N * self.N + 1
+        self.capacity = int(capacity)
+        self.max_moves = int(max_moves)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DeviceReplay lives on the GPU; use PrioritizedReplayBuffer for host trajectories")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        torch.cuda.init()
+        h = ctypes.c_void_p()
+        check(lib.mzgo_replay_create(self.N, self.capacity, self.max_moves, self.device.index, ctypes.byref(h)))
+        self._h = h
+        self.ledger = ReplayLedger(self.capacity)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.mzgo_replay_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __len__(self):
+        return len(self.ledger)
+
+    # ---- the ledger (PrioritizedReplayBuffer's interface) ----
+    @property
+    def priorities(self):
+        return self.ledger.priorities
+
+    @property
+    def lengths(self):
+        return self.ledger.lengths
+
+    @property
+    def key_gids(self):
+        return self.ledger.key_gids
+
+    def sample_indices(self, batch_size):
+        return self.ledger.sample_indices(batch_size)
+
+    def update_priorities(self, indices, new_priorities):
+        self.ledger.update_priorities(indices, new_priorities)
+
+    def _info(self):
+        size = ctypes.c_int32()
+        lengths = np.zeros(self.capacity, np.int32)
+        gids = np.zeros(self.capacity, np.int32)
+        check(lib.mzgo_replay_info(self._h, ctypes.byref(size), None, ptr(lengths), ptr(gids)))
+        return lengths[:size.value], gids[:size.value]
+
+    def _pushed(self, n):
+        """Enter the last n games the store took into the ledger."""
+        lengths, gids = self._info()
+        for _ in range(max(0, n - len(lengths))):         # (more games than the capacity: evicted unseen)
+            self.ledger.push(0, 0)
+        for L, g in zip(lengths[-n:], gids[-n:]):
+            self.ledger.push(L, g)
+        assert self.ledger.lengths == [int(x) for x in lengths]
+
+    # ---- ingest ----
+    def add_games(self, engine):
+        """Every finished game of ``engine``'s slots, device to device in one
+        launch (mzgo_replay_add_games), as G adds in slot order; only the G
+        lengths come back.  Refuses while a game is still playing."""
+        if engine.counters()["playing"] != 0:
+            raise RuntimeError("add_games: games are still playing on the engine")
+        check(lib.mzgo_replay_add_games(self._h, engine.handle, stream_of(self.device)))
+        self._pushed(engine.G)
+
+    def add(self, trajectory, key_gid=None):
+        """One main.py-format trajectory (observations T+2, actions T, policies
+        T, rewards T+1; ``root_values`` T optional) from the host.  ``key_gid``:
+        the game's search key id for ``reanalyse`` (default: a running count
+        of the games added this way)."""
+        T = len(trajectory["actions"])
+        if T > self.max_moves:
+            raise ValueError(f"trajectory of {T} moves, the store holds at most {self.max_moves}")
+        obs = np.asarray(trajectory["observations"][:T + 1], dtype=np.float64)
+        if obs.shape != (T + 1, 6, self.N, self.N):
+            raise ValueError(f"observations are {obs.shape[1:]} x {obs.shape[0]}, expected at least {T + 1} of "
+                             f"(6, {self.N}, {self.N})")
+        if len(trajectory["rewards"]) != T + 1 or len(trajectory["policies"]) != T:
+            raise ValueError("a trajectory has T actions, T policies and T + 1 rewards")
+        stones, invd, flags = (np.ascontiguousarray(t.numpy()) for t in positions_from_planes(obs))
+        action = np.ascontiguousarray(np.asarray(trajectory["actions"], dtype=np.int32))
+        policy = np.ascontiguousarray(np.asarray(trajectory["policies"], dtype=np.float64).reshape(T, self.A))
+        reward = np.ascontiguousarray(np.asarray(trajectory["rewards"], dtype=np.float64))
+        rv = trajectory.get("root_values")
+        rv = None if rv is None else np.ascontiguousarray(np.asarray(rv, dtype=np.float64).reshape(T))
+        if key_gid is None:
+            key_gid = self._host_adds = getattr(self, "_host_adds", -1) + 1
+        key_gid = int(np.array(int(key_gid) & 0xFFFFFFFF, np.uint32).view(np.int32))
+        check(lib.mzgo_replay_add(self._h, T, ptr(stones), ptr(invd), ptr(flags), ptr(action), ptr(policy),
+                                  ptr(reward), ptr(rv), key_gid, stream_of(self.device)))
+        self._pushed(1)
+
+    def export(self, i):
+        """Game i (0 = oldest) as a main.py-format dict: T+2 observations, T
+        actions, T policies, T+1 rewards, plus ``root_values`` and ``key_gid``."""
+        from .trainer import _planes
+        M, C, A, N = self.max_moves, self.N * self.N, self.A, self.N
+        length, gid = ctypes.c_int32(), ctypes.c_int32()
+        stones = np.empty((M + 1, C), np.int8)
+        invd = np.empty((M + 1, C), np.uint8)
+        flags = np.empty(M + 1, np.uint8)
+        action = np.empty(M, np.int32)
+        policy = np.empty((M, A), np.float64)
+        reward = np.empty(M + 1, np.float64)
+        rv = np.empty(M, np.float64)
+        i = int(i)
+        check(lib.mzgo_replay_export(self._h, i + len(self) if i < 0 else i, ctypes.byref(length), ctypes.byref(gid),
+                                     ptr(stones), ptr(invd), ptr(flags), ptr(action), ptr(policy), ptr(reward),
+                                     ptr(rv), stream_of(self.device)))
+        T = length.value
+        obs = [_planes(stones[t], invd[t], int(flags[t]), N) for t in range(T + 1)]
+        return {
+            "observations": obs + [obs[-1].copy()],
+            "actions": [int(a) for a in action[:T]],
+            "rewards": [float(r) for r in reward[:T + 1]],
+            "policies": [policy[t].copy() for t in range(T)],
+            "root_values": [float(v) for v in rv[:T]],
+            "key_gid": gid.value,
+        }
+
+    # ---- the trainer's batch ----
+    def batch(self, indices, starts, unroll_steps, discount, symmetries=None):
+        """The trainer's targets for B samples in one launch (mzgo_replay_batch):
+        sample b is game ``indices[b]`` from move ``starts[b]`` under symmetry
+        ``symmetries[b]`` (0..7; None = identity).  Returns a dict of CUDA
+        tensors: ``obs0`` f32 [B,6,N,N], ``boot_obs`` f32 [B,K+1,6,N,N],
+        ``acts`` i64 [B,K], ``t_rew`` f32 [B,K], ``t_pol`` f32 [B,K+1,A],
+        ``val`` / ``factor`` f64 [B,K+1] and ``has_boot`` u8 [B,K+1]
+        (``finish_values`` turns the last three and the network's values of
+        ``boot_obs`` into ``t_val``)."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int32).reshape(-1))
+        B, K, N, A, dev = len(idx), int(unroll_steps), self.N, self.A, self.device
+        st = np.ascontiguousarray(np.asarray(starts, dtype=np.int32).reshape(-1))
+        sy = None if symmetries is None else np.ascontiguousarray(np.asarray(symmetries, dtype=np.int32).reshape(-1))
+        if len(st) != B or (sy is not None and len(sy) != B):
+            raise ValueError("batch: indices, starts and symmetries must have one entry per sample")
+        K1 = max(K, 0) + 1
+        out = dict(obs0=torch.empty(B, 6, N, N, device=dev),
+                   boot_obs=torch.empty(B, K1, 6, N, N, device=dev),
+                   acts=torch.empty(B, max(K, 0), dtype=torch.int64, device=dev),
+                   t_rew=torch.empty(B, max(K, 0), device=dev),
+                   t_pol=torch.empty(B, K1, A, device=dev),
+                   val=torch.empty(B, K1, dtype=torch.float64, device=dev),
+                   factor=torch.empty(B, K1, dtype=torch.float64, device=dev),
+                   has_boot=torch.empty(B, K1, dtype=torch.uint8, device=dev))
+        check(lib.mzgo_replay_batch(self._h, ptr(idx), ptr(st), ptr(sy), B, K, float(discount), ptr(out["obs0"]),
+                                    ptr(out["boot_obs"]), ptr(out["acts"]), ptr(out["t_rew"]), ptr(out["t_pol"]),
+                                    ptr(out["val"]), ptr(out["factor"]), ptr(out["has_boot"]), stream_of(dev)))
+        return out
+
+    # ---- reanalysis in place ----
+    def reanalyse(self, reanalyser, games=None):
+        """Search the stored positions of ``games`` (logical indices; all by
+        default) under ``reanalyser``'s engine and weights, position t of a
+        game keyed (key_gid, t), latest moves first; the fresh policy rows and
+        root values replace the stored ones (mzgo_replay_reanalyse).  No
+        position or policy visits the host."""
+        if reanalyser.N != self.N:
+            raise ValueError(f"the reanalyser plays {reanalyser.N}x{reanalyser.N}, the store holds {self.N}x{self.N}")
+        g = None if games is None else np.ascontiguousarray(np.asarray(games, dtype=np.int32).reshape(-1))
+        check(lib.mzgo_replay_reanalyse(self._h, reanalyser.engine.handle, ptr(g), 0 if g is None else len(g),
+                                        stream_of(self.device)))

@@ -29,6 +29,10 @@ on the device, every game of a batch at once) and trains on it:
   representation's three after recomputing its two hidden activations on the
   same kernels); the 1x1 heads stay torch ops on the engine's latents.  The
   default is torch's ops (MIOpen), measured 8 % faster at main.py's sizes.
+  ``train`` also takes a ``mzgo.DeviceReplay`` here: the same targets
+  (``host_targets`` and ``device_targets`` agree bit for bit) assembled on the
+  device from games that never left it, optionally under a random board
+  symmetry per sample (``TrainConfig.symmetries``); both feed ``_unroll_step``.
 
 ``initial_inference_torch`` / ``recurrent_inference_torch`` restate
 main.py:72-144 with torch ops on the module's own parameters (reference
@@ -61,6 +65,7 @@ class TrainConfig:
     lr_step_size: int = 1000          # StepLR(step_size=1000, gamma=0.9), main.py:379
     lr_gamma: float = 0.9
     max_grad_norm: float = 1.0        # main.py:481
+    symmetries: bool = False          # DeviceReplay batches: a random board symmetry per sample (not in main.py)
 
 
 def reward_value_transform(x, epsilon=0.001):
@@ -361,6 +366,18 @@ class MainSelfPlay:
         sp.epoch += 1
         return out
 
+    def play_into(self, replay):
+        """``play()`` with the games left on the device: the G trajectories go
+        into ``replay`` (a ``DeviceReplay`` with this engine's board size and
+        move cap) in one device-to-device launch, in slot order; only their
+        lengths come back.  ``replay.export(i)`` is what ``play()`` returns."""
+        sp = self.sp
+        sp.reset()
+        for _ in range(self.max_moves):
+            sp.move()
+        replay.add_games(sp.engine)          # (refuses while a game is still playing)
+        sp.epoch += 1
+
 
 # ---------------------------------------------------------------------------
 # the training step (main.py:381-522)
@@ -391,6 +408,7 @@ class MuZeroTrainer:
         self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=self.config.lr_step_size,
                                                          gamma=self.config.lr_gamma)
         self.start_index = start_index or (lambda T: random.randint(0, T - 1))
+        self.symmetry_index = lambda: random.randrange(8)      # TrainConfig.symmetries
         self.last = {}
 
     @property
@@ -436,6 +454,9 @@ class MuZeroTrainer:
 
     # -- main.py's step -------------------------------------------------------
     def train(self, replay_buffer, batch_size):
+        from .replay import DeviceReplay
+        if isinstance(replay_buffer, DeviceReplay):
+            return self._train_device(replay_buffer, batch_size)
         batch, indices = replay_buffer.sample(batch_size)
         if not batch or len(batch) < batch_size:
             return None
@@ -489,10 +510,56 @@ class MuZeroTrainer:
                          reward_loss=tot_r / n, lr=self.optimizer.param_groups[0]["lr"])
         return loss_total / n
 
+    def _train_device(self, replay, batch_size):
+        """The batched step on a ``DeviceReplay``: indices drawn on the host
+        (main.py's np.random sequence), targets assembled on the device."""
+        if self.mode != "batched":
+            raise ValueError("a DeviceReplay trains in mode='batched' only: mode='reference' is main.py's "
+                             "per-trajectory step over host trajectories (use PrioritizedReplayBuffer)")
+        if len(replay) < batch_size:
+            return None
+        indices = replay.sample_indices(batch_size)
+        starts = [self.start_index(replay.lengths[i]) for i in indices]
+        syms = [self.symmetry_index() for _ in indices] if self.config.symmetries else None
+        avg = self._unroll_step(*self.device_targets(replay, indices, starts, syms), device_totals=True)
+        replay.update_priorities(indices, [avg] * len(indices))
+        self.scheduler.step()
+        return avg
+
+    def device_targets(self, replay, indices, starts, symmetries=None):
+        """``host_targets`` from a ``DeviceReplay``: one batch-assembly launch,
+        one ``initial_inference`` over all B (K+1) bootstrap rows (a workgroup
+        per row, so a row's value does not depend on its neighbours), one
+        finishing launch.  Nothing comes back to the host."""
+        from .replay import finish_values
+        c, N = self.config, self.net.board_size
+        bt = replay.batch(indices, starts, c.unroll_steps, c.discount, symmetries)
+        with torch.no_grad():
+            _, v, _ = self.net.initial_inference(bt["boot_obs"].view(-1, 6, N, N))
+        t_val = finish_values(bt["val"], bt["factor"], bt["has_boot"], v)
+        return bt["obs0"], bt["acts"], t_val, bt["t_rew"], bt["t_pol"]
+
+    def host_targets(self, batch, starts):
+        """``batch_targets`` as the float32 / int64 tensors the unroll reads,
+        on the trainer's device: (obs0, acts, t_val, t_rew, t_pol)."""
+        dev = self.device
+        obs0, acts, t_val, t_rew, t_pol = self.batch_targets(batch, starts)
+        f32 = lambda x: torch.as_tensor(x, dtype=torch.float32, device=dev)
+        t_val, t_rew, t_pol = f32(t_val), f32(t_rew), f32(t_pol)
+        return f32(obs0), torch.as_tensor(acts, device=dev), t_val, t_rew, t_pol
+
     def _train_batched(self, batch):
+        starts = [self.start_index(len(t["actions"])) for t in batch]
+        return self._unroll_step(*self.host_targets(batch, starts))
+
+    def batch_targets(self, batch, starts):
+        """The host target builder: for trajectories ``batch`` from moves
+        ``starts``, numpy arrays (obs0 f64 [B,6,N,N], acts i64 [B,K], t_val
+        f64 [B,K+1], t_rew f64 [B,K], t_pol f64 [B,K+1,A]) -- rewards,
+        policies, actions and every value target, whose bootstrap values come
+        from one batched ``initial_inference`` under the current weights."""
         c, dev, net = self.config, self.device, self.net
         A, K, B = self.action_size, c.unroll_steps, len(batch)
-        starts = [self.start_index(len(t["actions"])) for t in batch]
         # targets: rewards, policies and the discounted part of every value
         # target; all bootstrap positions in one inference
         t_val = np.zeros((B, K + 1))
@@ -524,9 +591,20 @@ class MuZeroTrainer:
             v = v.squeeze(1).double().cpu().numpy()
             for (b, k, factor), vb in zip(boot_at, v):
                 t_val[b, k] += factor * float(np.float32(vb))
-        f32 = lambda x: torch.as_tensor(x, dtype=torch.float32, device=dev)
-        t_val, t_rew, t_pol = f32(t_val), f32(t_rew), f32(t_pol)
-        obs0 = f32(np.stack([np.asarray(tr["observations"][s]) for tr, s in zip(batch, starts)]))
+        obs0 = np.stack([np.asarray(tr["observations"][s]) for tr, s in zip(batch, starts)])
+        return obs0, acts, t_val, t_rew, t_pol
+
+    def _unroll_step(self, obs0, acts, t_val, t_rew, t_pol, device_totals=False):
+        """One optimizer step on the summed losses of B samples unrolled K
+        steps, from targets on the device (obs0 f32 [B,6,N,N], acts i64 [B,K],
+        t_val f32 [B,K+1], t_rew f32 [B,K], t_pol f32 [B,K+1,A]); returns the
+        mean loss.  The per-term totals of ``self.last`` are read back term by
+        term (the host path), or with ``device_totals`` summed on the device in
+        float64 -- the same sums -- and read with the loss in one copy, the
+        step's only synchronisation."""
+        c, net = self.config, self.net
+        B, K = acts.shape
+        tot = (lambda x: x.detach().sum().double()) if device_totals else (lambda x: x.sum().item())
         self.optimizer.zero_grad()
         fwd0, fwd = ((initial_inference_hip, recurrent_inference_hip) if self.hip_forward
                      else (initial_inference_torch, recurrent_inference_torch))
@@ -535,21 +613,24 @@ class MuZeroTrainer:
         v_l = c.value_loss_weight * self._value_loss(value.squeeze(1), t_val[:, 0])
         p_l = c.policy_loss_weight * kl(logits, t_pol[:, 0])
         per = v_l + p_l
-        tot_v, tot_p, tot_r = v_l.sum().item(), p_l.sum().item(), 0.0
-        acts_t = torch.as_tensor(acts, device=dev)
+        tot_v, tot_p, tot_r = tot(v_l), tot(p_l), 0.0
         for k in range(1, K + 1):
-            latent, reward, value, logits = fwd(net, latent, acts_t[:, k - 1])
+            latent, reward, value, logits = fwd(net, latent, acts[:, k - 1])
             r_l = c.reward_loss_weight * F.mse_loss(reward.squeeze(1), t_rew[:, k - 1], reduction="none")
             v_l = c.value_loss_weight * self._value_loss(value.squeeze(1), t_val[:, k])
             p_l = c.policy_loss_weight * kl(logits, t_pol[:, k])
             per = per + r_l + v_l + p_l
-            tot_r += r_l.sum().item()
-            tot_v += v_l.sum().item()
-            tot_p += p_l.sum().item()
+            tot_r += tot(r_l)
+            tot_v += tot(v_l)
+            tot_p += tot(p_l)
         loss = per.sum()
         loss.backward()
         torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm=c.max_grad_norm)
         self.optimizer.step()
-        self.last = dict(training_loss=loss.item() / B, value_loss=tot_v / B, policy_loss=tot_p / B,
+        if device_totals:
+            total, tot_v, tot_p, tot_r = torch.stack([loss.detach().double(), tot_v, tot_p, tot_r]).tolist()
+        else:
+            total = loss.item()
+        self.last = dict(training_loss=total / B, value_loss=tot_v / B, policy_loss=tot_p / B,
                          reward_loss=tot_r / B, lr=self.optimizer.param_groups[0]["lr"])
-        return loss.item() / B
+        return total / B
