@@ -504,8 +504,11 @@ __device__ __forceinline__ void policy_weights(const float* hw, f32x4 (&wp)[Expa
 
 // The policy sums of every cell of one node -> out[CELLS] (LDS), by the whole
 // workgroup: lane group (wave, cg) takes cells 8 wave + cg + 8 WAVES r.  Y: the
-// parent's [CELLS][C] (HBM), ea: E[a] [9][C], hw: head weights [3][C].  All
-// threads; the caller synchronises before reading out.
+// parent's [CELLS][C], ea: E[a] [9][C], hw: head weights [3][C]; Y and hw
+// both in HBM, or both the expansion's LDS copies (L.yc, L.hw) when they hold
+// this parent's -- the caller's uniform choice, one call site each, so the
+// loads are global or LDS ones, never flat.  All threads; the caller
+// synchronises before reading out.
 template <class G>
 __device__ __forceinline__ void policy_sums_wg(float* out, const float* __restrict__ Y, const float* __restrict__ ea,
                                                const float* hw) {

@@ -669,7 +669,8 @@ __device__ __forceinline__ void verify_load_level(Smem<G>& sm, const SearchParam
 template <class G, class Acc>
 __device__ __forceinline__ void verify_levels(Smem<G>& sm, const SearchParams& sp, const TreeView& TV, const Acc& T,
                                               const int* nact, int D, int B, int l0, int nl, int ract,
-                                              bool with_root, Stamp* st = nullptr, bool loaded = false) {
+                                              bool with_root, Stamp* st = nullptr, bool loaded = false,
+                                              int BE = 0) {
   constexpr int DV = verify_depth<G>();
   typedef VerifyLds<G, DV> V;
   V& vl = *reinterpret_cast<V*>(&sm.u.f.wv[0]);
@@ -677,6 +678,7 @@ __device__ __forceinline__ void verify_levels(Smem<G>& sm, const SearchParams& s
   const int lane = lane_id_local();
   const bool alt = sp.variant == 0;
   const double* bv = sm.u.f.bv;
+  if (BE < B) BE = B;                             // (B + 1: simulation sim + B's walk is checked too)
   if (tid_local() < DV * G::AP) (&vl.exactm[0][0])[tid_local()] = 0;
   // ---- 1a. jobs 0..nl-1: level l0 + k's children (one wave each); jobs
   // nl..2nl-1: x's sequential value sums for those levels, and in the first
@@ -717,7 +719,7 @@ __device__ __forceinline__ void verify_levels(Smem<G>& sm, const SearchParams& s
         vl.invr[k][i] = hii > loi ? 1.0 / (hii - loi) : 0.0;
         vl.sq[k][i] = sqi;
         vl.sx[k][i] = sxi;
-        bad = i >= 1 && i < B && !(sxi > -INFINITY);
+        bad = i >= 1 && i < BE && !(sxi > -INFINITY);
       }
       const uint64_t bb = __ballot(bad);
       if (lane == 0 && bb) atomicOr(reinterpret_cast<unsigned long long*>(&vl.failm[j]), (unsigned long long)bb);
@@ -769,7 +771,7 @@ __device__ __forceinline__ void verify_levels(Smem<G>& sm, const SearchParams& s
       const double qa = dpp::lane(qa_l, kk), cpa = dpp::lane(cpa_l, kk), ia = dpp::lane(ia_l, kk);
 #pragma unroll
       for (int j = 0; j < G::AP; ++j) {
-        if (64 * j >= B) break;                     // (uniform) no simulation i in this register
+        if (64 * j >= BE) break;                    // (uniform) no simulation i in this register
         const double sc = (spread[j] ? (qa - loi[j]) * invr[j] : qa) + (cpa * sqi[j]) * ia;
         beaten[j] |= __ballot(sc > sxi[j] + tol[j]);
         close[j] |= __ballot(!(fabs(sc - sxi[j]) > tol[j]));
@@ -802,7 +804,7 @@ __device__ __forceinline__ void verify_levels(Smem<G>& sm, const SearchParams& s
       for (uint64_t mm = open[j]; mm; mm &= mm - 1, ++c) {
         if (c % G::WAVES != wave) continue;
         const int i = 64 * j + __builtin_ctzll(mm);
-        if (i < 1 || i >= B) continue;
+        if (i < 1 || i >= BE) continue;
         const int xa = vl.x[k];
         const int nx = vl.n0[k] + i;
         const double qx = vl.qx[k][i];
@@ -906,7 +908,13 @@ __device__ __forceinline__ int replay_help(Smem<G>& sm, const SearchParams& sp, 
 template <class G, class Acc>
 __device__ __forceinline__ int verify_batch(Smem<G>& sm, const SearchParams& sp, const EngineArrays& E, int g,
                                             const TreeView& TV, Acc& T, int* nact, int leaf, int D, int B, int nid,
-                                            Stamp* st = nullptr, bool preloaded = false) {
+                                            Stamp* st = nullptr, bool preloaded = false, bool ext = false,
+                                            bool* resume = nullptr) {
+  // ext (LDS trees; the batch takes every unexpanded child of the leaf and
+  // the search goes on after it): column i = B is checked as well -- the walk
+  // of simulation sim + B, after all B backups -- and *resume tells whether
+  // that walk reaches the leaf again (only if the batch is accepted in full):
+  // the caller's next select then starts at the leaf, on the path as it is
   if constexpr (!decltype(sm.u.f)::BATCH) {
     return 0;                                       // (no speculative batches without the batch LDS)
   } else {
@@ -942,22 +950,25 @@ __device__ __forceinline__ int verify_batch(Smem<G>& sm, const SearchParams& sp,
   } else {
     for (int l0 = 0; l0 < D; l0 += DV)
       verify_levels<G, Acc>(sm, sp, TV, T, nact, D, B, l0, D - l0 < DV ? D - l0 : DV, sm.t.ract, l0 == 0, st,
-                            preloaded && l0 == 0);
+                            preloaded && l0 == 0, ext ? B + 1 : B);
   }
   if ((D == 0 || vp.shared) && tid_local() == 0) prefix_sums<G>(T.ws(0), bv, B, alt && ((D + 1) & 1), vl.wroot);
   if (tid_local() == 0) {
-    int f = B;
+    int f = 64 * G::AP;                                // the first failing simulation (none: past every i)
 #pragma unroll
     for (int j = G::AP - 1; j >= 0; --j) {
       uint64_t mm = vl.failm[j];
       if (j == 0) mm &= ~1ull;                         // (simulation i = 0 reached the leaf already)
       if (mm) f = 64 * j + __builtin_ctzll(mm);
     }
-    vl.fail = f < B ? f : B;
+    // (B + 1: all B accepted and, ext, column B passed at every level too;
+    // without ext the bits from B on hold no check)
+    vl.fail = f < B ? f : (ext && !vp.shared && f > B ? B + 1 : B);
   }
   __syncthreads();
   if (st) st->lap(73);
-  const int m = vl.fail;
+  const int m = vl.fail < B ? vl.fail : B;
+  if (resume) *resume = vl.fail > B;
   // ---- 3. the tree takes the m accepted simulations: path node p_d (d >= 1)
   // gets m visits and the first m of its shares, summed in simulation order
   // (prefix_sums' f64 chain, one lane per node) ----
@@ -1043,10 +1054,14 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
     st.lap(4);
   }
   bool pending = false;                                   // a select for `sim` is already in sm.t
+  // where the next select starts: the root, or the last batch's leaf when its
+  // replay showed that the walk comes down to it again (verify_batch, ext;
+  // the path entries and t.ract are that walk's already)
+  int node0 = 0, depth0 = 0;
   while (sim < S) {
     if (!pending) {
       if (wave_id() == 0) {
-        const int a = select_leaf<G>(sm.t, T, sp, key, sim, &st);
+        const int a = select_leaf<G>(sm.t, T, sp, key, sim, &st, node0, depth0);
         if (lane_id_local() == 0) sm.t.action = a;
         st.wave_add(92, 1);
         st.wave_add(95, (unsigned long long)sm.t.depth);
@@ -1054,14 +1069,24 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
       __syncthreads();
     }
     pending = false;
+    node0 = 0;
+    depth0 = 0;
     // the walk reached a lazily expanded node for the first time: its policy
     // sums from its parent's Y and E[a] by the whole workgroup, then wave 0
     // resumes the walk there (it settles the node's priors and goes on)
     while (sm.t.action == kNeedLogits) {
       const int xn = sm.t.leaf, xd = sm.t.depth;
       st.lap(0);
-      policy_sums_wg<G>(sm.t.logits, pool + (size_t)sm.t.lpar * node_floats,
-                        np.etab + (size_t)sm.t.lact * 9 * G::C, np.head_w);
+      // the parent is nearly always the last batch's leaf, whose Y and head
+      // weights the expansion's LDS copies still hold (sm.t.ycache; the
+      // replay's arrays overlay the batch buffers only): the same sums from
+      // LDS instead of L2.  A workgroup-uniform branch; each side's loads
+      // keep their address space.
+      if (y_lds_target<G>(sm) != nullptr && sm.t.ycache == sm.t.lpar)
+        policy_sums_wg<G>(sm.t.logits, sm.u.f.yc, np.etab + (size_t)sm.t.lact * 9 * G::C, sm.u.f.hw);
+      else
+        policy_sums_wg<G>(sm.t.logits, pool + (size_t)sm.t.lpar * node_floats,
+                          np.etab + (size_t)sm.t.lact * 9 * G::C, np.head_w);
       if (tid_local() == 0) sm.t.lognode = xn;
       ++rows;
       __syncthreads();
@@ -1160,7 +1185,10 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
           }
           if (tid_local() == 0) sm.t.ycache = leaf;
           yc = leaf;
-          __syncthreads();
+          // (a batch follows: its entry's barrier, below, orders these writes
+          // too -- nothing reads them before it)
+          const int nun1 = sm.t.nunexp;
+          if (!(BATCH && (nun1 < S - sim ? nun1 : S - sim) >= 2)) __syncthreads();
         } else {
           yc = -1;
         }
@@ -1173,7 +1201,10 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
         st.lap(69);
         if (yc != leaf) load_y<G>(sm, yleaf, np.head_w);
         if constexpr (Acc::LDS) {
-          if (leaf != 0 && sm.t.rowc_node != leaf) {      // the replay's selects read leaf's rows from LDS
+          // the replay's selects read leaf's rows from LDS.  The select that
+          // chose the leaf left them there already (select_leaf, keep_rows)
+          // unless the leaf is the newest node, whose priors wave 1 wrote
+          if (leaf != 0 && sm.t.rowc_node != leaf) {
             for (int i = tid_local(); i < G::A; i += G::THREADS) {
               sm.t.rowc_child[i] = TV.child[(size_t)leaf * G::A + i];
               sm.t.rowc_prior[i] = TV.prior[(size_t)leaf * G::A + i];
@@ -1212,7 +1243,14 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
         st.lap(5);
         if (eager_rows) rows += B;
         if (replay_parallel(shared_jobs<G>(sp), B, depth)) {
-          const int m = verify_batch<G, Acc>(sm, sp, E, g, TV, T, nact, leaf, depth, B, nid, &st, shared_jobs<G>(sp));
+          // the batch takes the leaf's last unexpanded children and another
+          // simulation follows: the replay also checks that one's walk down
+          // to the leaf, and the next select resumes there if it holds
+          const bool ext = Acc::LDS && B == nun && sim + B < S;
+          bool resume = false;
+          const int m = verify_batch<G, Acc>(sm, sp, E, g, TV, T, nact, leaf, depth, B, nid, &st, shared_jobs<G>(sp),
+                                             ext, &resume);
+          if (resume) { node0 = leaf; depth0 = depth; }
           nodes += m;
           sim += m;
           st.lap(63);

@@ -828,6 +828,7 @@ __device__ __forceinline__ int select_leaf(TreeLds<G>& t, const Acc& T, const Se
     }
     double P[G::AP], rw[G::AP];
     int ch[G::AP], rn[G::AP];
+    bool hbm_rows = false;                      // P / ch came from the node's HBM rows
     // all of this node's loads first (one round trip); three sources, chosen
     // by wave-uniform branches (a select between an LDS and a global pointer
     // would compile to a flat load).  A fresh node has no children yet.
@@ -873,8 +874,15 @@ __device__ __forceinline__ int select_leaf(TreeLds<G>& t, const Acc& T, const Se
         const int a = lane + 64 * j;
         P[j] = a < G::A ? (double)q[j] : 0.0;
         ch[j] = -1;
+        // the node is about to become a parent: its rows into the LDS copy
+        // where they are made (the HBM stores stay; see keep_rows below)
+        if constexpr (Acc::LDS)
+          if (a < G::A) { t.rowc_prior[a] = q[j]; t.rowc_child[a] = -1; }
       }
+      if constexpr (Acc::LDS)
+        if (lane == 0) t.rowc_node = node;
     } else {
+      hbm_rows = true;
 #pragma unroll
       for (int j = 0; j < G::AP; ++j) {
         const int a = lane + 64 * j;
@@ -964,6 +972,29 @@ __device__ __forceinline__ int select_leaf(TreeLds<G>& t, const Acc& T, const Se
       t.nunexp = n_unexp;
 #pragma unroll
       for (int j = 0; j < G::AP; ++j) t.umask[j] = unexp[j];
+      // keep_rows (LDS trees): a leaf with two or more unexpanded children is
+      // the parent of the next speculative batch, whose replay reads its rows
+      // from the LDS copy: they go there from the registers that hold them
+      // (here, or where settle_lazy made them) instead of out to HBM and back
+      // at the batch's entry.  The copy stays the node's rows because
+      //   * every later child of the node is attached through set_child, which
+      //     updates rowc_child of rowc_node as it writes the HBM row;
+      //   * only nodes a select reached become rowc_node, and a reached node
+      //     is attached for good: the ids of a batch's dropped children, which
+      //     are reused, never are (their rows are not read before the id's new
+      //     owner is settled or expanded);
+      //   * the newest node's priors (fresh, t.newp) are not copied: wave 1
+      //     may still be writing them.
+      if constexpr (Acc::LDS) {
+        if (hbm_rows && n_unexp >= 2) {
+#pragma unroll
+          for (int j = 0; j < G::AP; ++j) {
+            const int a = lane + 64 * j;
+            if (a < G::A) { t.rowc_prior[a] = (float)P[j]; t.rowc_child[a] = ch[j]; }
+          }
+          if (lane == 0) t.rowc_node = node;
+        }
+      }
       if (root) t.ract = best;
       if (st) st->lap(37);
       return best;

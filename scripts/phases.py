@@ -38,6 +38,14 @@ PHASES = {
 MOVE_SLOTS = [83, 84, 85, 86, 87]
 
 
+def _laps(buf):
+    """The slot sums as f64.  A move stamp pair of which one end was never
+    set (a launch that runs no search leaves the search's stamps at 0) comes
+    out as a difference wrapped round 2^64: such a slot holds no interval and
+    counts as 0 instead of ~1.8e19 (profiles/r6o_mp9_phases.json)."""
+    return np.where(buf >= np.uint64(1) << np.uint64(62), np.uint64(0), buf).astype(np.float64)
+
+
 def _decile(f, game, sp):
     order = np.argsort(game)
     n = max(len(game) // 10, 1)
@@ -89,7 +97,7 @@ def main():
     if os.environ.get("MZGO_MOVE_PARALLEL") == "1":
         # the move-parallel epoch: the queue's workgroups have no games; phase
         # shares over every slot row (the boards launch's own slots 83 / 87 too)
-        fa = buf.astype(np.float64)
+        fa = _laps(buf)
         # the boards launch runs no search: its per-move laps 84-86 and 88-90
         # (representation, root, simulations) hold no interval there
         fa[:, [84, 85, 86, 88, 89, 90]] = 0.0
@@ -105,7 +113,7 @@ def main():
         json.dump(out, open(os.path.join(d, f"{tag}_phases.json"), "w"), indent=1)
         print(json.dumps(out))
         return
-    f = buf[:G].astype(np.float64)
+    f = _laps(buf[:G])
     game = f[:, MOVE_SLOTS].sum(1)                            # each game's busy cycles (its whole epoch)
     sims_slots = sorted({s for k, v in PHASES.items() if k not in ("representation", "board") for s in v} - {85})
     tot = {k: float(f[:, v].sum()) for k, v in PHASES.items()}
