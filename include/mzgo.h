@@ -367,6 +367,45 @@ int mzgo_replay_info(const mzgo_replay* replay, int32_t* size_host, int32_t* hea
  * tower engine (tower = 1); the engine's board_size or max_moves differs from
  * the store's. */
 int mzgo_replay_add_games(mzgo_replay* replay, mzgo_engine* eng, void* stream);
+/* Continuous self-play: play ``n_games`` games on the engine's G = num_games
+ * slots in ONE launch (k_selfplay_games) and push them into the store as
+ * n_games adds in index order.  min(n_games, G, CU count) workgroups each own
+ * one engine slot and claim the next game from a device queue when their own
+ * ends; a finished game is ingested by the workgroup that played it, under
+ * mzgo_replay_add_games' rules.
+ *
+ * Game j (0 <= j < n_games) IS slot j % G of epoch first_epoch + j / G: its
+ * key id is (game_base + j % G) ^ ((first_epoch + j / G) << 24) and every
+ * move's RNG key is (seed, that id, move).  The stored games are therefore
+ * those of ceil(n_games / G) epochs of mzgo_selfplay_reset(epoch) +
+ * mzgo_selfplay_moves(max_moves) + mzgo_replay_add_games (of the last epoch,
+ * its first n_games % G games when that is not 0), byte for byte and in that
+ * order: game j's ring slot is fixed before the launch, whichever workgroup
+ * finishes first.  No helper workgroups and no tail phase run, whatever
+ * MZGO_HELPERS_PER_GAME and MZGO_TAIL_HELPERS say; the records do not depend
+ * on either.
+ *
+ * Synchronises ``stream`` once (the n_games lengths and the error word come
+ * back to the host mirror) and sets the engine's epoch to first_epoch +
+ * ceil(n_games / G) - 1, the last one played.  Counters [0], [1], [2] advance
+ * per move and game as in every self-play launch, [7] once per workgroup.
+ *
+ * THE SLOTS AFTERWARDS: slot b < min(n_games, G, CU count) holds the last
+ * game workgroup b played -- games of different epochs, and which game depends
+ * on the schedule -- and slots past that are untouched.  mzgo_tree_export,
+ * mzgo_records_export, mzgo_records_pack and mzgo_replay_add_games read those
+ * slots as they are: the store is this call's result; mzgo_selfplay_reset
+ * starts the slots afresh.
+ *
+ * MZGO_EINVAL: null replay or engine; n_games < 1; n_games > the capacity (a
+ * ring slot would be written twice in one launch); a board-only engine; a
+ * tower engine; the engine's board_size or max_moves differs from the store's;
+ * a noise hook is set (mzgo_selfplay_inject_noise, mzgo_selfplay_record_noise:
+ * those buffers are indexed by slot).  Nothing is played or stored then.
+ * MZGO_EHIP, after the host mirror is filled: a game stopped on a board error
+ * (slot status >= 16); it is stored with the moves it has, the other games are
+ * unaffected, and the message names the smallest such j. */
+int mzgo_replay_play_games(mzgo_replay* replay, mzgo_engine* eng, int n_games, int first_epoch, void* stream);
 /* Add one game from host buffers (synchronises ``stream``): stones i8
  * [L+1][C], invd u8 [L+1][C], flags u8 [L+1], action i32 [L], policy f64
  * [L][A], reward f64 [L+1], root_value f64 [L] (NULL = zeros).

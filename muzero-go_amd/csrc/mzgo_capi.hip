@@ -887,6 +887,31 @@ static PlayParams play_params(const mzgo_engine* e, int arena, int moves) {
   return pp;
 }
 
+}  // extern "C"
+
+// the device replay store's continuous self-play (mzgo_replay_play_games, mzgo_replay.hip)
+bool mzgo::engine_noise_hooked(const mzgo_engine* e) { return e->noise != nullptr || e->noise_out != nullptr; }
+
+int mzgo::engine_play_games(mzgo_engine* e, const GamesArgs& ga, hipStream_t s) {
+  int rc = e->sync_weights();
+  if (rc) return rc;
+  const SearchParams sp = e->search_params();          // (no helpers, no tail phase, network 0)
+  PlayParams pp = play_params(e, 0, e->M);
+  pp.epoch = ga.epoch0;                                // (the kernel derives every game's own epoch from it)
+  pp.noise = nullptr;
+  pp.noise_out = nullptr;
+  const int ncu = device_cus();
+  int wg = std::min(ga.n, e->G);                       // workgroup b owns slot b
+  if (ncu > 0 && ncu < wg) wg = ncu;
+  HIPCHK(hipMemsetAsync(ga.head, 0, sizeof(unsigned), s));
+  HIPCHK(hipMemsetAsync(ga.error, 0x7f, sizeof(int), s));
+  HIPCHK(e->ks->selfplay_games(e->np, sp, pp, e->E, ga, wg, s));
+  e->epoch = ga.epoch0 + (ga.n + e->G - 1) / e->G - 1;
+  return MZGO_OK;
+}
+
+extern "C" {
+
 int mzgo_selfplay_move(mzgo_engine* e, void* stream) { return mzgo_selfplay_moves(e, 1, stream); }
 
 int mzgo_selfplay_set_timing(mzgo_engine* e, int on) {

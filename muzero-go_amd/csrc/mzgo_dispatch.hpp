@@ -30,6 +30,8 @@ struct KernelSet {
                              int G, int workgroups, hipStream_t);
   hipError_t (*reanalyse)(const NetParams& np, const SearchParams&, const EngineArrays&, const ReanalyseArgs&,
                           int workgroups, hipStream_t);
+  hipError_t (*selfplay_games)(const NetParams& np, const SearchParams&, const PlayParams&, const EngineArrays&,
+                               const GamesArgs&, int workgroups, hipStream_t);
 };
 
 const KernelSet* find_kernels(int N, int C);
@@ -88,12 +90,17 @@ struct Launch {
     hipLaunchKernelGGL((k_reanalyse_queue<N, C>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, E, ra);
     return hipGetLastError();
   }
+  static hipError_t games(const NetParams& np, const SearchParams& sp, const PlayParams& pp, const EngineArrays& E,
+                          const GamesArgs& ga, int workgroups, hipStream_t s) {
+    hipLaunchKernelGGL((k_selfplay_games<N, C>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, pp, E, ga);
+    return hipGetLastError();
+  }
   static KernelSet table() {
     typedef Geo<N, C> G;
     return KernelSet{N, C, sizeof(Smem<G>), rep_needs_scratch<G>() ? 64 * N * N : 0,
                      Smem<G>::GLOBAL_Y ? 1 : 0, TailConvs<G>::value ? 1 : 0, &ii, &ri, &search, &breset, &bstep,
                      &bplanes,
-                     &move, &boards, &queue, &reanalyse};
+                     &move, &boards, &queue, &reanalyse, &games};
   }
 };
 

@@ -7,6 +7,7 @@
 // brings in Smem and the conv wrappers, mzgo_smem.hpp).
 #pragma once
 #include "mzgo_jobs.hpp"
+#include "mzgo_replay.hpp"
 
 namespace mzgo {
 
@@ -1486,16 +1487,20 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
 // ---------------------------------------------------------------------------
 // Boards
 // ---------------------------------------------------------------------------
-template <int N, int C>
-__global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_waves_per_eu(Geo<N, C>::WPE, Geo<N, C>::WPE))) k_board_reset(EngineArrays E) {
-  typedef Geo<N, C> G;
-  const int g = blockIdx.x;
+// slot g <- an empty board and a game not yet begun
+template <class G>
+__device__ __forceinline__ void board_reset_slot(const EngineArrays& E, int g) {
   for (int c = tid_local(); c < G::CELLS; c += G::THREADS) {
     E.stones[(size_t)g * G::CELLS + c] = 0;
     E.invd[(size_t)g * G::CELLS + c] = 0;
   }
   if (tid_local() < 4) E.meta[g * 4 + tid_local()] = 0;
   if (tid_local() == 0) { E.status[g] = 0; E.game_len[g] = 0; E.final_reward[g] = 0.0; }
+}
+
+template <int N, int C>
+__global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_waves_per_eu(Geo<N, C>::WPE, Geo<N, C>::WPE))) k_board_reset(EngineArrays E) {
+  board_reset_slot<Geo<N, C>>(E, blockIdx.x);
 }
 
 // Step every slot with actions[g] >= 0 (gogame.next_state); status[g] gets a
@@ -1536,6 +1541,89 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
     p[3 * G::CELLS + j] = E.invd[(size_t)g * G::CELLS + j];
     p[4 * G::CELLS + j] = mm[1]; p[5 * G::CELLS + j] = mm[2];
   }
+}
+
+// ---------------------------------------------------------------------------
+// One self-play move of the game in slot g (run_self_play_game's loop body,
+// self_play.py:465-507): record the observation, search, choose, step the
+// board, record the result.  The board is in LDS (sm.stone, sm.invd, m) and
+// stays there; slot g is where the game is stored -- its tree, board and
+// record rows -- and key_id() (a game_key_id) is who the game is: its RNG keys
+// come from that id alone.  (pp.arena and the noise hooks index by slot: their
+// launches store game g of one epoch in slot g.)  All threads; returns
+// whether the game is over (finish_move).  The kernels that play whole games
+// a workgroup each call this: k_selfplay_move and k_selfplay_games.
+// (The id is a callable, evaluated where the key is formed: as a value
+// computed by the caller it is live across the move's laundered arguments,
+// and k_selfplay_move<19,96> spilled a second VGPR, 8 -> 12 B/lane.)
+// ---------------------------------------------------------------------------
+template <class G, class KeyId>
+__device__ __forceinline__ bool selfplay_one_move(Smem<G>& sm, const NetParams& np_a_arg, const NetParams& np_b_arg,
+                                                  const SearchParams& sp, const PlayParams& pp,
+                                                  const EngineArrays& E_arg, int g, KeyId key_id, BoardMeta& m) {
+#ifdef MZGO_STAMPS
+  unsigned long long tm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  tm[0] = __builtin_amdgcn_s_memtime();
+#else
+  unsigned long long* tm = nullptr;
+#endif
+  const int mv = m.moves;
+  // this move's view of the arguments (launder_global: no address arithmetic
+  // of the move is hoisted above this point)
+  const EngineArrays E = launder_arrays(E_arg);
+  const NetParams np_a = launder_params(np_a_arg), np_b = launder_params(np_b_arg);
+  // arena (main.py:535-549): turn 0 = "current" (np_a), 1 = "best" (np_b); game
+  // i starts with turn i % 2 (evaluate, :597-599)
+  // (field by field: a reference chosen between the two by-value kernel
+  // arguments would copy both to scratch)
+  const NetParams np = select_params(pp.arena && (((pp.game_base + g) + mv) & 1), np_b, np_a);
+  const size_t rec = (size_t)g * E.max_moves + mv;
+  record_observation<G>(E, rec, sm.stone, sm.invd, m);
+  const uint64_t key = move_key(sp, key_id(), mv);
+  const BoardMeta m0 = m;
+  const double* noise = pp.noise ? pp.noise + ((size_t)g * E.max_moves + mv) * G::A : nullptr;
+  double* noise_out = pp.noise_out ? pp.noise_out + ((size_t)g * E.max_moves + mv) * G::A : nullptr;
+#ifdef MZGO_STAMPS
+  tm[1] = __builtin_amdgcn_s_memtime();
+#endif
+  SearchParams spm = launder_search(sp);
+  spm.net = (pp.arena && (((pp.game_base + g) + mv) & 1)) ? 1 : 0;
+  run_search<G>(sm, np, spm, E, g, [&](int c, int j) { return board_plane<G>(sm.stone, sm.invd, m0, c, j); },
+                noise, key, tm ? tm + 2 : nullptr, noise_out);
+#ifdef MZGO_STAMPS
+  tm[4] = __builtin_amdgcn_s_memtime();
+#endif
+
+  const TreeView T = TreeViewOf<G>::make(E, g);
+  if (wave_id() == 0) {
+    const int a = choose_move_action<G>(sm.t, T, sp, pp, mv, key, E.rec_policy + rec * G::A);
+    if (lane_id_local() == 0) {
+      sm.bc[0] = a;
+      E.rec_action[rec] = a;
+      E.rec_value[rec] = root_value(T);
+    }
+  }
+  __syncthreads();
+  BoardLds<G> b = board_lds<G>(sm);
+  double w;
+  const int st = play_action<G>(E, g, b, m, sm.bc[0], pp.komi, w);
+#ifdef MZGO_STAMPS
+  // move phases (slots 83-87): board load + record, representation, root
+  // priors, the simulations, action choice + board step
+  if (tid_local() == 0 && E.stamps) {
+    const unsigned long long t5 = __builtin_amdgcn_s_memtime();
+    unsigned long long* sl = E.stamps + (size_t)blockIdx.x * kStampPhases;
+    sl[83] += tm[1] - tm[0];
+    sl[84] += tm[2] - tm[1];
+    sl[85] += tm[3] - tm[2];
+    sl[86] += tm[4] - tm[3];
+    sl[87] += t5 - tm[4];
+    sl[88] += tm[5] - tm[1];                     // representation: board planes + conv1
+    sl[89] += tm[6] - tm[5];                     //   conv2
+    sl[90] += tm[2] - tm[6];                     //   conv3 + heads
+  }
+#endif
+  return finish_move<G>(E, sp, g, rec, st, m, w);
 }
 
 // ---------------------------------------------------------------------------
@@ -1608,70 +1696,10 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
   // them): a game's moves run back to back on its CU instead of every move of
   // every game waiting for the slowest game's move at a launch boundary
   for (int step = 0; step < pp.moves; ++step) {
-#ifdef MZGO_STAMPS
-  unsigned long long tm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  tm[0] = __builtin_amdgcn_s_memtime();
-#else
-  unsigned long long* tm = nullptr;
-#endif
-  const int mv = m.moves;
-  // this move's view of the arguments (launder_global: no address arithmetic
-  // of the move is hoisted above this point)
-  const EngineArrays E = launder_arrays(E_arg);
-  const NetParams np_a = launder_params(np_a_arg), np_b = launder_params(np_b_arg);
-  // arena (main.py:535-549): turn 0 = "current" (np_a), 1 = "best" (np_b); game
-  // i starts with turn i % 2 (evaluate, :597-599)
-  // (field by field: a reference chosen between the two by-value kernel
-  // arguments would copy both to scratch)
-  const NetParams np = select_params(pp.arena && (((pp.game_base + g) + mv) & 1), np_b, np_a);
-  const size_t rec = (size_t)g * E.max_moves + mv;
-  record_observation<G>(E, rec, sm.stone, sm.invd, m);
-  const uint64_t key = move_key(sp, pp, g, mv);
-  const BoardMeta m0 = m;
-  const double* noise = pp.noise ? pp.noise + ((size_t)g * E.max_moves + mv) * G::A : nullptr;
-  double* noise_out = pp.noise_out ? pp.noise_out + ((size_t)g * E.max_moves + mv) * G::A : nullptr;
-#ifdef MZGO_STAMPS
-  tm[1] = __builtin_amdgcn_s_memtime();
-#endif
-  SearchParams spm = launder_search(sp);
-  spm.net = (pp.arena && (((pp.game_base + g) + mv) & 1)) ? 1 : 0;
-  run_search<G>(sm, np, spm, E, g, [&](int c, int j) { return board_plane<G>(sm.stone, sm.invd, m0, c, j); },
-                noise, key, tm ? tm + 2 : nullptr, noise_out);
-#ifdef MZGO_STAMPS
-  tm[4] = __builtin_amdgcn_s_memtime();
-#endif
-
-  const TreeView T = TreeViewOf<G>::make(E, g);
-  if (wave_id() == 0) {
-    const int a = choose_move_action<G>(sm.t, T, sp, pp, mv, key, E.rec_policy + rec * G::A);
-    if (lane_id_local() == 0) {
-      sm.bc[0] = a;
-      E.rec_action[rec] = a;
-      E.rec_value[rec] = root_value(T);
-    }
-  }
-  __syncthreads();
-  BoardLds<G> b = board_lds<G>(sm);
-  double w;
-  const int st = play_action<G>(E, g, b, m, sm.bc[0], pp.komi, w);
-#ifdef MZGO_STAMPS
-  // move phases (slots 83-87): board load + record, representation, root
-  // priors, the simulations, action choice + board step
-  if (tid_local() == 0 && E.stamps) {
-    const unsigned long long t5 = __builtin_amdgcn_s_memtime();
-    unsigned long long* sl = E.stamps + (size_t)blockIdx.x * kStampPhases;
-    sl[83] += tm[1] - tm[0];
-    sl[84] += tm[2] - tm[1];
-    sl[85] += tm[3] - tm[2];
-    sl[86] += tm[4] - tm[3];
-    sl[87] += t5 - tm[4];
-    sl[88] += tm[5] - tm[1];                     // representation: board planes + conv1
-    sl[89] += tm[6] - tm[5];                     //   conv2
-    sl[90] += tm[2] - tm[6];                     //   conv3 + heads
-  }
-#endif
-  if (finish_move<G>(E, sp, g, rec, st, m, w)) break;
-  __syncthreads();                               // this move's LDS reads before the next move's writes
+    if (selfplay_one_move<G>(sm, np_a_arg, np_b_arg, sp, pp, E_arg, g,
+                             [&]() { return game_key_id(pp.game_base, g, pp.epoch); }, m))
+      break;
+    __syncthreads();                               // this move's LDS reads before the next move's writes
   }
   release_helpers();
   tail_phase();
@@ -1895,6 +1923,68 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
       visit_policy<G>(sm.t, T, sp.variant, 1, launder_global(ra.policy) + (size_t)i * G::A, vc, msum);
     }
     __syncthreads();                               // this search's LDS reads before the next board
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Continuous self-play (mzgo_replay_play_games): any n games on the engine's
+// G slots from one queue, finished games going straight into the replay
+// store.  The schedule is k_search_queue's with whole games as the items: a
+// persistent grid of min(n, G, CUs) workgroups, workgroup b owning slot b --
+// tree, board and record rows -- for the whole launch and claiming the next
+// game, in index order, when its own ends; the launch's tail (the last games
+// running while other CUs idle) is paid once per call, not once per G games.
+//
+// Queue game j IS slot j % G of epoch epoch0 + j / G: its key id is
+// game_key_id(game_base, j % G, epoch0 + j / G), so its moves, searches and
+// record are those of ceil(n / G) epochs of reset + whole-game launch +
+// ingest, whichever workgroup plays it.  The slot that stores it (b) is not
+// its identity (selfplay_one_move).  Its ring slot, (first + j) % cap, is
+// fixed by j as well: the store's order does not depend on who finished first.
+//
+// No helper workgroups, no tail phase (sp.helpers = sp.tail = 0: 19x19 runs
+// its batch expansions on the game's own workgroup, as k_reanalyse_queue), one
+// network (pp.arena = 0), no noise hooks (they index by slot).  Workgroups
+// share one word, the queue head.  The ingest reads what this workgroup's own
+// threads stored, so the barrier before it (workgroup scope) is all it needs.
+// ---------------------------------------------------------------------------
+template <int N, int C>
+__global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_waves_per_eu(Geo<N, C>::WPE, Geo<N, C>::WPE))) k_selfplay_games(NetParams np_arg, SearchParams sp, PlayParams pp,
+                                                              EngineArrays E_arg, GamesArgs ga) {
+  typedef Geo<N, C> G;
+  __shared__ Smem<G> sm;
+  static_assert(sizeof(Smem<G>) <= 160 * 1024, "one workgroup per CU: the whole LDS at most");
+  if constexpr (G::WINO) wino_raw_zero<G>(sm.raw);        // zero halo of the conv input planes
+  const int slot = blockIdx.x;
+  if (tid_local() == 0) atomicAdd(&E_arg.counters[6], 1ull);
+  for (;;) {
+    if (tid_local() == 0) sm.bc[0] = (int)atomicAdd(ga.head, 1u);
+    __syncthreads();
+    const int j = __builtin_amdgcn_readfirstlane(sm.bc[0]);
+    __syncthreads();                               // (sm.bc is the search's scratch too)
+    if (j >= ga.n) break;
+    const uint32_t kid = game_key_id(pp.game_base, j % ga.G, ga.epoch0 + j / ga.G);
+    // a new game in the slot: k_board_reset's state, and its board in LDS
+    board_reset_slot<G>(E_arg, slot);
+    for (int c = tid_local(); c < G::CELLS; c += G::THREADS) {
+      sm.stone[c] = 0;
+      sm.invd[c] = 0;
+    }
+    BoardMeta m{0, 0, 0, 0};
+    __syncthreads();
+    for (int step = 0; step < pp.moves; ++step) {
+      if (selfplay_one_move<G>(sm, np_arg, np_arg, sp, pp, E_arg, slot, [&]() { return kid; }, m)) break;
+      __syncthreads();                             // this move's LDS reads before the next move's writes
+    }
+    __syncthreads();                               // the game's record and board: every thread's stores
+    // (tid 0 is finish_move's leader: it reads its own store)
+    if (tid_local() == 0 && E_arg.status[slot] >= 16) atomicMin(ga.error, j);
+    const ReplayEngineView V{N, ga.G, E_arg.max_moves, C, 0, pp.game_base, 0,
+                             E_arg.stones, E_arg.invd, E_arg.meta, E_arg.rec_stones, E_arg.rec_invd,
+                             E_arg.rec_flags, E_arg.rec_action, E_arg.rec_value, E_arg.rec_policy,
+                             E_arg.rec_reward, E_arg.final_reward};
+    replay_ingest_game(ga.R, V, slot, (ga.first + j) % ga.R.cap, (int)kid, tid_local(), G::THREADS);
+    __syncthreads();                               // the ingest's reads before the next game's records
   }
 }
 

@@ -1,8 +1,8 @@
 // mzgo_move.hpp -- one self-play move's record protocol (run_self_play_game's
 // loop body, self_play.py:465-507), defined once for every schedule that
-// plays moves: k_selfplay_move (a workgroup per game), k_selfplay_boards +
-// k_search_queue (the move-parallel epoch) and the tower engine's k_tobs +
-// k_tchoose.
+// plays moves: k_selfplay_move (a workgroup per game), k_selfplay_games (a
+// workgroup per slot, games from a queue), k_selfplay_boards + k_search_queue
+// (the move-parallel epoch) and the tower engine's k_tobs + k_tchoose.
 //
 // A move is: record the observation, derive the move's RNG key, build the
 // legal mask, (search,) choose and record the action, step and score the
@@ -60,8 +60,8 @@ struct EngineArrays {
                                  //     3: dynamics convs run (factored: one per new parent; tower
                                  //     engines: towers evaluated, speculative ones included),
                                  //     4: of those, tail conv jobs (conv_tail), 5: prior rows formed,
-                                 //     6: game workgroups started (k_selfplay_move), 7: tail helpers
-                                 //     whose bounded wait for a job expired (tail_help), 8: expired
+                                 //     6: game workgroups started (k_selfplay_move, k_selfplay_games),
+                                 //     7: tail helpers whose bounded wait for a job expired (tail_help), 8: expired
                                  //     mzgo_stream_wait_started gates (reported, then cleared)
   unsigned long long* stamps;    // [G][kStampPhases] phase cycles (MZGO_STAMPS builds only)
 };
@@ -150,10 +150,20 @@ __device__ __forceinline__ void record_observation(const EngineArrays& E, size_t
   if (T::leader()) E.rec_flags[rec] = flags_pack(m);
 }
 
-// the RNG key of slot g's move mv: the game's global id and generation
+// A game's key id: its global id and generation.  The id, not the slot that
+// stores the game, is the game's identity: k_selfplay_games plays games of
+// several epochs in one slot.  (Host and device: the replay store's mirror of
+// a game's id is this function's value.)
+__host__ __device__ __forceinline__ uint32_t game_key_id(int game_base, int g, int epoch) {
+  return (uint32_t)(game_base + g) ^ ((uint32_t)epoch << 24);
+}
+// the RNG key of move mv of the game with key id ``kid``
+__device__ __forceinline__ uint64_t move_key(const SearchParams& sp, uint32_t kid, int mv) {
+  return stream_key(sp.seed, kid, (uint32_t)mv);
+}
+// ... of slot g's move mv, where slot g holds game g of epoch pp.epoch
 __device__ __forceinline__ uint64_t move_key(const SearchParams& sp, const PlayParams& pp, int g, int mv) {
-  const uint32_t gid = (uint32_t)(pp.game_base + g) ^ ((uint32_t)pp.epoch << 24);
-  return stream_key(sp.seed, gid, (uint32_t)mv);
+  return move_key(sp, game_key_id(pp.game_base, g, pp.epoch), mv);
 }
 
 // valid_mask from the INVD plane (self_play.py:152-158); call with all of T

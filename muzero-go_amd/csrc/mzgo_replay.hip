@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/mzgo.h"
+#include "mzgo_move.hpp"
 #include "mzgo_replay.hpp"
 
 using namespace mzgo;
@@ -34,59 +35,14 @@ constexpr int kThreads = 256;      // k_replay_batch / k_replay_ingest workgroup
 constexpr int kMaxBoard = 19;
 constexpr int kMaxUnroll = 63;     // wave 0 of k_replay_batch holds the K + 1 value targets
 
-// The ring's arrays (device), one allocation per field over all slots.
-// M = max_moves, CELLS = N^2, A = CELLS + 1; a game of length L uses position
-// rows 0..L (the L searched positions, then the final board), L actions,
-// policy rows and root values, and L + 1 rewards (the winner last).
-struct Store {
-  int N, CELLS, A, M, cap;
-  int8_t* stones;      // [cap][M+1][CELLS]
-  uint8_t* invd;       // [cap][M+1][CELLS]
-  uint8_t* flags;      // [cap][M+1]
-  int* action;         // [cap][M]
-  double* policy;      // [cap][M][A]
-  double* reward;      // [cap][M+1]
-  double* root_value;  // [cap][M]
-  int* length;         // [cap]
-  int* key_gid;        // [cap]
-};
-
 // ---------------------------------------------------------------------------
 // Ingest: engine slots g0 .. g0+n-1 -> ring slots (first + i) % cap, one
-// workgroup per game (trajectory_from_record's rules, mzgo/trainer.py).
+// workgroup per game (replay_ingest_game, mzgo_replay.hpp).
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(kThreads) k_replay_ingest(Store R, ReplayEngineView E, int g0, int first) {
-  const int g = g0 + blockIdx.x, slot = (first + blockIdx.x) % R.cap, tid = threadIdx.x;
-  const int* mm = E.meta + (size_t)g * 4;
-  const int done = mm[2] != 0;
-  int L = mm[3];
-  L = L < 0 ? 0 : L > R.M ? R.M : L;
-  const int CELLS = R.CELLS, A = R.A;
-  const size_t src = (size_t)g * E.M, pos = (size_t)slot * (R.M + 1), mv = (size_t)slot * R.M;
-  for (int i = tid; i < L * CELLS; i += kThreads) {
-    R.stones[pos * CELLS + i] = E.rec_stones[src * CELLS + i];
-    R.invd[pos * CELLS + i] = E.rec_invd[src * CELLS + i];
-  }
-  for (int c = tid; c < CELLS; c += kThreads) {           // the board after the last move
-    R.stones[(pos + L) * CELLS + c] = E.stones[(size_t)g * CELLS + c];
-    R.invd[(pos + L) * CELLS + c] = E.invd[(size_t)g * CELLS + c];
-  }
-  for (int i = tid; i < L * A; i += kThreads) R.policy[mv * A + i] = E.rec_policy[src * A + i];
-  // -0.5 on the last move of a game that hit the move cap (main.py:699-702)
-  const bool capped = !done && L >= E.M && L > 0;
-  for (int t = tid; t < L; t += kThreads) {
-    R.flags[pos + t] = E.rec_flags[src + t];
-    R.action[mv + t] = E.rec_action[src + t];
-    R.root_value[mv + t] = E.rec_value[src + t];
-    const double r = E.rec_reward[src + t];
-    R.reward[pos + t] = capped && t == L - 1 ? r + -0.5 : r;
-  }
-  if (tid == 0) {
-    R.flags[pos + L] = (uint8_t)((mm[0] & 1) | ((mm[1] & 1) << 1) | (done << 2));
-    R.reward[pos + L] = done ? E.final_reward[g] : 0.0;       // env.winner(): 0 unless ended
-    R.length[slot] = L;
-    R.key_gid[slot] = (int)((uint32_t)(E.game_base + g) ^ ((uint32_t)E.epoch << 24));
-  }
+  const int g = g0 + blockIdx.x;
+  replay_ingest_game(R, E, g, (first + blockIdx.x) % R.cap, (int)game_key_id(E.game_base, g, E.epoch), threadIdx.x,
+                     kThreads);
 }
 
 // ---------------------------------------------------------------------------
@@ -230,6 +186,7 @@ struct mzgo_replay {
   // reanalysis staging (grown on demand)
   void* stage = nullptr;
   size_t stage_bytes = 0;
+  unsigned* games_q = nullptr;            // mzgo_replay_play_games: the queue head, then the error word
 
   int slot_of(int i) const { return (head + i) % R.cap; }
 
@@ -306,6 +263,7 @@ int mzgo_replay_create(int board_size, int capacity, int max_moves, int device, 
   chk(r->alloc(&R.root_value, cap * M));
   chk(r->alloc(&R.length, cap));
   chk(r->alloc(&R.key_gid, cap));
+  chk(r->alloc(&r->games_q, 2));
   if (rc == MZGO_OK && hipMemset(R.length, 0, cap * sizeof(int)) != hipSuccess)
     rc = set_error(MZGO_EHIP, "mzgo_replay_create: hipMemset failed");
   if (rc == MZGO_OK && hipEventCreateWithFlags(&r->items_read, hipEventDisableTiming) != hipSuccess)
@@ -356,8 +314,52 @@ int mzgo_replay_add_games(mzgo_replay* r, mzgo_engine* eng, void* stream) {
   for (int i = 0; i < n; ++i) {
     const int g = g0 + i, slot = (first + i) % r->R.cap;
     r->len[slot] = std::min(std::max(meta[(size_t)g * 4 + 3], 0), r->R.M);
-    r->gid[slot] = (int)((uint32_t)(E.game_base + g) ^ ((uint32_t)E.epoch << 24));
+    r->gid[slot] = (int)game_key_id(E.game_base, g, E.epoch);
   }
+  return MZGO_OK;
+}
+
+int mzgo_replay_play_games(mzgo_replay* r, mzgo_engine* eng, int n_games, int first_epoch, void* stream) {
+  if (!r || !eng) return set_error(MZGO_EINVAL, "mzgo_replay_play_games: null %s", !r ? "replay" : "engine");
+  if (n_games < 1) return set_error(MZGO_EINVAL, "mzgo_replay_play_games: n_games must be >= 1, got %d", n_games);
+  if (n_games > r->R.cap)
+    return set_error(MZGO_EINVAL, "mzgo_replay_play_games: n_games %d exceeds the capacity %d (a ring slot would be "
+                     "written twice in one launch)", n_games, r->R.cap);
+  ReplayEngineView E;
+  replay_engine_view(eng, &E);
+  if (E.latent_dim == 0)
+    return set_error(MZGO_EINVAL, "mzgo_replay_play_games: board-only engine (latent_dim 0) plays no games");
+  if (E.tower) return set_error(MZGO_EINVAL, "mzgo_replay_play_games: tower engines (tower = 1) are not supported");
+  if (E.N != r->R.N)
+    return set_error(MZGO_EINVAL, "mzgo_replay_play_games: board size mismatch (store %d, engine %d)", r->R.N, E.N);
+  if (E.M != r->R.M)
+    return set_error(MZGO_EINVAL, "mzgo_replay_play_games: max_moves mismatch (store %d, engine %d)", r->R.M, E.M);
+  if (engine_noise_hooked(eng))
+    return set_error(MZGO_EINVAL, "mzgo_replay_play_games: a noise hook is set on the engine (injected and recorded "
+                     "noise are indexed by slot, a slot plays several games here)");
+  hipStream_t s = (hipStream_t)stream;
+  const int n = n_games, cap = r->R.cap;
+  const int first = (r->head + r->size) % cap;              // (push(n)'s answer: n <= cap)
+  const GamesArgs ga{n, E.G, first_epoch, first, r->games_q, (int*)(r->games_q + 1), r->R};
+  if (int rc = engine_play_games(eng, ga, s)) return rc;
+  r->push(n);
+  // one synchronisation: the n lengths (the ring may wrap) and the error word
+  std::vector<int> len(n);
+  int err = 0;
+  const int run = std::min(n, cap - first);
+  RHIPCHK(hipMemcpyAsync(len.data(), r->R.length + first, (size_t)run * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (run < n)
+    RHIPCHK(hipMemcpyAsync(len.data() + run, r->R.length, (size_t)(n - run) * sizeof(int), hipMemcpyDeviceToHost, s));
+  RHIPCHK(hipMemcpyAsync(&err, ga.error, sizeof(int), hipMemcpyDeviceToHost, s));
+  RHIPCHK(hipStreamSynchronize(s));
+  for (int j = 0; j < n; ++j) {
+    const int slot = (first + j) % cap;
+    r->len[slot] = len[j];
+    r->gid[slot] = (int)game_key_id(E.game_base, j % E.G, first_epoch + j / E.G);
+  }
+  if (err < n)
+    return set_error(MZGO_EHIP, "mzgo_replay_play_games: game %d stopped on a board error (stored with the moves it "
+                     "has)", err);
   return MZGO_OK;
 }
 

@@ -1,8 +1,10 @@
 // mzgo_replay.hpp -- what the device replay store (mzgo_replay.hip) shares
 // with the rest of the library: the eight board symmetries as index maps
 // (host and device, so that the tables a test reads are the kernel's), and the
-// engine's side of the store's two engine-facing calls (mzgo_capi.hip owns
-// struct mzgo_engine and the thread-local error string).
+// ring's arrays and the ingest of one game (a device function: the store's
+// own ingest kernel and k_selfplay_games run the same text), and the engine's
+// side of the store's engine-facing calls (mzgo_capi.hip owns struct
+// mzgo_engine and the thread-local error string).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -58,8 +60,83 @@ struct ReplayEngineView {
   const double* final_reward;  // [G]
 };
 
+// The ring's arrays (device), one allocation per field over all slots.
+// M = max_moves, CELLS = N^2, A = CELLS + 1; a game of length L uses position
+// rows 0..L (the L searched positions, then the final board), L actions,
+// policy rows and root values, and L + 1 rewards (the winner last).
+struct Store {
+  int N, CELLS, A, M, cap;
+  int8_t* stones;      // [cap][M+1][CELLS]
+  uint8_t* invd;       // [cap][M+1][CELLS]
+  uint8_t* flags;      // [cap][M+1]
+  int* action;         // [cap][M]
+  double* policy;      // [cap][M][A]
+  double* reward;      // [cap][M+1]
+  double* root_value;  // [cap][M]
+  int* length;         // [cap]
+  int* key_gid;        // [cap]
+};
+
+// Ingest of one game: engine slot g -> ring slot ``slot`` under the key id
+// ``key_gid`` (trajectory_from_record's rules, mzgo/trainer.py), by a team of
+// ``nt`` threads, this one ``tid``: k_replay_ingest's workgroup (one per game
+// after the launch that played it) and k_selfplay_games' (the game's own, at
+// the game's end).  The caller has made the slot's record and board visible
+// to the team.
+__device__ __forceinline__ void replay_ingest_game(const Store& R, const ReplayEngineView& E, int g, int slot,
+                                                   int key_gid, int tid, int nt) {
+  const int* mm = E.meta + (size_t)g * 4;
+  const int done = mm[2] != 0;
+  int L = mm[3];
+  L = L < 0 ? 0 : L > R.M ? R.M : L;
+  const int CELLS = R.CELLS, A = R.A;
+  const size_t src = (size_t)g * E.M, pos = (size_t)slot * (R.M + 1), mv = (size_t)slot * R.M;
+  for (int i = tid; i < L * CELLS; i += nt) {
+    R.stones[pos * CELLS + i] = E.rec_stones[src * CELLS + i];
+    R.invd[pos * CELLS + i] = E.rec_invd[src * CELLS + i];
+  }
+  for (int c = tid; c < CELLS; c += nt) {                 // the board after the last move
+    R.stones[(pos + L) * CELLS + c] = E.stones[(size_t)g * CELLS + c];
+    R.invd[(pos + L) * CELLS + c] = E.invd[(size_t)g * CELLS + c];
+  }
+  for (int i = tid; i < L * A; i += nt) R.policy[mv * A + i] = E.rec_policy[src * A + i];
+  // -0.5 on the last move of a game that hit the move cap (main.py:699-702)
+  const bool capped = !done && L >= E.M && L > 0;
+  for (int t = tid; t < L; t += nt) {
+    R.flags[pos + t] = E.rec_flags[src + t];
+    R.action[mv + t] = E.rec_action[src + t];
+    R.root_value[mv + t] = E.rec_value[src + t];
+    const double r = E.rec_reward[src + t];
+    R.reward[pos + t] = capped && t == L - 1 ? r + -0.5 : r;
+  }
+  if (tid == 0) {
+    R.flags[pos + L] = (uint8_t)((mm[0] & 1) | ((mm[1] & 1) << 1) | (done << 2));
+    R.reward[pos + L] = done ? E.final_reward[g] : 0.0;       // env.winner(): 0 unless ended
+    R.length[slot] = L;
+    R.key_gid[slot] = key_gid;
+  }
+}
+
+// One mzgo_replay_play_games call: the game queue of k_selfplay_games
+// (mzgo_kernels.hpp).  Queue game j is slot j % G of epoch epoch0 + j / G and
+// lands in ring slot (first + j) % R.cap.
+struct GamesArgs {
+  int n;             // games in the queue
+  int G;             // the engine's game slots
+  int epoch0;        // the call's first epoch
+  int first;         // ring slot of game 0
+  unsigned* head;    // the queue head (zeroed before the launch)
+  int* error;        // the smallest j whose game stopped on a board error (>= n before the launch)
+  Store R;
+};
+
 // mzgo_capi.hip: fill *v from an engine (no checks beyond the null pointer)
 void replay_engine_view(const mzgo_engine* eng, ReplayEngineView* v);
+// mzgo_capi.hip: whether a noise hook (mzgo_selfplay_inject_noise / _record_noise) is set
+bool engine_noise_hooked(const mzgo_engine* eng);
+// mzgo_capi.hip: enqueue k_selfplay_games for ga (head and error are set here)
+// and move the engine's epoch to the last one the call plays
+int engine_play_games(mzgo_engine* eng, const GamesArgs& ga, hipStream_t s);
 // mzgo_capi.hip: set mzgo_last_error()'s text and return ``code``
 int set_error(int code, const char* fmt, ...);
 

@@ -23,7 +23,7 @@ from .engine import Engine, EngineConfig
 from .env import GoEnv
 from .net import MuZeroNet
 from .reanalyse import Reanalyser, positions_from_planes, record_ids
-from .replay import DeviceReplay
+from .replay import DeviceReplay, queue_key_gids
 from .resnet import ResMuZeroNet
 from .search import MCTS, MainMCTS, MuZeroAgent
 from .selfplay import GameHistory, SelfPlay, history_from_device, save_batches
@@ -32,4 +32,4 @@ from .weights import deterministic_res_state_dict, deterministic_state_dict
 __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "MuZeroAgent", "SelfPlay",
            "GameHistory", "history_from_device", "save_batches", "deterministic_state_dict", "SelfPlayEvaluator",
            "ResMuZeroNet", "deterministic_res_state_dict", "MzgoError", "Reanalyser",
-           "positions_from_planes", "record_ids", "DeviceReplay"]
+           "positions_from_planes", "record_ids", "DeviceReplay", "queue_key_gids"]

@@ -90,6 +90,7 @@ SIGNATURES = {
     "mzgo_replay_destroy": (None, [_P]),
     "mzgo_replay_info": (_I, [_P, _P, _P, _P, _P]),
     "mzgo_replay_add_games": (_I, [_P, _P, _P]),
+    "mzgo_replay_play_games": (_I, [_P, _P, _I, _I, _P]),
     "mzgo_replay_add": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int32, _P]),
     "mzgo_replay_export": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mzgo_replay_batch": (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -228,6 +228,16 @@ class Engine:
         """``moves`` moves of every unfinished game in one launch (mzgo_selfplay_moves)."""
         check(lib.mzgo_selfplay_moves(self._h, int(moves), stream_of(self.device)))
 
+    def play_games(self, replay, n_games, epoch=0):
+        """Continuous self-play (mzgo_replay_play_games): ``n_games`` games on
+        this engine's G slots in one launch, each workgroup claiming the next
+        game when its own ends, every finished game going straight into
+        ``replay`` (a ``DeviceReplay``) in index order.  Game j is slot j % G
+        of epoch ``epoch`` + j // G (``mzgo.replay.queue_key_gids``).
+        Synchronises.  Afterwards the slots hold games of mixed epochs: the
+        store is the result."""
+        check(lib.mzgo_replay_play_games(replay.handle, self._h, int(n_games), int(epoch), stream_of(self.device)))
+
     def arena_move(self, opponent, moves=1):
         """``moves`` moves of every unfinished arena game in one launch: this
         engine's network plays turn 0, ``opponent``'s turn 1 (mzgo_arena_moves)."""

@@ -14,7 +14,8 @@ and serves both consumers of stored games from there:
   engine, the fresh policies and root values written into the store.
 
 Ingest is ``add_games(engine)`` (device to device, one launch; what
-``MainSelfPlay.play_into`` calls), or ``add(trajectory)`` for main.py-format
+``MainSelfPlay.play_into`` calls), the playing launch itself
+(``SelfPlay.play_games_into``: continuous self-play, any number of games), or ``add(trajectory)`` for main.py-format
 dicts from files and tests; ``export(i)`` gives a game back as such a dict.
 
 Only the ledger crosses the bus: each game's length, key id and priority live
@@ -44,6 +45,18 @@ def symmetry_tables(board_size, symmetry):
     dst = np.empty(cells + 1, np.int32)
     check(lib.mzgo_replay_symmetry_table(int(board_size), int(symmetry), ptr(src), ptr(dst)))
     return src, dst
+
+
+def queue_key_gids(n_games, num_games, game_base=0, epoch=0):
+    """Key ids int32 [n_games] of the games one ``play_games_into(n_games)``
+    call stores, in the store's order: queue game j is slot j % num_games of
+    epoch ``epoch`` + j // num_games, so its id is (game_base + j % num_games)
+    ^ ((epoch + j // num_games) << 24) -- ``mzgo.reanalyse.record_ids``' first
+    column for that slot and epoch."""
+    j = np.arange(int(n_games), dtype=np.int64)
+    G = int(num_games)
+    gid = ((int(game_base) + j % G) & 0xFFFFFFFF) ^ (((int(epoch) + j // G) << 24) & 0xFFFFFFFF)
+    return gid.astype(np.uint32).view(np.int32)
 
 
 class ReplayLedger:

@@ -118,12 +118,14 @@ class SelfPlay:
         self.epoch = 0
         self.game_base = game_base
         self._record_epoch = 0      # the generation of the games in the slots (reset())
+        self._mixed_slots = False   # play_games_into() left games of several epochs in the slots
 
     def reset(self, epoch=None):
         if epoch is not None:
             self.epoch = epoch
         self.engine.selfplay_reset(self.epoch)
         self._record_epoch = self.epoch
+        self._mixed_slots = False
 
     def move(self, moves=1):
         """Enqueue ``moves`` moves for every unfinished game, one launch
@@ -143,7 +145,42 @@ class SelfPlay:
         self.epoch += 1
         return hist
 
+    def play_games_into(self, replay, n_games):
+        """Continuous self-play: ``n_games`` games (any number up to the
+        store's capacity) in one launch on the G slots, each slot's workgroup
+        taking the next game when its own ends, the finished games going
+        straight into ``replay`` (a ``DeviceReplay`` with this engine's board
+        size and move cap) in index order.  Game j is slot j % G of epoch
+        ``self.epoch`` + j // G -- the games ``ceil(n_games / G)`` rounds of
+        ``reset()`` + ``move(max_moves)`` + ``replay.add_games`` store -- and
+        ``self.epoch`` advances by that many, so ``play()`` continues the
+        sequence.  Afterwards the slots hold games of mixed epochs:
+        ``histories()`` and ``reanalyse()`` raise until the next ``reset()``
+        (``DeviceReplay.reanalyse`` reanalyses the stored games)."""
+        from ._lib import MzgoError
+        n_games = int(n_games)
+        try:
+            self.engine.play_games(replay, n_games, self.epoch)
+        except MzgoError as e:
+            if "stopped on a board error" not in str(e):
+                raise                                # refused: nothing was played or stored
+            self._played_games(replay, n_games)      # (every game was stored, that one with the moves it has)
+            raise
+        self._played_games(replay, n_games)
+
+    def _played_games(self, replay, n_games):
+        self._mixed_slots = True
+        self.epoch += -(-n_games // self.G)
+        replay._pushed(n_games)
+
+    def _slots_are_one_epoch(self, what):
+        if self._mixed_slots:
+            raise RuntimeError(f"{what}: play_games_into() left games of several epochs in the slots; the replay "
+                               "store holds its games (DeviceReplay.export / reanalyse), reset() starts the slots "
+                               "afresh")
+
     def histories(self):
+        self._slots_are_one_epoch("histories")
         return [history_from_device(self.engine.record(g), self.N, self.discount) for g in range(self.G)]
 
     def reanalyse(self, want_policy=True):
@@ -156,6 +193,7 @@ class SelfPlay:
         whatever the engine's compat -- what a compat "reference" record, whose
         policy is mask / sum(mask), lacks.  The records stay as they are."""
         from .reanalyse import latest_first, record_ids
+        self._slots_are_one_epoch("reanalyse")
         eng = self.engine
         recs = [eng.record(g) for g in range(self.G)]
         lens = [int(r["length"]) for r in recs]

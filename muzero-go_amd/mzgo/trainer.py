@@ -378,6 +378,14 @@ class MainSelfPlay:
         replay.add_games(sp.engine)          # (refuses while a game is still playing)
         sp.epoch += 1
 
+    def play_games_into(self, replay, n_games):
+        """``n_games`` games -- any number up to the store's capacity, not the
+        engine's G -- into ``replay`` from one launch (``SelfPlay.play_games_into``):
+        the games ``ceil(n_games / G)`` calls of ``play_into`` store (of the
+        last, its first ``n_games % G`` when that is not 0), without a launch
+        per move or a tail per G games."""
+        self.sp.play_games_into(replay, n_games)
+
 
 # ---------------------------------------------------------------------------
 # the training step (main.py:381-522)
