@@ -472,6 +472,55 @@ int mzgo_replay_reanalyse(mzgo_replay* replay, mzgo_engine* eng, const int32_t* 
  * MZGO_EINVAL: board_size outside 2..19; symmetry outside 0..7. */
 int mzgo_replay_symmetry_table(int board_size, int symmetry, int32_t* src_host, int32_t* dst_host);
 
+/* --------------------------------------------------------------------------
+ * The trainer's unroll loss in one launch (main.py:431-482: the value, policy
+ * and reward losses of a trajectory's K + 1 unroll steps, which the reference
+ * and mzgo.trainer's batched step build from log_softmax, kl_div, two value
+ * transforms, two mse_loss and their weights and sums, step by step; this call
+ * replaces that protocol and its autograd graph for B samples at once).
+ * All pointers are device pointers to contiguous f32 unless said otherwise.
+ *   logits [K+1][B][A], value [K+1][B], reward [K][B]   the heads' outputs,
+ *                              step-major (the unroll's outputs stacked)
+ *   t_pol [B][K+1][A], t_val [B][K+1], t_rew [B][K]     the targets,
+ *                              sample-major (mzgo_replay_batch's layout)
+ * Per row (b, k), with m = max_a logits, s = sum_a exp(logits - m),
+ * logp = logits - m - log s, p = exp(logits - m) / s and T = sum_a t_pol:
+ *   policy  w_policy * sum_a (xlogy(t, t) - t logp_a); an entry t == 0 adds
+ *           exactly 0 (F.kl_div); d/d logits_a = w_policy (p_a T - t_a), with
+ *           the row's own T (the (float)(1.0 / A) rows do not sum to 1)
+ *   value   w_value d^2, d = h(v) - h(t) with h(x) = sign(x)(sqrt(|x| + 1) - 1)
+ *           + 0.001 x (main.py:66-69) when value_transform != 0, else v - t;
+ *           d/dv = w_value 2 d h'(v), h'(v) = 0.5 / sqrt(|v| + 1) + 0.001 for
+ *           v != 0 and 0.001 at v == 0 (autograd's value: sign(0) = 0)
+ *   reward  (k >= 1) w_reward (r - t)^2; d/dr = w_reward 2 (r - t)
+ * Outputs:
+ *   per_sample f32 [B]   a sample's terms summed in k order: (value + policy)
+ *                        of row 0, then + reward + value + policy per row
+ *   totals f64 [4]       loss, value part, policy part, reward part over all
+ *                        samples, from a fixed-order f64 reduction
+ *   g_logits, g_value, g_reward   d (sum_b per_sample[b]) / d input, in the
+ *                        inputs' layouts
+ * Two launches (k_unroll_loss: a workgroup per sample, a wave per row;
+ * k_unroll_loss_totals: one workgroup), no atomics: the same inputs give the
+ * same bits.  Does not synchronise.  The per-sample parts pass between the
+ * launches in a buffer the library keeps per device, so calls on one device
+ * must be ordered (one stream, or synchronised); it grows (synchronising
+ * ``stream``) only when B exceeds 4096 and every earlier B.
+ * K == 0 has no reward tensors: reward, t_rew and g_reward may be NULL.
+ * MZGO_EINVAL, with the reason in mzgo_last_error(): B < 1; K < 0; A outside
+ * 2..362; a null required pointer. */
+int mzgo_unroll_loss(const float* logits, const float* value, const float* reward, const float* t_pol,
+                     const float* t_val, const float* t_rew, int B, int K, int A, float w_value, float w_policy,
+                     float w_reward, int value_transform, float* per_sample, double* totals, float* g_logits,
+                     float* g_value, float* g_reward, void* stream);
+/* The host twin: the same scalar functions (csrc/mzgo_loss.hpp) run serially
+ * over HOST arrays of the same layouts; the sums over a row run in entry
+ * order.  No device work.  The same MZGO_EINVAL conditions. */
+int mzgo_unroll_loss_host(const float* logits, const float* value, const float* reward, const float* t_pol,
+                          const float* t_val, const float* t_rew, int B, int K, int A, float w_value, float w_policy,
+                          float w_reward, int value_transform, float* per_sample, double* totals, float* g_logits,
+                          float* g_value, float* g_reward);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,12 +15,15 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
   current weights, from one device work queue (fresh policy targets for a trainer)
 * ``DeviceReplay`` -- finished games kept in HBM: the trainer's batches (with board
   symmetries) and reanalysis in place, without the games visiting the host
+* ``unroll_loss`` -- the trainer's value / policy / reward losses of a whole unroll, their
+  per-sample sums and the heads' gradients from one kernel (``TrainConfig.fused_loss``)
 * ``mzgo.play`` -- play.py's interactive human-vs-agent loop (``python -m mzgo.play weights.pth``)
 """
 from ._lib import MzgoError
 from .arena import SelfPlayEvaluator
 from .engine import Engine, EngineConfig
 from .env import GoEnv
+from .loss import unroll_loss, unroll_loss_host
 from .net import MuZeroNet
 from .reanalyse import Reanalyser, positions_from_planes, record_ids
 from .replay import DeviceReplay, queue_key_gids
@@ -32,4 +35,5 @@ from .weights import deterministic_res_state_dict, deterministic_state_dict
 __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "MuZeroAgent", "SelfPlay",
            "GameHistory", "history_from_device", "save_batches", "deterministic_state_dict", "SelfPlayEvaluator",
            "ResMuZeroNet", "deterministic_res_state_dict", "MzgoError", "Reanalyser",
-           "positions_from_planes", "record_ids", "DeviceReplay", "queue_key_gids"]
+           "positions_from_planes", "record_ids", "DeviceReplay", "queue_key_gids", "unroll_loss",
+           "unroll_loss_host"]

@@ -97,6 +97,8 @@ SIGNATURES = {
     "mzgo_replay_finish_values": (_I, [_P, _P, _P, _P, _I, _P, _P]),
     "mzgo_replay_reanalyse": (_I, [_P, _P, _P, _I, _P]),
     "mzgo_replay_symmetry_table": (_I, [_I, _I, _P, _P]),
+    "mzgo_unroll_loss": (_I, [_P] * 6 + [_I] * 3 + [ctypes.c_float] * 3 + [_I] + [_P] * 6),
+    "mzgo_unroll_loss_host": (_I, [_P] * 6 + [_I] * 3 + [ctypes.c_float] * 3 + [_I] + [_P] * 5),
 }
 
 

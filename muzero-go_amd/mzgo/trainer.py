@@ -33,6 +33,16 @@ on the device, every game of a batch at once) and trains on it:
   (``host_targets`` and ``device_targets`` agree bit for bit) assembled on the
   device from games that never left it, optionally under a random board
   symmetry per sample (``TrainConfig.symmetries``); both feed ``_unroll_step``.
+  ``TrainConfig.fused_loss`` (default off) moves the loss arithmetic of the
+  K + 1 steps -- some thirty-five small torch ops each, forward and again
+  backward -- onto one HIP launch (``mzgo.unroll_loss``, csrc/mzgo_loss.hip):
+  the heads' outputs are stacked once, the kernel returns the per-sample
+  losses, the f64 totals and the gradients with respect to every head output,
+  and autograd continues from those into the heads.  With
+  ``TrainConfig.sample_priorities`` (default off) a sampled game's new
+  priority is its own loss (floored at float32's smallest normal) instead of
+  main.py's batch mean, so the store tells sampled games apart; in batched
+  mode the per-sample losses ride in the step's one synchronising copy.
 
 ``initial_inference_torch`` / ``recurrent_inference_torch`` restate
 main.py:72-144 with torch ops on the module's own parameters (reference
@@ -66,6 +76,8 @@ class TrainConfig:
     lr_gamma: float = 0.9
     max_grad_norm: float = 1.0        # main.py:481
     symmetries: bool = False          # DeviceReplay batches: a random board symmetry per sample (not in main.py)
+    fused_loss: bool = False          # batched mode: the unroll's loss and head gradients on mzgo_unroll_loss
+    sample_priorities: bool = False   # a sampled game's priority = its own loss (main.py: the batch mean)
 
 
 def reward_value_transform(x, epsilon=0.001):
@@ -410,6 +422,9 @@ class MuZeroTrainer:
         # profiles/r5_trainer_step.json), so the faster one is the default
         self.hip_forward = False if hip_forward is None else hip_forward
         self.config = config or TrainConfig()
+        if self.config.fused_loss and mode != "batched":
+            raise ValueError("fused_loss needs mode='batched': mode='reference' is main.py's per-trajectory step, "
+                             "whose loss is built and backpropagated one trajectory at a time")
         self.mode = mode
         self.action_size = net.board_size ** 2 + 1
         self.optimizer = torch.optim.Adam(net.parameters(), lr=self.config.learning_rate)
@@ -418,6 +433,7 @@ class MuZeroTrainer:
         self.start_index = start_index or (lambda T: random.randint(0, T - 1))
         self.symmetry_index = lambda: random.randrange(8)      # TrainConfig.symmetries
         self.last = {}
+        self.last_per_sample = None      # TrainConfig.sample_priorities: the last step's per-sample losses (numpy)
 
     @property
     def device(self):
@@ -470,14 +486,24 @@ class MuZeroTrainer:
             return None
         avg = self._train_reference(batch) if self.mode == "reference" else self._train_batched(batch)
         if indices is not None:
-            replay_buffer.update_priorities(indices, [avg] * len(indices))
+            replay_buffer.update_priorities(indices, self._priorities(avg, len(indices)))
         self.scheduler.step()
         return avg
+
+    def _priorities(self, avg, n):
+        """The sampled games' new priorities: the batch's mean loss for every
+        one (main.py:498-499), or with ``sample_priorities`` each game's own
+        loss, kept positive (``np.random.choice`` takes no weight <= 0)."""
+        if not self.config.sample_priorities:
+            return [avg] * n
+        tiny = float(np.finfo(np.float32).tiny)
+        return [max(float(p), tiny) for p in self.last_per_sample]
 
     def _train_reference(self, batch):
         c, dev, net = self.config, self.device, self.net
         A = self.action_size
         loss_total = tot_v = tot_p = tot_r = 0.0
+        per = []
         self.optimizer.zero_grad()                       # once per batch (main.py:391)
         for trajectory in batch:
             T = len(trajectory["actions"])
@@ -512,8 +538,10 @@ class MuZeroTrainer:
             step_loss.backward()
             torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm=c.max_grad_norm)
             self.optimizer.step()
-            loss_total += step_loss.item()
+            per.append(step_loss.item())
+            loss_total += per[-1]
         n = len(batch)
+        self.last_per_sample = np.asarray(per, dtype=np.float32) if c.sample_priorities else None
         self.last = dict(training_loss=loss_total / n, value_loss=tot_v / n, policy_loss=tot_p / n,
                          reward_loss=tot_r / n, lr=self.optimizer.param_groups[0]["lr"])
         return loss_total / n
@@ -530,7 +558,7 @@ class MuZeroTrainer:
         starts = [self.start_index(replay.lengths[i]) for i in indices]
         syms = [self.symmetry_index() for _ in indices] if self.config.symmetries else None
         avg = self._unroll_step(*self.device_targets(replay, indices, starts, syms), device_totals=True)
-        replay.update_priorities(indices, [avg] * len(indices))
+        replay.update_priorities(indices, self._priorities(avg, len(indices)))
         self.scheduler.step()
         return avg
 
@@ -609,9 +637,14 @@ class MuZeroTrainer:
         mean loss.  The per-term totals of ``self.last`` are read back term by
         term (the host path), or with ``device_totals`` summed on the device in
         float64 -- the same sums -- and read with the loss in one copy, the
-        step's only synchronisation."""
+        step's only synchronisation.  ``TrainConfig.fused_loss`` takes the
+        loss, the totals and the heads' gradients from ``mzgo.unroll_loss``
+        instead (``_unroll_step_fused``); ``sample_priorities`` keeps the
+        per-sample losses in ``last_per_sample`` (in that same copy)."""
         c, net = self.config, self.net
         B, K = acts.shape
+        if c.fused_loss:
+            return self._unroll_step_fused(obs0, acts, t_val, t_rew, t_pol)
         tot = (lambda x: x.detach().sum().double()) if device_totals else (lambda x: x.sum().item())
         self.optimizer.zero_grad()
         fwd0, fwd = ((initial_inference_hip, recurrent_inference_hip) if self.hip_forward
@@ -635,10 +668,56 @@ class MuZeroTrainer:
         loss.backward()
         torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm=c.max_grad_norm)
         self.optimizer.step()
-        if device_totals:
+        self.last_per_sample = None
+        if device_totals and c.sample_priorities:
+            back = torch.cat([torch.stack([loss.detach().double(), tot_v, tot_p, tot_r]),
+                              per.detach().double()]).tolist()
+            total, tot_v, tot_p, tot_r = back[:4]
+            self.last_per_sample = np.asarray(back[4:], dtype=np.float32)
+        elif device_totals:
             total, tot_v, tot_p, tot_r = torch.stack([loss.detach().double(), tot_v, tot_p, tot_r]).tolist()
         else:
             total = loss.item()
+            if c.sample_priorities:
+                self.last_per_sample = per.detach().cpu().numpy()
+        self.last = dict(training_loss=total / B, value_loss=tot_v / B, policy_loss=tot_p / B,
+                         reward_loss=tot_r / B, lr=self.optimizer.param_groups[0]["lr"])
+        return total / B
+
+    def _unroll_step_fused(self, obs0, acts, t_val, t_rew, t_pol):
+        """``_unroll_step`` with the loss on the HIP kernel: the K + 1 steps'
+        head outputs are collected and stacked once, ``mzgo.unroll_loss`` gives
+        ``per`` and the f64 totals in one call, and autograd enters the network
+        through its saved head gradients.  One copy brings the totals (and,
+        with ``sample_priorities``, the per-sample losses) back."""
+        from .loss import unroll_loss
+        c, net = self.config, self.net
+        B, K = acts.shape
+        self.optimizer.zero_grad()
+        fwd0, fwd = ((initial_inference_hip, recurrent_inference_hip) if self.hip_forward
+                     else (initial_inference_torch, recurrent_inference_torch))
+        latent, value, logits = fwd0(net, obs0)
+        lgs, vals, rews = [logits], [value.squeeze(1)], []
+        for k in range(1, K + 1):
+            latent, reward, value, logits = fwd(net, latent, acts[:, k - 1])
+            lgs.append(logits)
+            vals.append(value.squeeze(1))
+            rews.append(reward.squeeze(1))
+        per, totals = unroll_loss(torch.stack(lgs), torch.stack(vals), torch.stack(rews) if rews else None,
+                                  t_pol, t_val, t_rew, value_loss_weight=c.value_loss_weight,
+                                  policy_loss_weight=c.policy_loss_weight, reward_loss_weight=c.reward_loss_weight,
+                                  value_transform=c.use_value_transform)
+        loss = per.sum()
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm=c.max_grad_norm)
+        self.optimizer.step()
+        self.last_per_sample = None
+        if c.sample_priorities:
+            back = torch.cat([totals, per.detach().double()]).tolist()
+            self.last_per_sample = np.asarray(back[4:], dtype=np.float32)
+        else:
+            back = totals.tolist()
+        total, tot_v, tot_p, tot_r = back[:4]
         self.last = dict(training_loss=total / B, value_loss=tot_v / B, policy_loss=tot_p / B,
                          reward_loss=tot_r / B, lr=self.optimizer.param_groups[0]["lr"])
         return total / B
