@@ -220,6 +220,16 @@ int mzgo_arena_move(mzgo_engine* eng, mzgo_engine* opponent, void* stream);
 /* ``moves`` arena moves per slot in one launch (as mzgo_selfplay_moves). */
 int mzgo_arena_moves(mzgo_engine* eng, mzgo_engine* opponent, int moves, void* stream);
 int mzgo_selfplay_counters(mzgo_engine* eng, uint64_t* counters_host, void* stream);
+/* Search statistics of the speculative batches after the root's (boards whose
+ * trees live in LDS: 5x5, 6x6, 9x9 with num_simulations + 2 <= 512; zeros
+ * elsewhere), summed over every search of the engine since its creation, three
+ * values: [0] batch children expanded, [1] batch children whose backup value
+ * came from the value cache instead (a batch at the same leaf was cut short
+ * before and had computed it; MZGO_VALUE_CACHE=0 at engine creation turns the
+ * cache off: [1] stays 0 and [0] counts them), [2] batches cut short by their
+ * replay.  Trees and records do not depend on the cache.  Synchronises
+ * ``stream``. */
+int mzgo_search_stats(mzgo_engine* eng, uint64_t* stats_host, void* stream);
 
 /* Move-parallel epoch (no reference counterpart; the schedule, not the
  * protocol): a multi-move mzgo_selfplay_moves under compat "reference"

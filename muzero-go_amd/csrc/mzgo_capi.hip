@@ -243,6 +243,7 @@ struct mzgo_engine {
   int tn = 0;                   // launch pairs recorded since the last read
   int64_t bytes = 0;
   int epoch = 0;
+  int value_cache = 0;          // the searches keep a cut batch's values (EngineArrays::cval allocated)
   const double* noise = nullptr;
   double* noise_out = nullptr;  // test hook: roots' normalised Dirichlet samples [G][M][A]
   TowerHost* tower = nullptr;   // residual-tower network (mzgo_config.tower, BASELINE config 5)
@@ -371,6 +372,7 @@ struct mzgo_engine {
     sp.tail = 0;
     const char* lz = getenv("MZGO_LAZY_ROWS");        // (=0: eager rows in self-play too, an A/B switch)
     sp.lazy_rows = lz && atoi(lz) == 0 ? 0 : 1;
+    sp.value_cache = value_cache;
     return sp;
   }
 };
@@ -531,6 +533,12 @@ int mzgo_engine_create(const mzgo_config* cfg, mzgo_engine** out) {
     chk(e->alloc(&E.path, TSL * (n1 + 1)));
     chk(e->alloc(&E.nodes, TSL));
     chk(e->alloc(&E.nact, TSL * n1));
+    // the value cache of the LDS trees' speculative batches (sim_loop): only
+    // engines whose searches take that path (MZGO_VALUE_CACHE=0: off, an A/B switch)
+    const char* vc = getenv("MZGO_VALUE_CACHE");
+    e->value_cache = !TW && !cfg->direct_dynamics && ks->value_cache_cap > 0 && e->S + 2 <= ks->value_cache_cap &&
+                     !(vc && atoi(vc) == 0);
+    if (e->value_cache) chk(e->alloc(&E.cval, TSL * n1 * A));
     chk(e->alloc(&E.jobs, TSL * job_bytes(A)));
     chk(e->alloc(&E.mpq, 2 * (size_t)G + 1));
     chk(e->alloc(&E.rec_stones, G * M * CELLS));
@@ -1088,6 +1096,16 @@ int mzgo_selfplay_counters(mzgo_engine* e, uint64_t* out, void* stream) {
     HIPCHK(hipStreamSynchronize(s));
     return fail(MZGO_EHIP, "mzgo_stream_wait_started: %llu gate(s) gave up before the target count", c[8]);
   }
+  return MZGO_OK;
+}
+
+int mzgo_search_stats(mzgo_engine* e, uint64_t* out, void* stream) {
+  if (!e || !out) return fail(MZGO_EINVAL, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  unsigned long long c[3] = {};
+  HIPCHK(hipMemcpyAsync(c, e->E.counters + 9, sizeof c, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  out[0] = c[0]; out[1] = c[1]; out[2] = c[2];
   return MZGO_OK;
 }
 

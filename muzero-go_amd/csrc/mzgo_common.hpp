@@ -92,7 +92,9 @@ __host__ __device__ __forceinline__ uint32_t randbelow(uint64_t h, uint32_t n) {
 // 88-90 representation convs, 91-95 select counts (levels at depth >= 2,
 // selects, sequential-replay batches and their simulations, leaf depth sum)
 constexpr int kStampPhases = 96;
-constexpr int kStampLds = 91;          // phases >= this are thread 0's counters, kept in registers
+constexpr int kStampLds = 88;          // phases >= this are thread 0's counters, kept in registers (88-90
+                                       // are added to the buffer directly, per move: no LDS slot -- the
+                                       // 9x9 stamps build has 16 B of LDS to spare)
 #ifdef MZGO_STAMPS
 // Phase sums accumulate in LDS (a global read-modify-write per lap would put
 // an HBM round trip on the measured wave's critical path); flush() adds them

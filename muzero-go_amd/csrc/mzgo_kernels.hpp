@@ -595,7 +595,10 @@ constexpr int verify_depth() { return G::AP > 2 ? 2 : 8; }
 // 24: 77.1 / 78.1 / 79.0 / 77.8 M sims/s (a minimum-B rule at its best, 6:
 // 77.0-77.2); HBM trees with helper workgroups (shared jobs, 19x19): K = 0 /
 // 8 / 16 / 32 / 64: 37.8 / 37.8 / 38.0 / 38.3 / 37.7 M
-// (profiles/r4x_shared_seq_ab.txt)
+// (profiles/r4x_shared_seq_ab.txt).  With the value cache (sim_loop) a
+// re-batch no longer pays an expansion; measured again, same call, three runs
+// each: K = 8 / 16 / 24: 137.6-137.9 / 139.1-139.4 / 137.3-137.6 M
+// (profiles/vc_knobs.txt)
 constexpr int kSeqK = 16, kSharedSeqK = 32;
 __device__ __forceinline__ bool replay_sequential(int B, int depth) { return (B - 1) * (depth + 1) < kSeqK; }
 __device__ __forceinline__ bool replay_parallel(bool shared, int B, int depth) {
@@ -910,12 +913,14 @@ template <class G, class Acc>
 __device__ __forceinline__ int verify_batch(Smem<G>& sm, const SearchParams& sp, const EngineArrays& E, int g,
                                             const TreeView& TV, Acc& T, int* nact, int leaf, int D, int B, int nid,
                                             Stamp* st = nullptr, bool preloaded = false, bool ext = false,
-                                            bool* resume = nullptr) {
+                                            bool* resume = nullptr, bool yleaf_lds = true) {
   // ext (LDS trees; the batch takes every unexpanded child of the leaf and
   // the search goes on after it): column i = B is checked as well -- the walk
   // of simulation sim + B, after all B backups -- and *resume tells whether
   // that walk reaches the leaf again (only if the batch is accepted in full):
-  // the caller's next select then starts at the leaf, on the path as it is
+  // the caller's next select then starts at the leaf, on the path as it is.
+  // yleaf_lds: L.yc holds the leaf's Y (false: a batch whose values came from
+  // the value cache, which loads no Y)
   if constexpr (!decltype(sm.u.f)::BATCH) {
     return 0;                                       // (no speculative batches without the batch LDS)
   } else {
@@ -998,7 +1003,7 @@ __device__ __forceinline__ int verify_batch(Smem<G>& sm, const SearchParams& sp,
       T.set_child(leaf, ai, n2);
       if (leaf == 0) T.add_root_child(ai, v);       // (set_child zeroed the mirror)
     }
-    if (lane == 0) { sm.t.newest = -1; sm.t.ycache = leaf; }
+    if (lane == 0) { sm.t.newest = -1; if (yleaf_lds) sm.t.ycache = leaf; }
   }
   __syncthreads();
   if (st) st->lap(74);
@@ -1039,6 +1044,31 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
   __syncthreads();
 
   int nodes = 1, convs = 0;
+  // The value cache (LDS trees with the batch LDS, factored dynamics).  A
+  // batch at leaf L takes every unexpanded child of L unless the search ends
+  // inside it, and a child's backup value depends on L's Y and its action
+  // only.  So when the replay cuts such a batch at m < B, the children still
+  // unexpanded at L are exactly the dropped ones: their values go to
+  // E.cval[L][action] and L's bit in sm.t.cvm is set (cleared with the tree,
+  // tree_reset_root).  The next batch at L takes its values from there: no Y
+  // reload, no expansion.  Stored at the cut only, by waves other than wave 0
+  // (whose next loads are the pending select's): an accepted batch pays
+  // nothing.  A single expansion (B == 1) at such a leaf keeps expand_heads:
+  // its value is summed per cell, in another fp32 order than expand_wave's
+  // channel-first totals, so the cached value would differ in its last bits.
+  constexpr bool VCACHE = Acc::LDS && BATCH && decltype(sm.u.f)::CACHE;
+  const bool vcache = VCACHE && factored && sp.value_cache != 0 && E.cval != nullptr && !shared_jobs<G>(sp);
+  int nbcomp = 0, nbcache = 0, ncut = 0;              // batch children expanded / from the cache, batches cut
+  // the batch of every unexpanded child of `leaf` was cut at m of B: keep the
+  // dropped children's values (a leaf whose values are stored already, or a
+  // batch the search's end shortened, stores nothing).  All threads.
+  auto cache_cut = [&](int leaf, int m, int B) {
+    double* cv = E.cval + ((size_t)g * ((size_t)E.S + 1) + (size_t)leaf) * G::A;
+    for (int i = m + tid_local() - 64; tid_local() >= 64 && i < B; i += G::THREADS - 64)
+      cv[sm.u.f.acts[i]] = sm.u.f.bv[i];
+    if (tid_local() == 0) sm.t.cvm[leaf >> 5] |= 1u << (leaf & 31);
+    __syncthreads();                                  // (the bit, before the next batch's entry reads it)
+  };
   // prior rows formed (HBM writes of a node's priors + child row): eager
   // expansions, and lazily expanded nodes on a select's first arrival
   int rows = 0;
@@ -1200,7 +1230,14 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
       if (BATCH && B >= 2) {
         // ---- speculative batch of B children of `leaf` ----
         st.lap(69);
-        if (yc != leaf) load_y<G>(sm, yleaf, np.head_w);
+        // a batch at this leaf was cut before: its unexpanded children's
+        // backup values are in E.cval (the value cache, above).  L.yc is then
+        // left as it is: nothing of this batch reads Y (reloading it anyway, so
+        // that a later arrival finds it in LDS, measured 137.0 against 139.3 M
+        // sims/s on the 9x9 epoch, profiles/vc_knobs.txt)
+        bool cached = false;
+        if constexpr (VCACHE) cached = vcache && sm.t.is_cached(leaf);
+        if (!cached && yc != leaf) load_y<G>(sm, yleaf, np.head_w);
         if constexpr (Acc::LDS) {
           // the replay's selects read leaf's rows from LDS.  The select that
           // chose the leaf left them there already (select_leaf, keep_rows)
@@ -1230,7 +1267,24 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
                                                verify_preload<G, Acc>(sm, sp, TV, T, nact, depth);
                                            });
           st.lap(71);
+        } else if (cached) {
+          // the same picks (same draws, same acts); every picked child is one
+          // the cut batch dropped, so its value is the one batch_expand would
+          // form again (it depends on the leaf's Y and the action only) and
+          // its node takes the lazy mark batch_expand<.., LAZY> would set
+          if (wave_id() == 0) {
+            pick_all<G>(um, nun - 1, 1, B - 1, key, sim + 1, sm.u.f.acts, &st);
+            wave_lds_sync();
+            st.lap(71);
+            const double* cv = E.cval + ((size_t)g * ((size_t)E.S + 1) + (size_t)leaf) * G::A;
+            for (int i = lane_id_local(); i < B; i += 64) {
+              sm.u.f.bv[i] = cv[sm.u.f.acts[i]];
+              atomicOr(&sm.t.rawp[(nid + i) >> 5], 1u << ((nid + i) & 31));
+            }
+          }
+          nbcache += B;
         } else {
+          nbcomp += B;
           if (wave_id() == 0) {
             // every pick at once (pick_all), then published together
             pick_all<G>(um, nun - 1, 1, B - 1, key, sim + 1, sm.u.f.acts, &st);
@@ -1250,8 +1304,13 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
           const bool ext = Acc::LDS && B == nun && sim + B < S;
           bool resume = false;
           const int m = verify_batch<G, Acc>(sm, sp, E, g, TV, T, nact, leaf, depth, B, nid, &st, shared_jobs<G>(sp),
-                                             ext, &resume);
+                                             ext, &resume, !cached);
           if (resume) { node0 = leaf; depth0 = depth; }
+          if constexpr (VCACHE)
+            if (m < B) {
+              if (vcache && !cached && B == nun) cache_cut(leaf, m, B);
+              ++ncut;
+            }
           nodes += m;
           sim += m;
           st.lap(63);
@@ -1260,7 +1319,7 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
         }
         if (wave_id() == 0) {
           const int lane = lane_id_local();
-          if (lane == 0) { sm.t.newest = -1; sm.t.ycache = leaf; }
+          if (lane == 0) { sm.t.newest = -1; if (!cached) sm.t.ycache = leaf; }
           wave_lds_sync();
           int m = 0;
           const bool alt = sp.variant == 0;
@@ -1292,6 +1351,11 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
         }
         __syncthreads();
         const int m = sm.t.bcast;
+        if constexpr (VCACHE)
+          if (m < B) {
+            if (vcache && !cached && B == nun) cache_cut(leaf, m, B);
+            ++ncut;
+          }
         nodes += m;
         sim += m;
         pending = m < B;
@@ -1359,6 +1423,9 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
     // direct dynamics: one conv per expansion
     atomicAdd(&E.counters[3], (unsigned long long)(factored ? convs : nodes - 1));
     atomicAdd(&E.counters[5], (unsigned long long)(factored ? rows : nodes - 1));
+    if (nbcomp) atomicAdd(&E.counters[9], (unsigned long long)nbcomp);
+    if (nbcache) atomicAdd(&E.counters[10], (unsigned long long)nbcache);
+    if (ncut) atomicAdd(&E.counters[11], (unsigned long long)ncut);
   }
   __syncthreads();
 }

@@ -20,7 +20,7 @@
 
 namespace mzgo {
 
-constexpr int kCounters = 9;     // EngineArrays::counters
+constexpr int kCounters = 12;    // EngineArrays::counters
 
 // Per-slot device state of an engine (sizes fixed at engine creation).
 struct EngineArrays {
@@ -37,6 +37,8 @@ struct EngineArrays {
   int* path;             // [G][S+2]
   int* nodes;            // [G]  nodes used by the last search
   int* nact;             // [G][S+1] action that created each node (factored: rebuilds its latent)
+  double* cval;          // [G][S+1][A] per (leaf, action): the child's backup value, kept when a batch at
+                         // the leaf was cut (LDS trees; null: no value cache, 19x19 and direct dynamics)
   // boards
   int8_t* stones;        // [G][CELLS]
   uint8_t* invd;         // [G][CELLS]
@@ -62,7 +64,10 @@ struct EngineArrays {
                                  //     4: of those, tail conv jobs (conv_tail), 5: prior rows formed,
                                  //     6: game workgroups started (k_selfplay_move, k_selfplay_games),
                                  //     7: tail helpers whose bounded wait for a job expired (tail_help), 8: expired
-                                 //     mzgo_stream_wait_started gates (reported, then cleared)
+                                 //     mzgo_stream_wait_started gates (reported, then cleared),
+                                 //     9: children of sim_loop's speculative batches expanded, 10: of such
+                                 //     batches' children, taken from cval instead, 11: such batches cut short
+                                 //     by their replay (mzgo_search_stats)
   unsigned long long* stamps;    // [G][kStampPhases] phase cycles (MZGO_STAMPS builds only)
 };
 

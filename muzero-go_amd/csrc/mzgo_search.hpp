@@ -35,6 +35,9 @@ struct SearchParams {
   int lazy_rows;            // Y-streaming boards (19x19) without helpers: batched children keep the
                             // lazy policy head (kLazyRow, as the shared batches do); 0: eager rows
                             // (mzgo_search, whose trees are exported whole)
+  int value_cache;          // LDS trees: a cut batch's dropped children keep their backup values for the
+                            // leaf's next batch (EngineArrays::cval); 0: every batch expands its children
+                            // (MZGO_VALUE_CACHE=0, an A/B switch)
 };
 
 // One game's tree (global memory).  Node 0 is the root; node ids grow by one
@@ -107,6 +110,13 @@ struct TreeLds {
   uint32_t rawp[G::TREE_CAP > 0 ? (G::TREE_CAP + 31) / 32 : 1];
   __device__ __forceinline__ bool is_raw(int n) const {
     if constexpr (G::TREE_CAP > 0) return n < G::TREE_CAP && ((rawp[n >> 5] >> (n & 31)) & 1u);
+    else return false;
+  }
+  // leaves whose unexpanded children all have their backup values in
+  // EngineArrays::cval (a batch at the leaf was cut; see sim_loop)
+  uint32_t cvm[G::TREE_CAP > 0 ? (G::TREE_CAP + 31) / 32 : 1];
+  __device__ __forceinline__ bool is_cached(int n) const {
+    if constexpr (G::TREE_CAP > 0) return n < G::TREE_CAP && ((cvm[n >> 5] >> (n & 31)) & 1u);
     else return false;
   }
 };
@@ -1055,7 +1065,7 @@ template <class G, class Acc>
 __device__ __forceinline__ void tree_reset_root(Acc& T) {
   for (int a = tid_local(); a < G::A; a += G::THREADS) T.set_child(0, a, -1);
   if constexpr (G::TREE_CAP > 0)
-    for (int i = tid_local(); i < (G::TREE_CAP + 31) / 32; i += G::THREADS) T.t.rawp[i] = 0u;
+    for (int i = tid_local(); i < (G::TREE_CAP + 31) / 32; i += G::THREADS) { T.t.rawp[i] = 0u; T.t.cvm[i] = 0u; }
   if (tid_local() == 0) { T.init(0); T.set_path(0, 0); }
 }
 

@@ -298,6 +298,15 @@ class Engine:
                     playing=int(out[3]), dynamics_convs=int(out[4]), tail_convs=int(out[5]),
                     prior_rows=int(out[6]), workgroups_started=int(out[7]), tail_wait_expiries=int(out[8]))
 
+    def search_stats(self):
+        """Speculative-batch statistics of every search since the engine was
+        made (mzgo_search_stats; LDS-tree boards, zeros elsewhere): batch
+        children expanded, batch children whose value came from the value
+        cache instead, batches cut short by their replay."""
+        out = np.zeros(3, np.uint64)
+        check(lib.mzgo_search_stats(self._h, ptr(out), stream_of(self.device)))
+        return dict(batch_children_computed=int(out[0]), batch_children_cached=int(out[1]), batches_cut=int(out[2]))
+
     def wait_started(self, target, stream=None):
         """Diagnostic (scripts/rccl_standin.py; bench.py does not use it):
         enqueue on ``stream`` (default: the current one) a gate that completes
