@@ -348,7 +348,8 @@ int mzgo_records_pack(mzgo_engine* eng, uint8_t* dst, int64_t capacity, int64_t*
  * Logical game i (0 = oldest) lives in slot (head + i) % capacity; a game
  * added to a full store evicts game 0.  The host mirrors only the lengths and
  * key ids (mzgo_replay_info); priorities and sampling are the caller's
- * (mzgo.DeviceReplay keeps main.py's np.random sequence).  Calls on one store
+ * (mzgo.DeviceReplay keeps main.py's np.random sequence) unless the device
+ * ledger and sampler further down are used (mzgo_replay_sample).  Calls on one store
  * must be ordered (one stream, or synchronised): they share index staging.
  * A store is not thread-safe.  Every failure below is reported through
  * mzgo_last_error().
@@ -481,6 +482,77 @@ int mzgo_replay_reanalyse(mzgo_replay* replay, mzgo_engine* eng, const int32_t* 
  * cell src[c]; dst i32 [N*N+1], action a becomes dst[a] (dst[N*N] = N*N).
  * MZGO_EINVAL: board_size outside 2..19; symmetry outside 0..7. */
 int mzgo_replay_symmetry_table(int board_size, int symmetry, int32_t* src_host, int32_t* dst_host);
+
+/* The device priority ledger and sampler (opt-in; independent of whatever
+ * priorities the caller keeps on the host).  Per ring slot the store holds a
+ * sampling weight prio f64 (already raised to the priority exponent) and a
+ * generation gen u32.  mzgo_replay_add_games, mzgo_replay_play_games and
+ * mzgo_replay_add give every game they store weight 1.0 and gen + 1 (one small
+ * launch on their stream).  A slot whose game has no moves weighs 0.
+ *
+ * mzgo_replay_sample draws B distinct games by successive sampling without
+ * replacement: draw t picks game i with probability w_i / (the sum of the
+ * weights not yet picked), from a 64-ary sum tree over the slots (leaves,
+ * sums of 64, sums of 64 of those; capacity <= 64^3).  Two launches
+ * (k_replay_sample_build: a wave per 64 slots; k_replay_sample_draw: one
+ * wave), no host staging, no synchronisation.  With key = stream_key(seed,
+ * 0x53414D50, step) (the engine's counter RNG, oracle/rng.py):
+ *   u = u01(draw(key, 5, t)); target = u * total; at each of the three levels
+ *   the 64 entries' inclusive prefix p comes from six steps d = 1, 2, .., 32 of
+ *   p[i] <- (i >= d ? p[i - d] : 0) + p[i]; the pick is the first non-zero
+ *   entry with p > target, or the last non-zero entry if rounding left none;
+ *   target -= p[pick - 1].  The picked leaf is zeroed and its two ancestors are
+ *   summed again (element 63 of the same scan), never subtracted from.
+ *   start = randbelow(draw(key, 6, t), length); symmetry = randbelow(draw(key,
+ *   7, t), 8) when ``symmetries`` != 0, else 0.
+ * Only f64 +, -, x, compares and integer operations decide the choice, so the
+ * result is defined bit for bit; mzgo_replay_sample_host is the same functions
+ * (csrc/mzgo_replay.hpp) run serially on host arrays in SLOT order.
+ * Device outputs: items i32 [B][3] (slot, start, symmetry), index i32 [B]
+ * (logical, oldest = 0), gen u32 [B] (the slot's generation at the draw) and,
+ * unless NULL, weight f32 [B] = (n_valid w_i / total)^(-beta) over the batch's
+ * largest, in f64 pow from the weights before any removal (n_valid = the games
+ * with moves).
+ * MZGO_EINVAL: null replay, items, index or gen; B < 1; B > the number of
+ * stored games with moves (the host mirror's count); capacity > 64^3; beta
+ * negative or not finite. */
+int mzgo_replay_sample(mzgo_replay* replay, int B, uint64_t seed, uint32_t step, int symmetries, double beta,
+                       int32_t* items, int32_t* index, uint32_t* gen, float* weight, void* stream);
+/* mzgo_replay_sample, then k_replay_batch on the sampler's device items: the
+ * eight output tensors of mzgo_replay_batch for the sampled (game, start,
+ * symmetry) triples.  No host staging, no synchronisation.  MZGO_EINVAL as
+ * mzgo_replay_sample, plus unroll_steps outside 1..63 and null outputs. */
+int mzgo_replay_sample_batch(mzgo_replay* replay, int B, int unroll_steps, double discount, uint64_t seed,
+                             uint32_t step, int symmetries, double beta, int32_t* items, int32_t* index,
+                             uint32_t* gen, float* weight, float* obs0, float* boot_obs, int64_t* acts, float* t_rew,
+                             float* t_pol, double* val, double* factor, uint8_t* has_boot, void* stream);
+/* The sampler's host twin (no device work): prio f64 [cap] and length i32
+ * [cap] in slot order, ``head`` the slot of logical game 0; host outputs
+ * items, index and (unless NULL) weight as above.  MZGO_EINVAL: a null
+ * pointer; cap outside 1..64^3; head outside 0..cap-1; B < 1 or > the slots
+ * with length > 0; a weight of such a slot that is not finite and > 0; beta. */
+int mzgo_replay_sample_host(const double* prio, const int32_t* length, int cap, int head, int B, uint64_t seed,
+                            uint32_t step, int symmetries, double beta, int32_t* items, int32_t* index,
+                            float* weight);
+/* New weights for a sampled batch (k_replay_update_priorities, a thread per
+ * sample; device pointers; does not synchronise).  Slot items[b][0] gets
+ * pow(max(p, FLT_MIN), alpha) -- exactly max(p, FLT_MIN) at alpha == 1 -- with
+ * p = per[b] (f32, a loss per sample) or *mean (f64, one value for all B);
+ * exactly one of the two is non-NULL.  A slot whose generation no longer
+ * equals gen[b] (a newer game has taken it) keeps its weight; so does a slot
+ * whose p is NaN, infinite or negative, and those are counted
+ * (mzgo_replay_skipped_updates).  MZGO_EINVAL: null replay, items or gen; B <
+ * 1; per and mean both or neither; alpha not finite or <= 0. */
+int mzgo_replay_update_priorities(mzgo_replay* replay, const int32_t* items, const uint32_t* gen, const float* per,
+                                  const double* mean, int B, double alpha, void* stream);
+/* The weights and generations of the games held, in logical order, copied to
+ * device buffers of ``size`` entries (either may be NULL; no synchronisation). */
+int mzgo_replay_priorities(mzgo_replay* replay, double* prio, uint32_t* gen, void* stream);
+/* Set the weights of the n = size games held from a host buffer in logical
+ * order (synchronises).  MZGO_EINVAL: n != size; a value not finite and > 0. */
+int mzgo_replay_set_priorities(mzgo_replay* replay, const double* values_host, int n, void* stream);
+/* The number of priority updates refused so far (synchronises). */
+int mzgo_replay_skipped_updates(mzgo_replay* replay, int64_t* count_host, void* stream);
 
 /* --------------------------------------------------------------------------
  * The trainer's unroll loss in one launch (main.py:431-482: the value, policy

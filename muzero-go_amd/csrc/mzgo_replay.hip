@@ -6,10 +6,14 @@
 // assembled from them by one launch per batch, k_replay_batch, which also
 // applies one of the eight board symmetries as an index permutation.  The
 // host keeps only each game's length and key id (and, in Python, its
-// priority): sampling stays main.py's np.random sequence.
+// priority): sampling stays main.py's np.random sequence -- unless the caller
+// opts for the device ledger (a weight and a generation per slot) and its
+// sampler further down: successive sampling without replacement from a 64-ary
+// sum tree (k_replay_sample_build, k_replay_sample_draw), batches assembled
+// from the sampler's device items, priorities written back by a launch.
 //
-// Kernels here use plain vector loads and stores only; workgroups never
-// communicate.  Compiled with -ffp-contract=off like every unit: the value
+// Kernels here use plain vector loads and stores only (and one vector atomic,
+// the count of refused priority updates); workgroups never communicate.  Compiled with -ffp-contract=off like every unit: the value
 // targets repeat the host's f64 operations one by one (no fused multiply-add).
 #include <hip/hip_runtime.h>
 
@@ -167,6 +171,133 @@ __global__ void __launch_bounds__(64) k_replay_scatter(Store R, const int* items
   if (threadIdx.x == 0) R.root_value[q] = value[i];
 }
 
+// ---------------------------------------------------------------------------
+// The priority ledger.  New games: weight 1.0 and the slot's generation + 1,
+// a thread per game, after the launch (or copies) that wrote them.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) k_replay_new_games(Ledger L, int first, int n) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const int slot = (first + i) % L.cap;
+  L.prio[slot] = 1.0;
+  L.gen[slot] += 1u;
+}
+
+// ---------------------------------------------------------------------------
+// The sampler: successive sampling without replacement from a 64-ary sum tree
+// (leaves = slots, level 1 = sums of 64 leaves, level 2 = sums of 64 of those;
+// every sum is element 63 of mzgo_replay.hpp's six-step scan).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ double wave_scan64(double v, int lane) {
+  for (int d = 1; d < 64; d <<= 1) {
+    const double below = __shfl_up(v, d);                  // lane i - d's (lanes < d: their own, unused)
+    v = scan_step(lane, d, v, below);
+  }
+  return v;
+}
+// one level of the descent over the wave's 64 entries x with inclusive prefix
+// p; *target becomes the remainder for the level below
+__device__ __forceinline__ int wave_pick(double x, double p, double* target) {
+  const uint64_t nonzero = __ballot(x > 0.0), over = __ballot(x > 0.0 && p > *target);
+  const int j = pick_entry(over, nonzero);
+  const double below = __shfl(p, j > 0 ? j - 1 : 0);
+  *target = *target - (j > 0 ? below : 0.0);
+  return j;
+}
+
+// a wave per group of 64 slots: the working leaves and the group's sum
+__global__ void __launch_bounds__(kThreads) k_replay_sample_build(Ledger L, const int* length) {
+  const int lane = threadIdx.x & 63, g = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+  if (g >= L.n1) return;                                   // (the whole wave)
+  const int i = g * 64 + lane;
+  double x = 0.0;
+  if (i < L.cap) {
+    x = length[i] > 0 ? L.prio[i] : 0.0;
+    L.leaf[i] = x;
+  }
+  const double p = wave_scan64(x, lane);
+  if (lane == 63) L.l1[g] = p;
+}
+
+struct SampleOut {
+  int* items;          // [B][3] slot, start, symmetry (k_replay_batch's)
+  int* index;          // [B]    logical, oldest = 0
+  uint32_t* gen;       // [B]    the slot's generation at the draw
+  float* weight;       // [B]    importance weights (may be null)
+};
+
+// one workgroup of one wave: level 1 in LDS, level 2 a lane each, B draws
+__global__ void __launch_bounds__(64) k_replay_sample_draw(Ledger L, const int* length, int head, int B, uint64_t key,
+                                                           int symmetries, double beta, int n_valid, SampleOut O) {
+  __shared__ double s1[64 * 64];
+  const int lane = threadIdx.x;
+  const int n1 = L.n1, n2 = (n1 + 63) / 64;
+  for (int i = lane; i < n2 * 64; i += 64) s1[i] = i < n1 ? L.l1[i] : 0.0;
+  __syncthreads();
+  double x2 = 0.0;                                         // lane i: level-2 entry i
+  for (int g = 0; g < n2; ++g) {
+    const double s = __shfl(wave_scan64(s1[g * 64 + lane], lane), 63);
+    if (lane == g) x2 = s;
+  }
+  double total0 = 0.0;
+  for (int t = 0; t < B; ++t) {
+    const double p2 = wave_scan64(x2, lane);
+    const double total = __shfl(p2, 63);
+    if (t == 0) total0 = total;
+    double target = sample_u(key, t) * total;
+    const int j2 = wave_pick(x2, p2, &target);
+    const double x1 = s1[j2 * 64 + lane];
+    const int j1 = wave_pick(x1, wave_scan64(x1, lane), &target);
+    const int g1 = j2 * 64 + j1, i0 = g1 * 64 + lane;
+    double x0 = i0 < L.cap ? L.leaf[i0] : 0.0;
+    const int j0 = wave_pick(x0, wave_scan64(x0, lane), &target);
+    const int slot = min(g1 * 64 + j0, L.cap - 1);
+    const double w = __shfl(x0, j0);
+    // remove the leaf; its two ancestors are summed again, never subtracted from
+    if (lane == j0) {
+      x0 = 0.0;
+      L.leaf[slot] = 0.0;
+    }
+    const double sum0 = __shfl(wave_scan64(x0, lane), 63);
+    const double sum1 = __shfl(wave_scan64(lane == j1 ? sum0 : x1, lane), 63);
+    if (lane == j1) s1[g1] = sum0;
+    if (lane == j2) x2 = sum1;
+    if (lane == 0) {
+      O.items[3 * t] = slot;
+      O.items[3 * t + 1] = sample_start(key, t, length[slot]);
+      O.items[3 * t + 2] = sample_symmetry(key, t, symmetries);
+      O.index[t] = (slot - head + L.cap) % L.cap;
+      O.gen[t] = L.gen[slot];
+      L.pick_w[t] = w;
+    }
+    __syncthreads();                                       // (the leaf and s1 before the next draw reads them)
+  }
+  if (!O.weight) return;
+  // importance weights from the weights before any removal, over the batch's largest
+  double vmax = 0.0;
+  for (int b = lane; b < B; b += 64) vmax = fmax(vmax, pow((double)n_valid * L.pick_w[b] / total0, -beta));
+  for (int d = 32; d > 0; d >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, d));
+  for (int b = lane; b < B; b += 64) O.weight[b] = (float)(pow((double)n_valid * L.pick_w[b] / total0, -beta) / vmax);
+}
+
+// a thread per sample: the sampled slot's new priority, unless the slot has
+// taken another game since (its generation moved on).  ``per`` f32 [B]: each
+// sample's own loss; or ``mean`` f64 [1]: one value for all B.
+__global__ void __launch_bounds__(kThreads) k_replay_update_priorities(Ledger L, const int* items, const uint32_t* gen,
+                                                                       const float* per, const double* mean, int B,
+                                                                       double alpha) {
+  const int b = blockIdx.x * kThreads + threadIdx.x;
+  if (b >= B) return;
+  const int slot = items[3 * b];
+  if (slot < 0 || slot >= L.cap || L.gen[slot] != gen[b]) return;
+  const double p = per ? (double)per[b] : *mean;
+  if (!(p >= 0.0 && p <= 1.79769313486231570815e308)) {   // NaN, inf or negative: the slot keeps its weight
+    atomicAdd(L.skipped, 1u);
+    return;
+  }
+  L.prio[slot] = priority_of(p, alpha);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -187,8 +318,21 @@ struct mzgo_replay {
   void* stage = nullptr;
   size_t stage_bytes = 0;
   unsigned* games_q = nullptr;            // mzgo_replay_play_games: the queue head, then the error word
+  Ledger L{};                             // device priorities, generations and the sampler's scratch
+  int n_valid = 0;                        // slots whose mirrored length is > 0 (the sampler's population)
 
   int slot_of(int i) const { return (head + i) % R.cap; }
+  void set_len(int slot, int length) {
+    n_valid += (length > 0) - (len[slot] > 0);
+    len[slot] = length;
+  }
+  // weight 1.0 and the next generation for the n games from ring slot ``first`` (n <= cap)
+  int new_games(int first, int n, hipStream_t s) {
+    if (n < 1) return MZGO_OK;
+    hipLaunchKernelGGL(k_replay_new_games, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, L, first, n);
+    RHIPCHK(hipGetLastError());
+    return MZGO_OK;
+  }
 
   template <class T>
   int alloc(T** p, size_t n) {
@@ -264,7 +408,19 @@ int mzgo_replay_create(int board_size, int capacity, int max_moves, int device, 
   chk(r->alloc(&R.length, cap));
   chk(r->alloc(&R.key_gid, cap));
   chk(r->alloc(&r->games_q, 2));
-  if (rc == MZGO_OK && hipMemset(R.length, 0, cap * sizeof(int)) != hipSuccess)
+  Ledger& L = r->L;
+  L.cap = capacity;
+  L.n1 = (capacity + 63) / 64;
+  chk(r->alloc(&L.prio, cap));
+  chk(r->alloc(&L.gen, cap));
+  chk(r->alloc(&L.leaf, cap));
+  chk(r->alloc(&L.l1, (size_t)L.n1));
+  chk(r->alloc(&L.pick_w, cap));
+  chk(r->alloc(&L.skipped, 1));
+  if (rc == MZGO_OK && (hipMemset(R.length, 0, cap * sizeof(int)) != hipSuccess ||
+                        hipMemset(L.prio, 0, cap * sizeof(double)) != hipSuccess ||
+                        hipMemset(L.gen, 0, cap * sizeof(uint32_t)) != hipSuccess ||
+                        hipMemset(L.skipped, 0, sizeof(unsigned)) != hipSuccess))
     rc = set_error(MZGO_EHIP, "mzgo_replay_create: hipMemset failed");
   if (rc == MZGO_OK && hipEventCreateWithFlags(&r->items_read, hipEventDisableTiming) != hipSuccess)
     rc = set_error(MZGO_EHIP, "mzgo_replay_create: hipEventCreate failed");
@@ -308,12 +464,13 @@ int mzgo_replay_add_games(mzgo_replay* r, mzgo_engine* eng, void* stream) {
   const int first = r->push(n);
   hipLaunchKernelGGL(k_replay_ingest, dim3(n), dim3(kThreads), 0, s, r->R, E, g0, first);
   RHIPCHK(hipGetLastError());
+  if (int rc = r->new_games(first, n, s)) return rc;
   std::vector<int> meta((size_t)E.G * 4);
   RHIPCHK(hipMemcpyAsync(meta.data(), E.meta, meta.size() * sizeof(int), hipMemcpyDeviceToHost, s));
   RHIPCHK(hipStreamSynchronize(s));
   for (int i = 0; i < n; ++i) {
     const int g = g0 + i, slot = (first + i) % r->R.cap;
-    r->len[slot] = std::min(std::max(meta[(size_t)g * 4 + 3], 0), r->R.M);
+    r->set_len(slot, std::min(std::max(meta[(size_t)g * 4 + 3], 0), r->R.M));
     r->gid[slot] = (int)game_key_id(E.game_base, g, E.epoch);
   }
   return MZGO_OK;
@@ -343,6 +500,7 @@ int mzgo_replay_play_games(mzgo_replay* r, mzgo_engine* eng, int n_games, int fi
   const GamesArgs ga{n, E.G, first_epoch, first, r->games_q, (int*)(r->games_q + 1), r->R};
   if (int rc = engine_play_games(eng, ga, s)) return rc;
   r->push(n);
+  if (int rc = r->new_games(first, n, s)) return rc;
   // one synchronisation: the n lengths (the ring may wrap) and the error word
   std::vector<int> len(n);
   int err = 0;
@@ -354,7 +512,7 @@ int mzgo_replay_play_games(mzgo_replay* r, mzgo_engine* eng, int n_games, int fi
   RHIPCHK(hipStreamSynchronize(s));
   for (int j = 0; j < n; ++j) {
     const int slot = (first + j) % cap;
-    r->len[slot] = len[j];
+    r->set_len(slot, len[j]);
     r->gid[slot] = (int)game_key_id(E.game_base, j % E.G, first_epoch + j / E.G);
   }
   if (err < n)
@@ -390,8 +548,9 @@ int mzgo_replay_add(mzgo_replay* r, int length, const int8_t* stones_host, const
   }
   RHIPCHK(hipMemcpyAsync(R.length + slot, &length, 4, hipMemcpyHostToDevice, s));
   RHIPCHK(hipMemcpyAsync(R.key_gid + slot, &key_gid, 4, hipMemcpyHostToDevice, s));
+  if (int rc = r->new_games(slot, 1, s)) return rc;
   RHIPCHK(hipStreamSynchronize(s));                         // (the host buffers are the caller's)
-  r->len[slot] = length;
+  r->set_len(slot, length);
   r->gid[slot] = key_gid;
   return MZGO_OK;
 }
@@ -528,6 +687,189 @@ int mzgo_replay_reanalyse(mzgo_replay* r, mzgo_engine* eng, const int32_t* games
   if (int rc = mzgo_reanalyse(eng, st, iv, fl, ids, nullptr, (int)n, visits, value, policy, stream)) return rc;
   hipLaunchKernelGGL(k_replay_scatter, dim3((unsigned)n), dim3(64), 0, s, r->R, r->d_items, policy, value);
   RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+// the sampler's checks and its two launches (``who``: the entry point's name)
+static int sample_launch(mzgo_replay* r, const char* who, int B, uint64_t seed, uint32_t step, int symmetries,
+                         double beta, int32_t* items, int32_t* index, uint32_t* gen, float* weight, hipStream_t s) {
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
+  if (r->R.cap > kSampleMaxCap)
+    return set_error(MZGO_EINVAL, "%s: capacity %d exceeds the sampler's 64^3 = %d slots", who, r->R.cap,
+                     kSampleMaxCap);
+  if (B > r->n_valid)
+    return set_error(MZGO_EINVAL, "%s: B %d exceeds the %d stored games that have moves", who, B, r->n_valid);
+  if (!(beta >= 0.0) || std::isinf(beta)) return set_error(MZGO_EINVAL, "%s: beta must be finite and >= 0", who);
+  if (!items || !index || !gen)
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !items ? "items" : !index ? "index" : "gen");
+  const Ledger& L = r->L;
+  hipLaunchKernelGGL(k_replay_sample_build, dim3((L.n1 + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads), 0, s,
+                     L, r->R.length);
+  RHIPCHK(hipGetLastError());
+  const SampleOut O{items, index, gen, weight};
+  hipLaunchKernelGGL(k_replay_sample_draw, dim3(1), dim3(64), 0, s, L, r->R.length, r->head, B,
+                     stream_key(seed, kSamplerDomain, step), symmetries != 0, beta, r->n_valid, O);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+int mzgo_replay_sample(mzgo_replay* r, int B, uint64_t seed, uint32_t step, int symmetries, double beta,
+                       int32_t* items, int32_t* index, uint32_t* gen, float* weight, void* stream) {
+  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_sample: null replay");
+  return sample_launch(r, "mzgo_replay_sample", B, seed, step, symmetries, beta, items, index, gen, weight,
+                       (hipStream_t)stream);
+}
+
+int mzgo_replay_sample_batch(mzgo_replay* r, int B, int unroll_steps, double discount, uint64_t seed, uint32_t step,
+                             int symmetries, double beta, int32_t* items, int32_t* index, uint32_t* gen,
+                             float* weight, float* obs0, float* boot_obs, int64_t* acts, float* t_rew, float* t_pol,
+                             double* val, double* factor, uint8_t* has_boot, void* stream) {
+  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_sample_batch: null replay");
+  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "mzgo_replay_sample_batch: unroll_steps %d out of range (1..%d)", unroll_steps,
+                     kMaxUnroll);
+  if (!obs0 || !boot_obs || !acts || !t_rew || !t_pol || !val || !factor || !has_boot)
+    return set_error(MZGO_EINVAL, "mzgo_replay_sample_batch: null %s",
+                     !obs0 ? "obs0" : !boot_obs ? "boot_obs" : !acts ? "acts" : !t_rew ? "t_rew" : !t_pol ? "t_pol"
+                     : !val ? "val" : !factor ? "factor" : "has_boot");
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = sample_launch(r, "mzgo_replay_sample_batch", B, seed, step, symmetries, beta, items, index, gen,
+                             weight, s))
+    return rc;
+  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot};
+  hipLaunchKernelGGL(k_replay_batch, dim3(B), dim3(kThreads), 0, s, r->R, items, unroll_steps, discount, O);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+int mzgo_replay_sample_host(const double* prio, const int32_t* length, int cap, int head, int B, uint64_t seed,
+                            uint32_t step, int symmetries, double beta, int32_t* items, int32_t* index,
+                            float* weight) {
+  const char* who = "mzgo_replay_sample_host";
+  if (cap < 1 || cap > kSampleMaxCap)
+    return set_error(MZGO_EINVAL, "%s: capacity %d outside 1..64^3 = %d", who, cap, kSampleMaxCap);
+  if (!prio || !length || !items || !index)
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !prio ? "prio" : !length ? "length" : !items ? "items" : "index");
+  if (head < 0 || head >= cap) return set_error(MZGO_EINVAL, "%s: head %d outside 0..%d", who, head, cap - 1);
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
+  if (!(beta >= 0.0) || std::isinf(beta)) return set_error(MZGO_EINVAL, "%s: beta must be finite and >= 0", who);
+  int n_valid = 0;
+  std::vector<double> leaf((size_t)cap);
+  for (int i = 0; i < cap; ++i) {
+    leaf[i] = length[i] > 0 ? prio[i] : 0.0;
+    if (length[i] > 0 && !(prio[i] > 0.0 && !std::isinf(prio[i])))
+      return set_error(MZGO_EINVAL, "%s: slot %d: weight %g (finite and > 0)", who, i, prio[i]);
+    n_valid += length[i] > 0;
+  }
+  if (B > n_valid) return set_error(MZGO_EINVAL, "%s: B %d exceeds the %d stored games that have moves", who, B, n_valid);
+  // k_replay_sample_build and the draw kernel's prologue
+  const int n1 = (cap + 63) / 64, n2 = (n1 + 63) / 64;
+  std::vector<double> l1((size_t)n2 * 64, 0.0);
+  double x2[64] = {0.0}, p[64];
+  for (int g = 0; g < n1; ++g) {
+    scan64_host(leaf.data() + (size_t)g * 64, std::min(64, cap - g * 64), p);
+    l1[g] = p[63];
+  }
+  for (int g = 0; g < n2; ++g) {
+    scan64_host(l1.data() + (size_t)g * 64, 64, p);
+    x2[g] = p[63];
+  }
+  const uint64_t key = stream_key(seed, kSamplerDomain, step);
+  std::vector<double> pick_w((size_t)B);
+  double total0 = 0.0;
+  for (int t = 0; t < B; ++t) {
+    scan64_host(x2, 64, p);
+    const double total = p[63];
+    if (t == 0) total0 = total;
+    double target = sample_u(key, t) * total;
+    const int j2 = pick64_host(x2, 64, &target);
+    const int j1 = pick64_host(l1.data() + (size_t)j2 * 64, 64, &target);
+    const int g1 = j2 * 64 + j1;
+    const int n0 = std::max(0, std::min(64, cap - g1 * 64));
+    const int j0 = pick64_host(leaf.data() + (size_t)g1 * 64, n0, &target);
+    const int slot = std::min(g1 * 64 + j0, cap - 1);
+    pick_w[t] = leaf[slot];
+    leaf[slot] = 0.0;
+    scan64_host(leaf.data() + (size_t)g1 * 64, n0, p);
+    l1[g1] = p[63];
+    scan64_host(l1.data() + (size_t)j2 * 64, 64, p);
+    x2[j2] = p[63];
+    items[3 * t] = slot;
+    items[3 * t + 1] = sample_start(key, t, length[slot]);
+    items[3 * t + 2] = sample_symmetry(key, t, symmetries != 0);
+    index[t] = (slot - head + cap) % cap;
+  }
+  if (weight) {
+    double vmax = 0.0;
+    for (int b = 0; b < B; ++b) vmax = std::max(vmax, std::pow((double)n_valid * pick_w[b] / total0, -beta));
+    for (int b = 0; b < B; ++b) weight[b] = (float)(std::pow((double)n_valid * pick_w[b] / total0, -beta) / vmax);
+  }
+  return MZGO_OK;
+}
+
+int mzgo_replay_update_priorities(mzgo_replay* r, const int32_t* items, const uint32_t* gen, const float* per,
+                                  const double* mean, int B, double alpha, void* stream) {
+  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_update_priorities: null replay");
+  if (B < 1) return set_error(MZGO_EINVAL, "mzgo_replay_update_priorities: B must be >= 1, got %d", B);
+  if (!items || !gen)
+    return set_error(MZGO_EINVAL, "mzgo_replay_update_priorities: null %s", !items ? "items" : "gen");
+  if ((per != nullptr) == (mean != nullptr))
+    return set_error(MZGO_EINVAL, "mzgo_replay_update_priorities: give per (a loss per sample) or mean (one value), "
+                     "not %s", per ? "both" : "neither");
+  if (!(alpha > 0.0) || std::isinf(alpha))
+    return set_error(MZGO_EINVAL, "mzgo_replay_update_priorities: alpha must be finite and > 0");
+  hipLaunchKernelGGL(k_replay_update_priorities, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0,
+                     (hipStream_t)stream, r->L, items, gen, per, mean, B, alpha);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+// logical order = the ring from ``head``: at most two runs of slots
+// (entries of ``width`` bytes)
+static int copy_logical(mzgo_replay* r, void* logical, void* slots, size_t width, bool to_slots, hipMemcpyKind kind,
+                        hipStream_t s) {
+  const int run = std::min(r->size, r->R.cap - r->head);
+  const int n[2] = {run, r->size - run}, at[2] = {r->head, 0};
+  for (int k = 0, done = 0; k < 2; done += n[k], ++k) {
+    if (n[k] == 0) continue;
+    char *a = (char*)logical + (size_t)done * width, *b = (char*)slots + (size_t)at[k] * width;
+    RHIPCHK(hipMemcpyAsync(to_slots ? b : a, to_slots ? a : b, (size_t)n[k] * width, kind, s));
+  }
+  return MZGO_OK;
+}
+
+int mzgo_replay_priorities(mzgo_replay* r, double* prio, uint32_t* gen, void* stream) {
+  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_priorities: null replay");
+  hipStream_t s = (hipStream_t)stream;
+  if (prio)
+    if (int rc = copy_logical(r, prio, r->L.prio, sizeof(double), false, hipMemcpyDeviceToDevice, s)) return rc;
+  if (gen)
+    if (int rc = copy_logical(r, gen, r->L.gen, sizeof(uint32_t), false, hipMemcpyDeviceToDevice, s)) return rc;
+  return MZGO_OK;
+}
+
+int mzgo_replay_set_priorities(mzgo_replay* r, const double* values_host, int n, void* stream) {
+  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_set_priorities: null replay");
+  if (!values_host) return set_error(MZGO_EINVAL, "mzgo_replay_set_priorities: null values");
+  if (n != r->size)
+    return set_error(MZGO_EINVAL, "mzgo_replay_set_priorities: %d values for the %d games held", n, r->size);
+  for (int i = 0; i < n; ++i)
+    if (!(values_host[i] > 0.0) || std::isinf(values_host[i]))
+      return set_error(MZGO_EINVAL, "mzgo_replay_set_priorities: game %d: %g (finite values > 0 only)", i,
+                       values_host[i]);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = copy_logical(r, const_cast<double*>(values_host), r->L.prio, sizeof(double), true, hipMemcpyHostToDevice, s)) return rc;
+  RHIPCHK(hipStreamSynchronize(s));                         // (the host buffer is the caller's)
+  return MZGO_OK;
+}
+
+int mzgo_replay_skipped_updates(mzgo_replay* r, int64_t* count_host, void* stream) {
+  if (!r || !count_host)
+    return set_error(MZGO_EINVAL, "mzgo_replay_skipped_updates: null %s", !r ? "replay" : "count");
+  unsigned c = 0;
+  RHIPCHK(hipMemcpyAsync(&c, r->L.skipped, sizeof(c), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  RHIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  *count_host = c;
   return MZGO_OK;
 }
 

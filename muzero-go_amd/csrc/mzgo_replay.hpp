@@ -2,13 +2,18 @@
 // with the rest of the library: the eight board symmetries as index maps
 // (host and device, so that the tables a test reads are the kernel's), and the
 // ring's arrays and the ingest of one game (a device function: the store's
-// own ingest kernel and k_selfplay_games run the same text), and the engine's
+// own ingest kernel and k_selfplay_games run the same text), the device
+// priority ledger and the sampler's order of additions, descent rule and
+// fallback (host and device: the sampler's host twin runs them), and the engine's
 // side of the store's engine-facing calls (mzgo_capi.hip owns struct
 // mzgo_engine and the thread-local error string).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
+
+#include "mzgo_common.hpp"
 
 struct mzgo_engine;
 
@@ -129,6 +134,82 @@ struct GamesArgs {
   int* error;        // the smallest j whose game stopped on a board error (>= n before the launch)
   Store R;
 };
+
+// ---------------------------------------------------------------------------
+// The device priority ledger and its sampler (mzgo_replay.hip: k_replay_sample_*,
+// k_replay_update_priorities; mzgo.h: mzgo_replay_sample).  Kept apart from
+// Store, which the ingest and self-play kernels take by value.
+// ---------------------------------------------------------------------------
+struct Ledger {
+  int cap, n1;         // slots; level-1 entries = ceil(cap / 64)
+  double* prio;        // [cap]  the sampling weight (already raised to alpha); 1.0 for a new game
+  uint32_t* gen;       // [cap]  + 1 whenever a game is written into the slot
+  double* leaf;        // [cap]  sampler scratch: length > 0 ? prio : 0, picked leaves zeroed
+  double* l1;          // [n1]   sampler scratch: the sums of 64 leaves
+  double* pick_w;      // [cap]  sampler scratch: the picked games' weights, in draw order
+  unsigned* skipped;   // [1]    priority updates refused (a loss that is not finite or < 0)
+};
+
+constexpr uint32_t kSamplerDomain = 0x53414D50u;   // stream_key's "game" word of the sampler's draws
+constexpr int kSampleMaxCap = 64 * 64 * 64;        // three levels of 64
+enum : uint32_t { TAG_SAMPLE = 5, TAG_START = 6, TAG_SYM = 7 };
+
+// The sampler adds 64 entries x[0..63] (past the array's end: 0) in ONE order,
+// the inclusive scan p of six steps d = 1, 2, 4, 8, 16, 32:
+//   p[i] <- (i >= d ? p[i - d] : 0) + p[i]      for all i at once, from p = x
+// (a wave does a step with one lane shift; the host twin with a copy).  The
+// sum of the 64 is p[63].  Only + on doubles: the same bits everywhere.
+__host__ __device__ __forceinline__ double scan_step(int i, int d, double own, double below) {
+  return i >= d ? below + own : own;
+}
+// The descent rule at one level, from two 64-bit masks over the entries:
+// ``over`` = entry is non-zero and its inclusive prefix exceeds the target,
+// ``nonzero`` = entry is non-zero.  The first ``over`` entry; if rounding left
+// none, the last non-zero one; 0 for an all-zero group (which the callers
+// exclude: no more draws than games with a weight).
+__host__ __device__ __forceinline__ int pick_entry(uint64_t over, uint64_t nonzero) {
+  if (over) return __builtin_ctzll(over);
+  if (nonzero) return 63 - __builtin_clzll(nonzero);
+  return 0;
+}
+// the draws of sample t under ``key`` = stream_key(seed, kSamplerDomain, step)
+__host__ __device__ __forceinline__ double sample_u(uint64_t key, int t) { return u01(draw(key, TAG_SAMPLE, (uint64_t)t)); }
+__host__ __device__ __forceinline__ int sample_start(uint64_t key, int t, int length) {
+  return (int)randbelow(draw(key, TAG_START, (uint64_t)t), (uint32_t)length);
+}
+__host__ __device__ __forceinline__ int sample_symmetry(uint64_t key, int t, int symmetries) {
+  return symmetries ? (int)randbelow(draw(key, TAG_SYM, (uint64_t)t), 8u) : 0;
+}
+// the stored priority of a loss ``p`` (finite, >= 0): floored at float32's
+// smallest normal, then raised to alpha (exactly the floored value at alpha 1)
+__host__ __device__ __forceinline__ double priority_of(double p, double alpha) {
+  const double v = p > 1.17549435082228750797e-38 ? p : 1.17549435082228750797e-38;
+  return alpha == 1.0 ? v : pow(v, alpha);
+}
+
+// host serial forms of the scan and of one level's pick (the twin's)
+inline void scan64_host(const double* x, int n, double* p) {
+  double a[64], b[64];
+  for (int i = 0; i < 64; ++i) a[i] = i < n ? x[i] : 0.0;
+  for (int d = 1; d < 64; d <<= 1) {
+    for (int i = 0; i < 64; ++i) b[i] = scan_step(i, d, a[i], i >= d ? a[i - d] : 0.0);
+    for (int i = 0; i < 64; ++i) a[i] = b[i];
+  }
+  for (int i = 0; i < 64; ++i) p[i] = a[i];
+}
+// picks among x[0..n) for *target; on return *target is the remainder for the level below
+inline int pick64_host(const double* x, int n, double* target) {
+  double p[64];
+  scan64_host(x, n, p);
+  uint64_t over = 0, nonzero = 0;
+  for (int i = 0; i < n && i < 64; ++i) {
+    if (x[i] > 0.0) nonzero |= 1ull << i;
+    if (x[i] > 0.0 && p[i] > *target) over |= 1ull << i;
+  }
+  const int j = pick_entry(over, nonzero);
+  *target = *target - (j > 0 ? p[j - 1] : 0.0);
+  return j;
+}
 
 // mzgo_capi.hip: fill *v from an engine (no checks beyond the null pointer)
 void replay_engine_view(const mzgo_engine* eng, ReplayEngineView* v);

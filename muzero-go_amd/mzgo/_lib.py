@@ -98,6 +98,15 @@ SIGNATURES = {
     "mzgo_replay_finish_values": (_I, [_P, _P, _P, _P, _I, _P, _P]),
     "mzgo_replay_reanalyse": (_I, [_P, _P, _P, _I, _P]),
     "mzgo_replay_symmetry_table": (_I, [_I, _I, _P, _P]),
+    "mzgo_replay_sample": (_I, [_P, _I, ctypes.c_uint64, ctypes.c_uint32, _I, ctypes.c_double, _P, _P, _P, _P, _P]),
+    "mzgo_replay_sample_batch": (_I, [_P, _I, _I, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _I,
+                                      ctypes.c_double] + [_P] * 13),
+    "mzgo_replay_sample_host": (_I, [_P, _P, _I, _I, _I, ctypes.c_uint64, ctypes.c_uint32, _I, ctypes.c_double, _P, _P,
+                                     _P]),
+    "mzgo_replay_update_priorities": (_I, [_P, _P, _P, _P, _P, _I, ctypes.c_double, _P]),
+    "mzgo_replay_priorities": (_I, [_P, _P, _P, _P]),
+    "mzgo_replay_set_priorities": (_I, [_P, _P, _I, _P]),
+    "mzgo_replay_skipped_updates": (_I, [_P, _P, _P]),
     "mzgo_unroll_loss": (_I, [_P] * 6 + [_I] * 3 + [ctypes.c_float] * 3 + [_I] + [_P] * 6),
     "mzgo_unroll_loss_host": (_I, [_P] * 6 + [_I] * 3 + [ctypes.c_float] * 3 + [_I] + [_P] * 5),
 }

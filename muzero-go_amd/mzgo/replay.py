@@ -23,6 +23,14 @@ on the host (``ReplayLedger``), and sampling is main.py's --
 ``sample_indices`` draws exactly what ``PrioritizedReplayBuffer.sample`` draws
 from the same ``np.random`` state.  One store equals
 ``MultiVersionReplayBuffer(num_versions=1)``.
+
+Opt-in, the store also keeps a second, device-resident ledger -- a weight and
+a generation per slot -- with a sampler on the GPU (``sample_batch``,
+``update_device_priorities``, ``device_priorities``,
+``set_device_priorities``; ``TrainConfig.device_sampling``): successive
+sampling without replacement from a 64-ary sum tree, with a priority exponent
+and importance weights, nothing on the host but the count of games.  The two
+ledgers are independent: neither reads or writes the other.
 """
 import ctypes
 
@@ -105,6 +113,27 @@ def finish_values(val, factor, has_boot, value):
     check(lib.mzgo_replay_finish_values(ptr(val), ptr(factor), ptr(has_boot), ptr(value), n, ptr(t_val),
                                         stream_of(val.device)))
     return t_val
+
+
+def sample_host(prio, length, head, batch_size, *, seed, step, symmetries=False, beta=0.0):
+    """The device sampler's host twin (mzgo_replay_sample_host: the kernels'
+    own scan, descent and fallback functions run serially; no GPU).  ``prio``
+    f64 and ``length`` i32 are per ring SLOT (``len(prio)`` = the capacity),
+    ``head`` is the slot of logical game 0.  Returns a dict of numpy arrays:
+    ``items`` i32 [B,3] (slot, start, symmetry), ``index`` i32 [B] and
+    ``weight`` f32 [B]."""
+    prio = np.ascontiguousarray(np.asarray(prio, dtype=np.float64).reshape(-1))
+    length = np.ascontiguousarray(np.asarray(length, dtype=np.int32).reshape(-1))
+    if len(prio) != len(length):
+        raise ValueError("sample_host: prio and length have one entry per slot")
+    B = int(batch_size)
+    items = np.empty((max(B, 0), 3), np.int32)
+    index = np.empty(max(B, 0), np.int32)
+    weight = np.empty(max(B, 0), np.float32)
+    check(lib.mzgo_replay_sample_host(ptr(prio), ptr(length), len(prio), int(head), B, int(seed) & (2 ** 64 - 1),
+                                      int(step) & 0xFFFFFFFF, int(bool(symmetries)), float(beta), ptr(items),
+                                      ptr(index), ptr(weight)))
+    return dict(items=items, index=index, weight=weight)
 
 
 class DeviceReplay:
@@ -276,6 +305,121 @@ class DeviceReplay:
                                     ptr(out["boot_obs"]), ptr(out["acts"]), ptr(out["t_rew"]), ptr(out["t_pol"]),
                                     ptr(out["val"]), ptr(out["factor"]), ptr(out["has_boot"]), stream_of(dev)))
         return out
+
+    # ---- the device ledger and sampler ----
+    # Independent of ``ledger`` above: the host ledger (``priorities``,
+    # ``sample_indices``, ``update_priorities``) is main.py's np.random path and
+    # never reads or writes the device weights; the methods below never touch
+    # the host ledger.  A trainer uses one or the other (TrainConfig.device_sampling).
+    def _batch_out(self, B, K):
+        N, A, dev, K1 = self.N, self.A, self.device, max(K, 0) + 1
+        return dict(obs0=torch.empty(B, 6, N, N, device=dev),
+                    boot_obs=torch.empty(B, K1, 6, N, N, device=dev),
+                    acts=torch.empty(B, max(K, 0), dtype=torch.int64, device=dev),
+                    t_rew=torch.empty(B, max(K, 0), device=dev),
+                    t_pol=torch.empty(B, K1, A, device=dev),
+                    val=torch.empty(B, K1, dtype=torch.float64, device=dev),
+                    factor=torch.empty(B, K1, dtype=torch.float64, device=dev),
+                    has_boot=torch.empty(B, K1, dtype=torch.uint8, device=dev))
+
+    def _sample_out(self, B):
+        dev = self.device
+        return dict(items=torch.empty(max(B, 0), 3, dtype=torch.int32, device=dev),
+                    index=torch.empty(max(B, 0), dtype=torch.int32, device=dev),
+                    gen=torch.empty(max(B, 0), dtype=torch.int32, device=dev),      # (u32 bits)
+                    weight=torch.empty(max(B, 0), device=dev))
+
+    def sample(self, batch_size, *, seed, step, symmetries=False, beta=0.0):
+        """The sampler alone (mzgo_replay_sample, two launches, nothing on the
+        host): ``batch_size`` distinct games drawn by successive sampling
+        without replacement from the device weights.  Returns CUDA tensors
+        ``items`` i32 [B,3] (slot, start, symmetry), ``index`` i32 [B]
+        (logical, oldest = 0), ``gen`` i32 [B] (the slots' generations, u32
+        bits) and ``weight`` f32 [B] (importance weights, all 1 at beta 0)."""
+        B = int(batch_size)
+        s = self._sample_out(B)
+        check(lib.mzgo_replay_sample(self._h, B, int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, int(bool(symmetries)),
+                                     float(beta), ptr(s["items"]), ptr(s["index"]), ptr(s["gen"]), ptr(s["weight"]),
+                                     stream_of(self.device)))
+        return s
+
+    def sample_batch(self, batch_size, unroll_steps, discount, *, seed, step, symmetries=False, beta=0.0):
+        """``sample`` and ``batch`` in one call without the host
+        (mzgo_replay_sample_batch): ``batch``'s dict for the sampled (game,
+        start, symmetry) triples plus ``sample``'s ``items``, ``index``,
+        ``gen`` and ``weight``.  The draw depends on (seed, step) and the
+        device weights only; it is ``sample_host``'s, bit for bit."""
+        B, K = int(batch_size), int(unroll_steps)
+        out = self._batch_out(B, K)
+        out.update(self._sample_out(B))
+        check(lib.mzgo_replay_sample_batch(self._h, B, K, float(discount), int(seed) & (2 ** 64 - 1),
+                                           int(step) & 0xFFFFFFFF, int(bool(symmetries)), float(beta),
+                                           ptr(out["items"]), ptr(out["index"]), ptr(out["gen"]), ptr(out["weight"]),
+                                           ptr(out["obs0"]), ptr(out["boot_obs"]), ptr(out["acts"]), ptr(out["t_rew"]),
+                                           ptr(out["t_pol"]), ptr(out["val"]), ptr(out["factor"]), ptr(out["has_boot"]),
+                                           stream_of(self.device)))
+        return out
+
+    def update_device_priorities(self, sample, per=None, alpha=1.0, *, mean=None):
+        """New device weights for a sampled batch (``sample``: what ``sample``
+        or ``sample_batch`` returned): ``max(per[b], FLT_MIN) ** alpha`` for
+        sample b from ``per`` (a CUDA f32 tensor [B]), or from ``mean`` (a CUDA
+        f64 tensor of one element) the same value for all.  A slot that has
+        taken a newer game since the draw keeps that game's 1.0; a loss that
+        is NaN, infinite or negative leaves the weight alone and is counted
+        (``skipped_updates``).  No synchronisation."""
+        B = sample["items"].shape[0]
+        if (per is None) == (mean is None):
+            raise ValueError("update_device_priorities: give per or mean")
+        if per is not None:
+            per = per.detach().to(self.device, torch.float32).reshape(-1).contiguous()
+            if per.numel() != B:
+                raise ValueError(f"update_device_priorities: {per.numel()} losses for {B} samples")
+        else:
+            mean = mean.detach().to(self.device, torch.float64).reshape(-1).contiguous()
+            if mean.numel() != 1:
+                raise ValueError("update_device_priorities: mean is one value")
+        check(lib.mzgo_replay_update_priorities(self._h, ptr(sample["items"]), ptr(sample["gen"]), ptr(per), ptr(mean),
+                                                B, float(alpha), stream_of(self.device)))
+
+    def device_priorities(self):
+        """The device weights of the games held, f64 CUDA tensor in logical
+        order (oldest first)."""
+        out = torch.empty(len(self), dtype=torch.float64, device=self.device)
+        check(lib.mzgo_replay_priorities(self._h, ptr(out), None, stream_of(self.device)))
+        return out
+
+    def device_generations(self):
+        """The slots' generation counts of the games held (int64 CUDA tensor,
+        logical order): + 1 each time a game is written into the slot."""
+        out = torch.empty(len(self), dtype=torch.int32, device=self.device)
+        check(lib.mzgo_replay_priorities(self._h, None, ptr(out), stream_of(self.device)))
+        return out.long() & 0xFFFFFFFF
+
+    def set_device_priorities(self, values):
+        """Set the device weights of the games held (logical order; finite
+        values > 0 only)."""
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.float64).reshape(-1))
+        check(lib.mzgo_replay_set_priorities(self._h, ptr(v), len(v), stream_of(self.device)))
+
+    def skipped_updates(self):
+        """How many priority updates were refused so far (synchronises)."""
+        n = ctypes.c_int64()
+        check(lib.mzgo_replay_skipped_updates(self._h, ctypes.byref(n), stream_of(self.device)))
+        return n.value
+
+    def sample_host(self, batch_size, *, seed, step, symmetries=False, beta=0.0):
+        """The sampler's host twin on this store's present weights (copied
+        back) and lengths: numpy ``items``, ``index``, ``weight``."""
+        size, head = ctypes.c_int32(), ctypes.c_int32()
+        check(lib.mzgo_replay_info(self._h, ctypes.byref(size), ctypes.byref(head), None, None))
+        lengths, _ = self._info()
+        slots = (head.value + np.arange(size.value)) % self.capacity
+        prio, length = np.zeros(self.capacity), np.zeros(self.capacity, np.int32)
+        prio[slots] = self.device_priorities().cpu().numpy()
+        length[slots] = lengths
+        return sample_host(prio, length, head.value, batch_size, seed=seed, step=step, symmetries=symmetries,
+                           beta=beta)
 
     # ---- reanalysis in place ----
     def reanalyse(self, reanalyser, games=None):

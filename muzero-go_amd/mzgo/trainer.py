@@ -43,6 +43,13 @@ on the device, every game of a batch at once) and trains on it:
   priority is its own loss (floored at float32's smallest normal) instead of
   main.py's batch mean, so the store tells sampled games apart; in batched
   mode the per-sample losses ride in the step's one synchronising copy.
+  ``TrainConfig.device_sampling`` (default off; batched mode on a
+  ``DeviceReplay`` only) moves the sampling and the priorities onto the
+  store's device ledger: ``sample_batch`` draws the games, starts and
+  symmetries and assembles the targets without the host, the priority update
+  is a launch, and only the totals come back -- on demand (``read_stats``)
+  with ``deferred_stats``.  ``importance_beta`` weights the loss by the
+  sampler's importance weights, ``priority_alpha`` is the priority exponent.
 
 ``initial_inference_torch`` / ``recurrent_inference_torch`` restate
 main.py:72-144 with torch ops on the module's own parameters (reference
@@ -78,6 +85,10 @@ class TrainConfig:
     symmetries: bool = False          # DeviceReplay batches: a random board symmetry per sample (not in main.py)
     fused_loss: bool = False          # batched mode: the unroll's loss and head gradients on mzgo_unroll_loss
     sample_priorities: bool = False   # a sampled game's priority = its own loss (main.py: the batch mean)
+    device_sampling: bool = False     # DeviceReplay: sample and update priorities on the device (its own ledger)
+    importance_beta: float = 0.0      # device_sampling: importance-weight exponent (0 = unweighted loss)
+    priority_alpha: float = 1.0       # device_sampling: a new priority is loss ** alpha
+    deferred_stats: bool = False      # device_sampling: train() returns a device scalar; read_stats() fills last
 
 
 def reward_value_transform(x, epsilon=0.001):
@@ -410,7 +421,7 @@ class MuZeroTrainer:
     ``random.randint(0, T - 1)``; tests pass a fixed sequence)."""
 
     def __init__(self, net: MuZeroNet, config: TrainConfig = None, mode="reference", start_index=None,
-                 hip_forward=None):
+                 hip_forward=None, sample_seed=0):
         if mode not in ("reference", "batched"):
             raise ValueError(f"mode must be 'reference' or 'batched', not {mode!r}")
         self.net = net
@@ -425,7 +436,20 @@ class MuZeroTrainer:
         if self.config.fused_loss and mode != "batched":
             raise ValueError("fused_loss needs mode='batched': mode='reference' is main.py's per-trajectory step, "
                              "whose loss is built and backpropagated one trajectory at a time")
+        c = self.config
+        if c.device_sampling and mode != "batched":
+            raise ValueError("device_sampling needs mode='batched' and a DeviceReplay: mode='reference' is main.py's "
+                             "per-trajectory step over host trajectories")
+        if not c.device_sampling and (c.deferred_stats or c.importance_beta != 0.0 or c.priority_alpha != 1.0):
+            raise ValueError("deferred_stats, importance_beta and priority_alpha belong to device_sampling "
+                             "(TrainConfig.device_sampling=True)")
+        if c.importance_beta < 0 or not c.priority_alpha > 0:
+            raise ValueError("importance_beta must be >= 0 and priority_alpha > 0")
         self.mode = mode
+        self.sample_seed = int(sample_seed)   # device_sampling: the sampler's seed; its step is sample_step
+        self.sample_step = 0                  # steps taken with device_sampling
+        self._pending = None                  # device_sampling: the last step's totals, still on the device
+        self.last_per_sample_device = None    # device_sampling + sample_priorities: the per-sample losses (CUDA)
         self.action_size = net.board_size ** 2 + 1
         self.optimizer = torch.optim.Adam(net.parameters(), lr=self.config.learning_rate)
         self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=self.config.lr_step_size,
@@ -481,6 +505,8 @@ class MuZeroTrainer:
         from .replay import DeviceReplay
         if isinstance(replay_buffer, DeviceReplay):
             return self._train_device(replay_buffer, batch_size)
+        if self.config.device_sampling:
+            raise ValueError("device_sampling needs a DeviceReplay: a host buffer has no device ledger to sample")
         batch, indices = replay_buffer.sample(batch_size)
         if not batch or len(batch) < batch_size:
             return None
@@ -554,6 +580,8 @@ class MuZeroTrainer:
                              "per-trajectory step over host trajectories (use PrioritizedReplayBuffer)")
         if len(replay) < batch_size:
             return None
+        if self.config.device_sampling:
+            return self._train_device_sampled(replay, batch_size)
         indices = replay.sample_indices(batch_size)
         starts = [self.start_index(replay.lengths[i]) for i in indices]
         syms = [self.symmetry_index() for _ in indices] if self.config.symmetries else None
@@ -561,6 +589,53 @@ class MuZeroTrainer:
         replay.update_priorities(indices, self._priorities(avg, len(indices)))
         self.scheduler.step()
         return avg
+
+    def _train_device_sampled(self, replay, batch_size):
+        """``_train_device`` with the store's device ledger: the sample, the
+        targets, the step and the priority update are queued on the stream
+        without the host seeing an index or a loss; the one copy of the totals
+        is the step's only synchronisation (none with ``deferred_stats``)."""
+        from .replay import finish_values
+        c, N = self.config, self.net.board_size
+        s = replay.sample_batch(batch_size, c.unroll_steps, c.discount, seed=self.sample_seed, step=self.sample_step,
+                                symmetries=c.symmetries, beta=c.importance_beta)
+        self.sample_step += 1
+        with torch.no_grad():
+            _, v, _ = self.net.initial_inference(s["boot_obs"].view(-1, 6, N, N))
+        t_val = finish_values(s["val"], s["factor"], s["has_boot"], v)
+        avg = self._unroll_step(s["obs0"], s["acts"], t_val, s["t_rew"], s["t_pol"], device_totals=True,
+                                device_sample=(replay, s))
+        self.scheduler.step()
+        return avg
+
+    def _finish_device(self, device_sample, per, totals, B):
+        """The tail of a device-sampled step: the priorities from ``per`` (f32
+        [B], unweighted) or the batch mean, and the totals (f64 [4], unweighted)
+        left on the device for ``read_stats``."""
+        replay, sample = device_sample
+        c = self.config
+        if c.sample_priorities:
+            replay.update_device_priorities(sample, per, c.priority_alpha)
+        else:
+            replay.update_device_priorities(sample, alpha=c.priority_alpha, mean=totals[:1] / B)
+        self.last_per_sample = None
+        self.last_per_sample_device = per if c.sample_priorities else None
+        self._pending = (totals, B, self.optimizer.param_groups[0]["lr"])
+        if c.deferred_stats:
+            self.last = {}
+            return totals[0] / B
+        return self.read_stats()["training_loss"]
+
+    def read_stats(self):
+        """``last`` of the latest step; with ``deferred_stats`` this is where the
+        totals are copied from the device (one synchronising copy)."""
+        if self._pending is not None:
+            totals, B, lr = self._pending
+            self._pending = None
+            total, tot_v, tot_p, tot_r = totals.tolist()
+            self.last = dict(training_loss=total / B, value_loss=tot_v / B, policy_loss=tot_p / B,
+                             reward_loss=tot_r / B, lr=lr)
+        return self.last
 
     def device_targets(self, replay, indices, starts, symmetries=None):
         """``host_targets`` from a ``DeviceReplay``: one batch-assembly launch,
@@ -630,7 +705,7 @@ class MuZeroTrainer:
         obs0 = np.stack([np.asarray(tr["observations"][s]) for tr, s in zip(batch, starts)])
         return obs0, acts, t_val, t_rew, t_pol
 
-    def _unroll_step(self, obs0, acts, t_val, t_rew, t_pol, device_totals=False):
+    def _unroll_step(self, obs0, acts, t_val, t_rew, t_pol, device_totals=False, device_sample=None):
         """One optimizer step on the summed losses of B samples unrolled K
         steps, from targets on the device (obs0 f32 [B,6,N,N], acts i64 [B,K],
         t_val f32 [B,K+1], t_rew f32 [B,K], t_pol f32 [B,K+1,A]); returns the
@@ -640,11 +715,15 @@ class MuZeroTrainer:
         step's only synchronisation.  ``TrainConfig.fused_loss`` takes the
         loss, the totals and the heads' gradients from ``mzgo.unroll_loss``
         instead (``_unroll_step_fused``); ``sample_priorities`` keeps the
-        per-sample losses in ``last_per_sample`` (in that same copy)."""
+        per-sample losses in ``last_per_sample`` (in that same copy).  With
+        ``device_sample`` = (the store, what its ``sample_batch`` returned) the
+        losses and totals stay on the device (``_finish_device``) and the loss
+        is weighted by the sample's importance weights when
+        ``importance_beta`` > 0."""
         c, net = self.config, self.net
         B, K = acts.shape
         if c.fused_loss:
-            return self._unroll_step_fused(obs0, acts, t_val, t_rew, t_pol)
+            return self._unroll_step_fused(obs0, acts, t_val, t_rew, t_pol, device_sample)
         tot = (lambda x: x.detach().sum().double()) if device_totals else (lambda x: x.sum().item())
         self.optimizer.zero_grad()
         fwd0, fwd = ((initial_inference_hip, recurrent_inference_hip) if self.hip_forward
@@ -664,11 +743,14 @@ class MuZeroTrainer:
             tot_r += tot(r_l)
             tot_v += tot(v_l)
             tot_p += tot(p_l)
-        loss = per.sum()
+        loss = per.sum() if not self._weighted(device_sample) else (per * device_sample[1]["weight"]).sum()
         loss.backward()
         torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm=c.max_grad_norm)
         self.optimizer.step()
         self.last_per_sample = None
+        if device_sample is not None:
+            d = per.detach()
+            return self._finish_device(device_sample, d, torch.stack([d.sum().double(), tot_v, tot_p, tot_r]), B)
         if device_totals and c.sample_priorities:
             back = torch.cat([torch.stack([loss.detach().double(), tot_v, tot_p, tot_r]),
                               per.detach().double()]).tolist()
@@ -684,7 +766,12 @@ class MuZeroTrainer:
                          reward_loss=tot_r / B, lr=self.optimizer.param_groups[0]["lr"])
         return total / B
 
-    def _unroll_step_fused(self, obs0, acts, t_val, t_rew, t_pol):
+    def _weighted(self, device_sample):
+        """Whether the step's loss is the importance-weighted sum (the
+        priorities and the reported totals stay unweighted)."""
+        return device_sample is not None and self.config.importance_beta > 0
+
+    def _unroll_step_fused(self, obs0, acts, t_val, t_rew, t_pol, device_sample=None):
         """``_unroll_step`` with the loss on the HIP kernel: the K + 1 steps'
         head outputs are collected and stacked once, ``mzgo.unroll_loss`` gives
         ``per`` and the f64 totals in one call, and autograd enters the network
@@ -707,11 +794,13 @@ class MuZeroTrainer:
                                   t_pol, t_val, t_rew, value_loss_weight=c.value_loss_weight,
                                   policy_loss_weight=c.policy_loss_weight, reward_loss_weight=c.reward_loss_weight,
                                   value_transform=c.use_value_transform)
-        loss = per.sum()
+        loss = per.sum() if not self._weighted(device_sample) else (per * device_sample[1]["weight"]).sum()
         loss.backward()
         torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm=c.max_grad_norm)
         self.optimizer.step()
         self.last_per_sample = None
+        if device_sample is not None:
+            return self._finish_device(device_sample, per.detach(), totals, B)
         if c.sample_priorities:
             back = torch.cat([totals, per.detach().double()]).tolist()
             self.last_per_sample = np.asarray(back[4:], dtype=np.float32)
