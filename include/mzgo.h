@@ -230,6 +230,17 @@ int mzgo_selfplay_counters(mzgo_engine* eng, uint64_t* counters_host, void* stre
  * replay.  Trees and records do not depend on the cache.  Synchronises
  * ``stream``. */
 int mzgo_search_stats(mzgo_engine* eng, uint64_t* stats_host, void* stream);
+/* The same statistics and those added since, with the room the caller has:
+ * writes min(cap, n) values to stats_host, n = 5 today, and nothing past
+ * them.  [0..2] as mzgo_search_stats; [3], [4] arrival convs: first arrivals
+ * of a select at a lazily expanded node whose parent conv ran at once, the
+ * node's priors and the simulation's pick formed under it (9x9 LDS trees with
+ * self_play.py's search; MZGO_ARRIVAL_CONV=0 at engine creation keeps the
+ * select-then-conv order: both stay 0), split by where the conv and the
+ * policy sums read the parent's Y: [3] its LDS copy, [4] L2.  Trees, records
+ * and the other counters do not depend on the switch.  Synchronises
+ * ``stream``. */
+int mzgo_search_stats2(mzgo_engine* eng, uint64_t* stats_host, int cap, void* stream);
 
 /* Move-parallel epoch (no reference counterpart; the schedule, not the
  * protocol): a multi-move mzgo_selfplay_moves under compat "reference"

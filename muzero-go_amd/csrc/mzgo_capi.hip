@@ -244,6 +244,7 @@ struct mzgo_engine {
   int64_t bytes = 0;
   int epoch = 0;
   int value_cache = 0;          // the searches keep a cut batch's values (EngineArrays::cval allocated)
+  int arrival_conv = 1;         // the 9x9 LDS-tree searches run a new parent's conv at its select's arrival
   const double* noise = nullptr;
   double* noise_out = nullptr;  // test hook: roots' normalised Dirichlet samples [G][M][A]
   TowerHost* tower = nullptr;   // residual-tower network (mzgo_config.tower, BASELINE config 5)
@@ -373,6 +374,7 @@ struct mzgo_engine {
     const char* lz = getenv("MZGO_LAZY_ROWS");        // (=0: eager rows in self-play too, an A/B switch)
     sp.lazy_rows = lz && atoi(lz) == 0 ? 0 : 1;
     sp.value_cache = value_cache;
+    sp.arrival_conv = arrival_conv;
     return sp;
   }
 };
@@ -539,6 +541,12 @@ int mzgo_engine_create(const mzgo_config* cfg, mzgo_engine** out) {
     e->value_cache = !TW && !cfg->direct_dynamics && ks->value_cache_cap > 0 && e->S + 2 <= ks->value_cache_cap &&
                      !(vc && atoi(vc) == 0);
     if (e->value_cache) chk(e->alloc(&E.cval, TSL * n1 * A));
+    // the arrival conv of the 9x9 LDS-tree searches (sim_loop; MZGO_ARRIVAL_CONV=0: today's
+    // order of select and conv, an A/B switch; 1, the default, or more: the conv first.  The
+    // value 2 was the batch's picks under the conv as well, measured slower and taken out
+    // again, DESIGN §7: it means 1)
+    const char* ac = getenv("MZGO_ARRIVAL_CONV");
+    e->arrival_conv = !(ac && atoi(ac) <= 0);
     chk(e->alloc(&E.jobs, TSL * job_bytes(A)));
     chk(e->alloc(&E.mpq, 2 * (size_t)G + 1));
     chk(e->alloc(&E.rec_stones, G * M * CELLS));
@@ -1106,6 +1114,17 @@ int mzgo_search_stats(mzgo_engine* e, uint64_t* out, void* stream) {
   HIPCHK(hipMemcpyAsync(c, e->E.counters + 9, sizeof c, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   out[0] = c[0]; out[1] = c[1]; out[2] = c[2];
+  return MZGO_OK;
+}
+
+int mzgo_search_stats2(mzgo_engine* e, uint64_t* out, int cap, void* stream) {
+  if (!e || !out || cap < 0) return fail(MZGO_EINVAL, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  constexpr int n = kCounters - 9;
+  unsigned long long c[n] = {};
+  HIPCHK(hipMemcpyAsync(c, e->E.counters + 9, sizeof c, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  for (int i = 0; i < (cap < n ? cap : n); ++i) out[i] = c[i];
   return MZGO_OK;
 }
 

@@ -1059,6 +1059,27 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
   constexpr bool VCACHE = Acc::LDS && BATCH && decltype(sm.u.f)::CACHE;
   const bool vcache = VCACHE && factored && sp.value_cache != 0 && E.cval != nullptr && !shared_jobs<G>(sp);
   int nbcomp = 0, nbcache = 0, ncut = 0;              // batch children expanded / from the cache, batches cut
+  // The arrival conv (LDS trees with the LDS Y copy and the one-strip
+  // Winograd conv: 9x9; self_play.py's select).  A select that reaches a
+  // lazily expanded node X for the first time ends there: X gets its priors
+  // and the simulation picks one of its children, all unexpanded, so X's
+  // parent conv always follows (a settled node has an eligible child: pass is
+  // valid, and child_prior_regs falls back to the uniform row).  That conv
+  // needs the parent's Y and E[a_X] only, so it starts at once: X's policy
+  // sums are formed at its head, and wave 0 settles X and picks (the rest of
+  // the select, settle_arrival) between the MFMA groups of the GEMM's second
+  // K half, while its SIMD's other two waves keep the matrix core fed -- in
+  // place of sums, barrier, the resumed select on wave 0 with eleven waves
+  // idle, barrier, and only then the conv.  (The following batch's picks in
+  // the same place measured slower: DESIGN §7.)  The same operations on the same
+  // data: trees, records and counters are the sequential ones.  main.py's
+  // select (variant 1) can end at a settled node without an action, where no
+  // conv runs, and a tail conv job (sp.tail) is handed to helpers: both keep
+  // the resumed select.
+  constexpr bool ARRIVAL = Acc::LDS && BATCH && G::WINO && decltype(sm.u.f)::CACHE && Wino<G>::NSTRIP == 1;
+  const bool arrival = ARRIVAL && factored && sp.arrival_conv != 0 && sp.variant == 0 && !sp.tail &&
+                       !shared_jobs<G>(sp);
+  int narr_lds = 0, narr_l2 = 0;                      // arrival convs whose parent's Y came from LDS / from L2
   // the batch of every unexpanded child of `leaf` was cut at m of B: keep the
   // dropped children's values (a leaf whose values are stored already, or a
   // batch the search's end shortened, stores nothing).  All threads.
@@ -1105,7 +1126,9 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
     // the walk reached a lazily expanded node for the first time: its policy
     // sums from its parent's Y and E[a] by the whole workgroup, then wave 0
     // resumes the walk there (it settles the node's priors and goes on)
+    bool arrive = false;                                  // ... or, the arrival conv: under X's parent conv
     while (sm.t.action == kNeedLogits) {
+      if (arrival) { arrive = true; break; }
       const int xn = sm.t.leaf, xd = sm.t.depth;
       st.lap(0);
       // the parent is nearly always the last batch's leaf, whose Y and head
@@ -1131,8 +1154,11 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
       st.lap(33);
     }
     st.lap(0);
-    const int a = sm.t.action, leaf = sm.t.leaf, depth = sm.t.depth;
-    if (a < 0) {                                         // terminal leaf: backup 0 (:188-191)
+    // (arrival conv: leaf = X and its depth; the action and the leaf's
+    // unexpanded children are known once wave 0 has picked, under the conv)
+    int a = sm.t.action;
+    const int leaf = sm.t.leaf, depth = sm.t.depth;
+    if (a < 0 && !arrive) {                              // terminal leaf: backup 0 (:188-191)
       // self_play.py: terminal leaf -> backup 0 (:188-191); main.py: nothing (:296)
       if (wave_id() == 0 && a == -1) backup<G>(T, depth, -1, 0.0);
       __syncthreads();
@@ -1150,7 +1176,7 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
       static_assert(!decltype(sm.u.f)::CACHE || 3 * G::C <= G::THREADS, "one head weight per thread");
       float hwpre = 0.f;                                 // this thread's head weight, fetched before the conv
       bool hwready = false;
-      if (!sm.t.yready) {
+      if (arrive || !sm.t.yready) {
         const bool sj = shared_jobs<G>(sp);
         // Winograd boards rebuild the latent inside the conv's input
         // transform (wino_input_rebuilt); the others materialize it first
@@ -1195,6 +1221,35 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
           if (tail) {
             conv_tail<G>(sm, np, E, g, leaf, par, nact[leaf], sp.net, y_lds_target<G>(sm),
                          y_lds_target<G>(sm) != nullptr && yc == par, &st);
+          } else if constexpr (ARRIVAL) {
+            const float* ypar = pool + (size_t)par * node_floats;
+            const float* ea = np.etab + (size_t)nact[leaf] * 9 * G::C;
+            latent_conv_rebuilt<G>(
+                sm, np, ypar, ea, yleaf, &st, y_lds_target<G>(sm), yc == par,
+                // the arrival conv: X's policy sums from its parent's Y, the LDS
+                // copy (before the transform overwrites it) or L2 -- a uniform
+                // branch, each side's loads keep their address space
+                [&]() {
+                  if (arrive) {
+                    if (yc == par) policy_sums_wg<G>(sm.t.logits, sm.u.f.yc, ea, sm.u.f.hw);
+                    else policy_sums_wg<G>(sm.t.logits, ypar, ea, np.head_w);
+                  }
+                },
+                // ... and the rest of the select on wave 0, under the second K half
+                [&]() {
+                  if (arrive && __builtin_amdgcn_readfirstlane(wave_id()) == 0) {
+                    const unsigned long long t_a = st.now();
+                    if (lane_id_local() == 0) sm.t.lognode = leaf;
+                    const int ax = settle_arrival<G>(sm.t, T, sp, key, sim, nullptr, leaf, depth);
+                    if (lane_id_local() == 0) sm.t.action = ax;
+                    st.wave_add(49, st.now() - t_a);
+                    st.wave_add(50, 1);
+                  }
+                });
+            if (arrive) {
+              ++rows;
+              if (yc == par) ++narr_lds; else ++narr_l2;
+            }
           } else {
             latent_conv_rebuilt<G>(sm, np, pool + (size_t)par * node_floats, np.etab + (size_t)nact[leaf] * 9 * G::C,
                                    yleaf, &st, y_lds_target<G>(sm), y_lds_target<G>(sm) != nullptr && yc == par);
@@ -1206,6 +1261,9 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
         }
         __syncthreads();                                 // Y stores before the expansion reads them
         st.lap(82);
+        // (wave 0's pick at X: always an action, see above; published by the
+        // conv's barriers behind the GEMM, like t.nunexp and t.umask)
+        if (arrive) a = sm.t.action;
         // the conv overwrote the union; one-strip Winograd boards got the
         // leaf's Y into L.yc by the conv itself (only the head weights reload)
         if (!sj && G::WINO && y_lds_target<G>(sm) != nullptr) {
@@ -1426,6 +1484,8 @@ __device__ __forceinline__ void sim_loop(Smem<G>& sm, const NetParams& np, const
     if (nbcomp) atomicAdd(&E.counters[9], (unsigned long long)nbcomp);
     if (nbcache) atomicAdd(&E.counters[10], (unsigned long long)nbcache);
     if (ncut) atomicAdd(&E.counters[11], (unsigned long long)ncut);
+    if (narr_lds) atomicAdd(&E.counters[12], (unsigned long long)narr_lds);
+    if (narr_l2) atomicAdd(&E.counters[13], (unsigned long long)narr_l2);
   }
   __syncthreads();
 }

@@ -20,7 +20,7 @@
 
 namespace mzgo {
 
-constexpr int kCounters = 12;    // EngineArrays::counters
+constexpr int kCounters = 14;   // EngineArrays::counters
 
 // Per-slot device state of an engine (sizes fixed at engine creation).
 struct EngineArrays {
@@ -67,7 +67,9 @@ struct EngineArrays {
                                  //     mzgo_stream_wait_started gates (reported, then cleared),
                                  //     9: children of sim_loop's speculative batches expanded, 10: of such
                                  //     batches' children, taken from cval instead, 11: such batches cut short
-                                 //     by their replay (mzgo_search_stats)
+                                 //     by their replay (mzgo_search_stats), 12 / 13: arrival convs
+                                 //     (sim_loop) whose parent's Y came from its LDS copy / from L2
+                                 //     (mzgo_search_stats2)
   unsigned long long* stamps;    // [G][kStampPhases] phase cycles (MZGO_STAMPS builds only)
 };
 

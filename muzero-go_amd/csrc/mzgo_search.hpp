@@ -38,6 +38,9 @@ struct SearchParams {
   int value_cache;          // LDS trees: a cut batch's dropped children keep their backup values for the
                             // leaf's next batch (EngineArrays::cval); 0: every batch expands its children
                             // (MZGO_VALUE_CACHE=0, an A/B switch)
+  int arrival_conv;         // 9x9 LDS trees: a select's first arrival at a lazily expanded node runs the
+                            // node's parent conv first and forms its priors and pick under it (sim_loop);
+                            // 0: priors and pick first, then the conv (MZGO_ARRIVAL_CONV=0, an A/B switch)
 };
 
 // One game's tree (global memory).  Node 0 is the root; node ids grow by one
@@ -799,6 +802,72 @@ __device__ __forceinline__ int puct_pick(const double (&P)[G::AP], const int (&n
   return best_a;
 }
 
+// The rest of a select whose walk reached the lazily expanded node `node`
+// (LDS trees, t.is_raw(node)) at `depth` for the first time, its policy sums
+// in t.logits: the node's priors and rows (settle_lazy; the rows also into
+// the LDS copy), its lazy mark cleared, then the select's end there -- none
+// of its children is expanded, so the walk ends at it: the draw's pick among
+// its eligible children, or no action.  Wave 0.  select_leaf's tail, and
+// sim_loop's under the node's parent conv (SearchParams::arrival_conv): the
+// same operations in the same order from either.
+template <class G, class Acc>
+__device__ __forceinline__ int settle_arrival(TreeLds<G>& t, const Acc& T, const SearchParams& sp, uint64_t key,
+                                              int sim, Stamp* st, int node, int depth) {
+  const int lane = lane_id_local();
+  // t.fbuf / t.dbuf are wave 1's while it forms the newest node's priors
+  if (t.newest >= 0)
+    while (__hip_atomic_load(&t.newp_node, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != t.newest)
+      __builtin_amdgcn_s_sleep(1);
+  float q[G::AP];
+  if (st) st->lap(36);
+  settle_lazy<G>(t, T.T.prior + (size_t)node * G::A, T.T.child + (size_t)node * G::A, sp.variant, t.fbuf, t.dbuf, q);
+  if (lane == 0) atomicAnd(&t.rawp[node >> 5], ~(1u << (node & 31)));
+  if (st) { st->lap(49); st->wave_add(50, 1); }
+  double P[G::AP];
+#pragma unroll
+  for (int j = 0; j < G::AP; ++j) {
+    const int a = lane + 64 * j;
+    P[j] = a < G::A ? (double)q[j] : 0.0;
+    // the node is about to become a parent: its rows into the LDS copy
+    // where they are made (the HBM stores stay; see keep_rows below)
+    if constexpr (Acc::LDS)
+      if (a < G::A) { t.rowc_prior[a] = q[j]; t.rowc_child[a] = -1; }
+  }
+  if constexpr (Acc::LDS)
+    if (lane == 0) t.rowc_node = node;
+  // (select_leaf's eligibility test and pick, every child unexpanded)
+  uint64_t anypos = 0, unexp[G::AP];
+  int n_unexp = 0;
+#pragma unroll
+  for (int j = 0; j < G::AP; ++j) {
+    unexp[j] = __ballot(P[j] > 0.0);
+    anypos |= unexp[j];
+    n_unexp += __popcll(unexp[j]);
+  }
+  if (st) st->lap(36);
+  // no eligible child: a terminal node (main.py's select, variant 1: no action)
+  if (!anypos) { t.leaf = node; t.depth = depth; return sp.variant == 1 ? -2 : -1; }
+  uint32_t k = randbelow(draw(key, TAG_SELECT, (uint64_t)sim), (uint32_t)n_unexp);
+  int best = -1;
+#pragma unroll
+  for (int j = 0; j < G::AP; ++j) {
+    const uint32_t c = __popcll(unexp[j]);
+    if (best < 0 && k < c) {
+      best = 64 * j + kth_set_bit(unexp[j], k);
+    } else if (best < 0) {
+      k -= c;
+    }
+  }
+  t.leaf = node;
+  t.depth = depth;
+  t.yready = 0;
+  t.nunexp = n_unexp;
+#pragma unroll
+  for (int j = 0; j < G::AP; ++j) t.umask[j] = unexp[j];
+  if (st) st->lap(37);
+  return best;
+}
+
 // ---------------------------------------------------------------------------
 // select_leaf (self_play.py:239-335).  Wave 0.  Returns the action to expand
 // at t.leaf, or -1 when the walk ends at a terminal node (t.leaf).  The path
@@ -870,27 +939,8 @@ __device__ __forceinline__ int select_leaf(TreeLds<G>& t, const Acc& T, const Se
       }
     } else if (t.is_raw(node)) {               // first arrival at a lazily expanded node
       if (t.lognode != node) return need_logits();
-      // t.fbuf / t.dbuf are wave 1's while it forms the newest node's priors
-      if (t.newest >= 0)
-        while (__hip_atomic_load(&t.newp_node, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != t.newest)
-          __builtin_amdgcn_s_sleep(1);
-      float q[G::AP];
-      if (st) st->lap(36);
-      settle_lazy<G>(t, const_cast<float*>(pr_row), T.T.child + (size_t)node * G::A, sp.variant, t.fbuf, t.dbuf, q);
-      if (lane == 0) atomicAnd(&t.rawp[node >> 5], ~(1u << (node & 31)));
-      if (st) { st->lap(49); st->wave_add(50, 1); }
-#pragma unroll
-      for (int j = 0; j < G::AP; ++j) {
-        const int a = lane + 64 * j;
-        P[j] = a < G::A ? (double)q[j] : 0.0;
-        ch[j] = -1;
-        // the node is about to become a parent: its rows into the LDS copy
-        // where they are made (the HBM stores stay; see keep_rows below)
-        if constexpr (Acc::LDS)
-          if (a < G::A) { t.rowc_prior[a] = q[j]; t.rowc_child[a] = -1; }
-      }
-      if constexpr (Acc::LDS)
-        if (lane == 0) t.rowc_node = node;
+      // (its priors and rows, then the walk's end: none of its children is expanded)
+      return settle_arrival<G>(t, T, sp, key, sim, st, node, depth);
     } else {
       hbm_rows = true;
 #pragma unroll

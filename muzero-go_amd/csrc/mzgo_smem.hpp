@@ -213,14 +213,18 @@ __device__ __forceinline__ void latent_conv(Smem<G>& sm, const float* __restrict
 // and E[a] (Winograd boards): latent_conv with wino_input_rebuilt as the
 // input transform -- no materialized copy of the latent.  All threads;
 // returns synchronised (strip boards) / with the stores issued (one strip).
-template <class G>
+// pre / mid (one-strip boards only; wino_conv_rebuilt): the caller's work at
+// the conv's head, while the parent's Y is still in LDS, and under the GEMM's
+// second K half.
+template <class G, class Pre = WinoNoMid, class Mid = WinoNoMid>
 __device__ __forceinline__ void latent_conv_rebuilt(Smem<G>& sm, const NetParams& np, const float* ypar,
                                                     const float* ea, float* dst, Stamp* st = nullptr,
-                                                    float* ylds = nullptr, bool par_in_lds = false) {
+                                                    float* ylds = nullptr, bool par_in_lds = false,
+                                                    Pre pre = Pre{}, Mid mid = Mid{}) {
   if constexpr (G::WINO && Wino<G>::NSTRIP == 1) {
     // (the second channel slab transformed under the GEMM's first K half)
     wino_conv_rebuilt<G>(sm.u.v, sm.raw, sm.u.x.red, sm.u.x.hp, sm.u.x.outs, sm.hfin, ypar, ea, np.w_dyn, np.b_dyn,
-                         dst, st, ylds, par_in_lds ? ylds : nullptr);
+                         dst, st, ylds, par_in_lds ? ylds : nullptr, 0, 0, G::C / 16, pre, mid);
   } else if constexpr (G::WINO) {
     for (int s = 0; s < Wino<G>::NSTRIP; ++s)
       wino_conv_rebuilt<G>(sm.u.v, sm.raw, sm.u.x.red, sm.u.x.hp, sm.u.x.outs, sm.hfin, ypar, ea, np.w_dyn,

@@ -429,11 +429,14 @@ __device__ __forceinline__ constexpr float wino_at3(int ox, int j) {
 // chain still adds k = 0 .. KP-1 in order, so the sums are the same bits):
 // hook(s) runs between the MFMA groups of step s of the first half, and a
 // hook that DEFERS the second half's V (wino_conv_rebuilt: that half is
-// transformed during the first) finishes with hook.finish() before it.
+// transformed during the first) finishes with hook.finish() before it;
+// hook.second(s) runs likewise after step s of the second half (no barrier
+// may stand there: after finish() the next one is the one behind the GEMM).
 struct WinoNoHook {
   static constexpr bool DEFERS = false;
   __device__ void operator()(int) const {}
   __device__ void finish() const {}
+  __device__ void second(int) const {}
 };
 template <class G, int CIN, int COUT, int NH, bool YM = false, class Hook = WinoNoHook>
 __device__ __forceinline__ void wino_conv(const float* V, float* red, float* hp, float* outs, float* hfin,
@@ -526,6 +529,7 @@ __device__ __forceinline__ void wino_conv(const float* V, float* red, float* hp,
             if (pos0 + q + PF < L) ar[(pos0 + q) % PF] = ap[(pos0 + q + PF) * 64];
           __builtin_amdgcn_sched_barrier(0);
           if (kh == 0) hook(s);
+          else hook.second(g * KH + kk);
         }
       }
     }
@@ -795,7 +799,15 @@ __device__ __forceinline__ void wino_conv(const float* V, float* red, float* hp,
 // between the first half's MFMA groups instead of before the GEMM: its LDS
 // and VALU work issues under the matrix cores' time.  The same operations as
 // wino_input_rebuilt + wino_conv, so the same bits.
-template <class G>
+//
+// Mid (sim_loop's arrival conv): wave-level work of the caller's that needs
+// none of the conv's LDS, run by whichever waves it chooses after step
+// kArrive of the second half -- the SIMD's other waves keep its matrix core
+// fed meanwhile.  It holds no barrier.
+struct WinoNoMid {
+  __device__ void operator()() const {}
+};
+template <class G, class Mid = WinoNoMid>
 struct RebuiltHook {
   static constexpr bool DEFERS = true;
   // first-half steps (of KP / 2 * XI / 2 / kWinoXG = 15 at 9x9) after which
@@ -803,28 +815,42 @@ struct RebuiltHook {
   // (measured, same call: (2, 7, 10) 81.4-81.6 M sims/s, (2, 6, 9) 81.3,
   // (4, 10, 12) 81.3-81.4, (1, 5, 7) 81.0, (0, 3, 4) 80.4-80.7)
   static constexpr int kScatter = 2, kBarrier = 7, kTransform = 10;
+  // second-half step (of the same 15) after which Mid runs (measured with
+  // sim_loop's arrival conv, same call: step 1 143.5-143.7 M sims/s, 5
+  // 142.9-143.3, 9 142.5-142.9, 13 142.9-143.0; the earlier wave 0 starts,
+  // the more of its own MFMAs are left to hide behind)
+  static constexpr int kArrive = 1;
   RebuiltInput<G, G::C> in;
+  Mid mid;
   __device__ __forceinline__ void operator()(int s) {
     if (s == kScatter) in.scatter(1);
     else if (s == kBarrier) __syncthreads();
     else if (s == kTransform) in.transform(1);
   }
   __device__ __forceinline__ void finish() { __syncthreads(); }
+  __device__ __forceinline__ void second(int s) {
+    if (s == kArrive) mid();
+  }
 };
-template <class G>
+// pre(): the caller's work on the parent's Y before the transform overwrites
+// its LDS copy (all threads, no barrier; the conv's barriers publish it)
+template <class G, class Pre = WinoNoMid, class Mid = WinoNoMid>
 __device__ __forceinline__ void wino_conv_rebuilt(float* V, float* raw, float* red, float* hp, float* outs,
                                                   float* hfin, const float* __restrict__ ypar,
                                                   const float* __restrict__ ea, const float* __restrict__ upk,
                                                   const float* __restrict__ bias, float* __restrict__ out,
                                                   Stamp* st, float* ylds, const float* ysrc_lds, int strip = 0,
-                                                  int m0 = 0, int nm = G::C / 16) {
+                                                  int m0 = 0, int nm = G::C / 16, Pre pre = Pre{},
+                                                  Mid mid = Mid{}) {
   static_assert(RebuiltInput<G, G::C>::SLABS == 2, "two slabs");
   RebuiltInput<G, G::C> in(V, raw, ypar, ea, strip, ysrc_lds);
   in.begin();
+  pre();
   in.slab(0);
   if (st) st->lap(1);
-  wino_conv<G, G::C, G::C, 0, true, RebuiltHook<G>>(V, red, hp, outs, hfin, upk, bias, out, G::CS, G::CS, nullptr,
-                                                     strip, st, ylds, m0, nm, RebuiltHook<G>{in});
+  wino_conv<G, G::C, G::C, 0, true, RebuiltHook<G, Mid>>(V, red, hp, outs, hfin, upk, bias, out, G::CS, G::CS,
+                                                          nullptr, strip, st, ylds, m0, nm,
+                                                          RebuiltHook<G, Mid>{in, mid});
 }
 
 }  // namespace mzgo

@@ -300,12 +300,15 @@ class Engine:
 
     def search_stats(self):
         """Speculative-batch statistics of every search since the engine was
-        made (mzgo_search_stats; LDS-tree boards, zeros elsewhere): batch
+        made (mzgo_search_stats2; LDS-tree boards, zeros elsewhere): batch
         children expanded, batch children whose value came from the value
-        cache instead, batches cut short by their replay."""
-        out = np.zeros(3, np.uint64)
-        check(lib.mzgo_search_stats(self._h, ptr(out), stream_of(self.device)))
-        return dict(batch_children_computed=int(out[0]), batch_children_cached=int(out[1]), batches_cut=int(out[2]))
+        cache instead, batches cut short by their replay, and the arrival
+        convs (9x9; MZGO_ARRIVAL_CONV) whose parent's Y came from its LDS
+        copy / from L2."""
+        out = np.zeros(5, np.uint64)
+        check(lib.mzgo_search_stats2(self._h, ptr(out), len(out), stream_of(self.device)))
+        return dict(batch_children_computed=int(out[0]), batch_children_cached=int(out[1]), batches_cut=int(out[2]),
+                    arrival_convs_lds=int(out[3]), arrival_convs_l2=int(out[4]))
 
     def wait_started(self, target, stream=None):
         """Diagnostic (scripts/rccl_standin.py; bench.py does not use it):
