@@ -8,6 +8,8 @@
  *   mzgo_recurrent_inference  MuZeroNet.recurrent_inference    self_play.py:125-128
  *   mzgo_set_weights          MuZeroNet.load_state_dict /       self_play.py:404-412
  *                             MuZeroAgent.load_weights
+ *   mzgo_set_weights_device   the same from the parameters in device memory
+ *                             (after an optimizer step; no reference counterpart)
  *   mzgo_search               MCTS.run                         self_play.py:148-237
  *   mzgo_board_reset          GoEnv.reset (GymGo)              self_play.py:455
  *   mzgo_board_step           GoEnv.step  (GymGo)              self_play.py:479
@@ -93,6 +95,37 @@ int64_t mzgo_engine_device_bytes(const mzgo_engine* eng);
 int mzgo_set_weights(mzgo_engine* eng, const char* key, const float* data_host,
                      const int64_t* shape, int ndim);
 int mzgo_weights_ready(const mzgo_engine* eng);
+
+/* The same weights from device memory (reference network engines, tower = 0).
+ *
+ * All 22 state_dict tensors from device memory (float32, contiguous, on the
+ * engine's device), packed on `stream` by kernels; no host copy is made.
+ * keys/data/shapes/ndims have n entries and must name every key exactly once.
+ * The embedding is (N*N+1, C): the first rows of a larger table.
+ *
+ * Ordering: the pack is enqueued on `stream` and returns without waiting.  It
+ * reads the tensors and writes the engine's packed weights in stream order, so
+ * (as for every other entry point) calls on one engine share a stream or are
+ * synchronised by the caller: the tensors must not change before the pack has
+ * run, and no launch of this engine on another stream may still be running or
+ * start before it has.  After the first load of an engine (which allocates),
+ * mzgo_set_weights_device and mzgo_weights_copy allocate nothing, make no
+ * blocking copy and synchronise neither stream nor device.
+ *
+ * Afterwards the engine's host copies (mzgo_set_weights) are dropped:
+ * mzgo_weights_ready() returns 1, and a later mzgo_set_weights takes effect
+ * once all 22 keys have been given again (MZGO_ENOWEIGHTS until then). */
+int mzgo_set_weights_device(mzgo_engine* eng, const char* const* keys, const float* const* data_dev,
+                            const int64_t* const* shapes, const int* ndims, int n, void* stream);
+/* dst's packed weights := src's (same board_size, latent_dim, tower = 0): one
+ * device-to-device copy on `stream`.  Tensors that src got by mzgo_set_weights
+ * and has not uploaded yet are packed first (that part blocks, as every first
+ * use after mzgo_set_weights does). */
+int mzgo_weights_copy(mzgo_engine* dst, const mzgo_engine* src, void* stream);
+/* The packed blob to the host (synchronises `stream`): *n_floats = its length;
+ * data may be NULL to query; cap in floats.  A test and diagnostic hook: the
+ * layout is mzgo_weights.hpp's and depends on (board_size, latent_dim) only. */
+int mzgo_weights_export(mzgo_engine* eng, float* data_host, int64_t cap, int64_t* n_floats, void* stream);
 
 /* MuZeroNet protocol, batch B (any B >= 1):
  *   obs f32 [B][6][N][N] -> latent f32 [B][C][N][N], value f32 [B][1], logits f32 [B][N*N+1]  */

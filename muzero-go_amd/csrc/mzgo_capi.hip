@@ -15,6 +15,7 @@
 #include "mzgo_dispatch.hpp"
 #include "mzgo_replay.hpp"
 #include "mzgo_tower_host.hpp"
+#include "mzgo_weights.hpp"
 
 namespace mzgo {
 extern const KernelSet kernels_n5_c96, kernels_n6_c96, kernels_n9_c96, kernels_n19_c96, kernels_n6_c128,
@@ -227,6 +228,8 @@ struct mzgo_engine {
   std::map<std::string, std::vector<float>> sd;  // host copies of the state_dict
   std::vector<Spec> spec;
   bool dirty = true;
+  bool dev_weights = false;     // d_w holds weights packed on the device (or copied): sd is empty, not missing
+  WeightLayout wl;              // d_w's parts and offsets (mzgo_weights.hpp)
   float* d_w = nullptr;
   size_t d_w_bytes = 0;
   NetParams np{};
@@ -276,7 +279,31 @@ struct mzgo_engine {
     if (d_scr) (void)hipFree(d_scr);
   }
 
+  // The weight blob (reference network): allocated and zeroed at the first
+  // load by either path, with NetParams pointing into it; never moved after.
+  int ensure_blob() {
+    if (d_w) return MZGO_OK;
+    wl = weight_layout(N, C, A);
+    HIPCHK(hipMalloc(&d_w, wl.total * 4));
+    d_w_bytes = wl.total * 4;
+    HIPCHK(hipMemset(d_w, 0, d_w_bytes));            // the parts' padding stays zero
+    const float* b = d_w;
+    const size_t* off = wl.off;
+    np.w_conv1 = b + off[WP_CONV1_W]; np.b_conv1 = b + off[WP_CONV1_B];
+    np.w_conv2 = b + off[WP_CONV2_W]; np.b_conv2 = b + off[WP_CONV2_B];
+    np.w_conv3 = b + off[WP_CONV3_W]; np.b_conv3 = b + off[WP_CONV3_B];
+    np.w_dyn = b + off[WP_DYN_W]; np.b_dyn = b + off[WP_DYN_B];
+    np.emb = b + off[WP_EMB]; np.head_w = b + off[WP_HEAD_W]; np.etab = b + off[WP_ETAB];
+    np.hs.reward_b = b + off[WP_REWARD_B]; np.hs.fc1_w = b + off[WP_FC1_W]; np.hs.fc1_b = b + off[WP_FC1_B];
+    np.hs.fc2_w = b + off[WP_FC2_W]; np.hs.fc2_b = b + off[WP_FC2_B]; np.hs.value_b = b + off[WP_VALUE_B];
+    np.hs.vfc_w = b + off[WP_VFC_W]; np.hs.vfc_b = b + off[WP_VFC_B]; np.hs.policy_b = b + off[WP_POLICY_B];
+    np.hs.pass_logit = b + off[WP_PASS_LOGIT];
+    return MZGO_OK;
+  }
+
   // pack + upload the network if any tensor changed since the last upload
+  // (nothing to do after mzgo_set_weights_device / mzgo_weights_copy until a
+  // host tensor arrives; then all 22 are needed again)
   int sync_weights() {
     if (C == 0) return fail(MZGO_EINVAL, "board-only engine (latent_dim 0) has no network");
     if (!dirty) return MZGO_OK;
@@ -287,15 +314,14 @@ struct mzgo_engine {
       dirty = false;
       return MZGO_OK;
     }
+    if (int rc = ensure_blob()) return rc;
+    // the parts in blob order (WeightPart, mzgo_weights.hpp)
     std::vector<std::vector<float>> parts;
     parts.push_back(pack_conv(sd["representation.conv1.weight"].data(), 64, 6, false));
     parts.push_back(sd["representation.conv1.bias"]);
-    // k-range split of the ring conv: 2 when the board runs 8 waves (Geo::KSPLIT)
-    const int ct = (N * N + 15) / 16, ng = ct >= 3 ? 3 : ct, ncg = (ct + ng - 1) / ng;
-    const int ksplit = ncg <= 2 ? 2 : 1;
-    const bool wino = N == 9 || N == 19;           // Geo::WINO
     auto latent = [&](const char* key, int cout, int cin) {
-      return wino ? pack_wino(sd[key].data(), cout, cin, true) : pack_conv(sd[key].data(), cout, cin, true, ksplit);
+      return wl.wino ? pack_wino(sd[key].data(), cout, cin, true)
+                     : pack_conv(sd[key].data(), cout, cin, true, wl.ksplit);
     };
     parts.push_back(latent("representation.conv2.weight", 64, 64));
     parts.push_back(sd["representation.conv2.bias"]);
@@ -305,39 +331,18 @@ struct mzgo_engine {
     parts.push_back(sd["dynamics.conv.bias"]);
     parts.push_back(sd["dynamics.action_embedding.weight"]);
     std::vector<float> hw;
-    for (const char* k : {"dynamics.reward_conv.weight", "prediction.value_conv.weight",
-                          "prediction.policy_conv.weight"})
-      hw.insert(hw.end(), sd[k].begin(), sd[k].end());
+    for (WeightKey k : kHeadKeys) hw.insert(hw.end(), sd[spec[k].key].begin(), sd[spec[k].key].end());
     parts.push_back(hw);
     parts.push_back(action_taps(sd["dynamics.conv.weight"].data(), sd["dynamics.action_embedding.weight"].data(), C, A));
-    const char* scal[] = {"dynamics.reward_conv.bias", "dynamics.fc_reward_hidden.weight",
-                          "dynamics.fc_reward_hidden.bias", "dynamics.fc_reward_output.weight",
-                          "dynamics.fc_reward_output.bias", "prediction.value_conv.bias",
-                          "prediction.value_fc.weight", "prediction.value_fc.bias",
-                          "prediction.policy_conv.bias", "prediction.pass_logit"};
-    for (const char* k : scal) parts.push_back(sd[k]);
-    std::vector<size_t> off;
-    size_t total = 0;
-    for (auto& p : parts) { off.push_back(total); total += (p.size() + 63) / 64 * 64; }
-    std::vector<float> blob(total, 0.f);
-    for (size_t i = 0; i < parts.size(); ++i) std::memcpy(blob.data() + off[i], parts[i].data(), parts[i].size() * 4);
-    if (total * 4 > d_w_bytes) {
-      if (d_w) (void)hipFree(d_w);
-      d_w = nullptr;
-      HIPCHK(hipMalloc(&d_w, total * 4));
-      d_w_bytes = total * 4;
-    }
-    HIPCHK(hipMemcpy(d_w, blob.data(), total * 4, hipMemcpyHostToDevice));
-    const float* b = d_w;
-    np.w_conv1 = b + off[0]; np.b_conv1 = b + off[1];
-    np.w_conv2 = b + off[2]; np.b_conv2 = b + off[3];
-    np.w_conv3 = b + off[4]; np.b_conv3 = b + off[5];
-    np.w_dyn = b + off[6]; np.b_dyn = b + off[7];
-    np.emb = b + off[8]; np.head_w = b + off[9]; np.etab = b + off[10];
-    np.hs.reward_b = b + off[11]; np.hs.fc1_w = b + off[12]; np.hs.fc1_b = b + off[13];
-    np.hs.fc2_w = b + off[14]; np.hs.fc2_b = b + off[15]; np.hs.value_b = b + off[16];
-    np.hs.vfc_w = b + off[17]; np.hs.vfc_b = b + off[18]; np.hs.policy_b = b + off[19];
-    np.hs.pass_logit = b + off[20];
+    for (WeightKey k : kScalarKeys) parts.push_back(sd[spec[k].key]);
+    if ((int)parts.size() != WP_COUNT) return fail(MZGO_EASSERT, "weight blob: %zu parts, layout has %d", parts.size(), (int)WP_COUNT);
+    for (int i = 0; i < WP_COUNT; ++i)
+      if (parts[i].size() != wl.size[i])
+        return fail(MZGO_EASSERT, "weight blob: part %d has %zu floats, layout says %zu", i, parts[i].size(), wl.size[i]);
+    std::vector<float> blob(wl.total, 0.f);
+    for (int i = 0; i < WP_COUNT; ++i) std::memcpy(blob.data() + wl.off[i], parts[i].data(), parts[i].size() * 4);
+    HIPCHK(hipMemcpy(d_w, blob.data(), wl.total * 4, hipMemcpyHostToDevice));
+    dev_weights = false;
     dirty = false;
     return MZGO_OK;
   }
@@ -607,9 +612,76 @@ int mzgo_set_weights(mzgo_engine* e, const char* key, const float* data, const i
 
 int mzgo_weights_ready(const mzgo_engine* e) {
   if (!e || e->C == 0) return 0;
+  if (e->dev_weights && !e->dirty) return 1;
   for (const Spec& s : e->spec)
     if (!e->sd.count(s.key)) return 0;
   return 1;
+}
+
+int mzgo_set_weights_device(mzgo_engine* e, const char* const* keys, const float* const* data_dev,
+                            const int64_t* const* shapes, const int* ndims, int n, void* stream) {
+  if (!e || !keys || !data_dev || !shapes || !ndims) return fail(MZGO_EINVAL, "mzgo_set_weights_device: null argument");
+  if (e->C == 0) return fail(MZGO_EINVAL, "mzgo_set_weights_device: board-only engine (latent_dim 0) has no network");
+  if (e->tower) return fail(MZGO_EINVAL, "mzgo_set_weights_device: tower engines (tower = 1) are not supported");
+  if ((int)e->spec.size() != WK_COUNT) return fail(MZGO_EASSERT, "mzgo_set_weights_device: %zu specs", e->spec.size());
+  const float* src[WK_COUNT] = {};
+  for (int i = 0; i < n; ++i) {
+    if (!keys[i] || !data_dev[i] || (!shapes[i] && ndims[i] > 0))
+      return fail(MZGO_EINVAL, "mzgo_set_weights_device: null entry %d ('%s')", i, keys[i] ? keys[i] : "?");
+    int k = 0;
+    while (k < WK_COUNT && e->spec[k].key != keys[i]) ++k;
+    if (k == WK_COUNT) return fail(MZGO_EINVAL, "unexpected key '%s' in state_dict", keys[i]);
+    if (src[k]) return fail(MZGO_EINVAL, "duplicate key '%s'", keys[i]);
+    const Spec& s = e->spec[k];
+    if ((int)s.shape.size() != ndims[i])
+      return fail(MZGO_EINVAL, "'%s': expected %zu dims, got %d", keys[i], s.shape.size(), ndims[i]);
+    for (int d = 0; d < ndims[i]; ++d)
+      if (shapes[i][d] != s.shape[d])
+        return fail(MZGO_EINVAL, "'%s': dim %d is %lld, expected %lld", keys[i], d, (long long)shapes[i][d],
+                    (long long)s.shape[d]);
+    src[k] = data_dev[i];
+  }
+  for (int k = 0; k < WK_COUNT; ++k)
+    if (!src[k]) return fail(MZGO_EINVAL, "missing weight '%s'", e->spec[k].key.c_str());
+  if (int rc = e->ensure_blob()) return rc;
+  HIPCHK(pack_weights_device(e->wl, src, e->d_w, (hipStream_t)stream));
+  e->sd.clear();                                      // the host copies are stale
+  e->dirty = false;
+  e->dev_weights = true;
+  return MZGO_OK;
+}
+
+int mzgo_weights_copy(mzgo_engine* dst, const mzgo_engine* src_c, void* stream) {
+  mzgo_engine* src = const_cast<mzgo_engine*>(src_c);   // (its pending host tensors are packed first)
+  if (!dst || !src) return fail(MZGO_EINVAL, "mzgo_weights_copy: null engine");
+  if (dst->C == 0 || src->C == 0)
+    return fail(MZGO_EINVAL, "mzgo_weights_copy: board-only engine (latent_dim 0) has no network");
+  if (dst->tower || src->tower) return fail(MZGO_EINVAL, "mzgo_weights_copy: tower engines (tower = 1) are not supported");
+  if (dst->N != src->N || dst->C != src->C)
+    return fail(MZGO_EINVAL, "mzgo_weights_copy: engines differ (board_size %d / latent_dim %d from %d / %d)", dst->N,
+                dst->C, src->N, src->C);
+  if (int rc = src->sync_weights()) return rc;          // MZGO_ENOWEIGHTS when src was never loaded
+  if (dst == src) return MZGO_OK;
+  if (int rc = dst->ensure_blob()) return rc;
+  HIPCHK(hipMemcpyAsync(dst->d_w, src->d_w, src->wl.total * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  dst->sd.clear();
+  dst->dirty = false;
+  dst->dev_weights = true;
+  return MZGO_OK;
+}
+
+int mzgo_weights_export(mzgo_engine* e, float* data_host, int64_t cap, int64_t* n_floats, void* stream) {
+  if (!e || !n_floats) return fail(MZGO_EINVAL, "mzgo_weights_export: null argument");
+  if (e->C == 0) return fail(MZGO_EINVAL, "mzgo_weights_export: board-only engine (latent_dim 0) has no network");
+  if (e->tower) return fail(MZGO_EINVAL, "mzgo_weights_export: tower engines (tower = 1) are not supported");
+  if (int rc = e->sync_weights()) return rc;
+  *n_floats = (int64_t)e->wl.total;
+  if (!data_host) return MZGO_OK;
+  if (cap < *n_floats)
+    return fail(MZGO_EINVAL, "mzgo_weights_export: cap %lld < %lld floats", (long long)cap, (long long)*n_floats);
+  HIPCHK(hipMemcpyAsync(data_host, e->d_w, e->wl.total * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  return MZGO_OK;
 }
 
 int mzgo_initial_inference(mzgo_engine* e, const float* obs, int B, float* latent, float* value,

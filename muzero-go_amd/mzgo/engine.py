@@ -110,6 +110,55 @@ class Engine:
         if not lib.mzgo_weights_ready(self._h):
             check(_lib.MZGO_ENOWEIGHTS)
 
+    def set_parameters_device(self, named_tensors):
+        """Load the reference state_dict from CUDA tensors without a host copy
+        (mzgo_set_weights_device): one pack launch on the current stream, no
+        synchronisation.  ``named_tensors``: a mapping or (key, tensor) pairs
+        naming every key once, on this engine's device; a tensor that is not
+        contiguous float32 is converted on the device first.  The embedding's
+        rows past the board's actions stay out (play.py:193), as in
+        ``set_state_dict``.  The tensors must not change before the launch has
+        run -- work on the current stream after this call is ordered behind it."""
+        items = list(named_tensors.items() if hasattr(named_tensors, "items") else named_tensors)
+        n = len(items)
+        keys = (ctypes.c_char_p * n)()
+        data = (ctypes.c_void_p * n)()
+        shapes = (ctypes.POINTER(ctypes.c_int64) * n)()
+        ndims = (ctypes.c_int * n)()
+        keep = []
+        for i, (key, t) in enumerate(items):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError(f"set_parameters_device: '{key}' is not a CUDA tensor (set_state_dict takes host tensors)")
+            if t.device != self.device:
+                raise ValueError(f"set_parameters_device: '{key}' is on {t.device}, the engine on {self.device}")
+            t = t.detach()
+            if key == "dynamics.action_embedding.weight" and t.dim() == 2 and t.shape[0] > self.A:
+                t = t[:self.A]                            # rows past the board's actions (play.py:193)
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                t = t.to(torch.float32).contiguous()
+            shape = (ctypes.c_int64 * max(t.dim(), 1))(*t.shape)
+            keep.append((t, shape))
+            keys[i] = key.encode()
+            data[i] = t.data_ptr()
+            shapes[i] = ctypes.cast(shape, ctypes.POINTER(ctypes.c_int64))
+            ndims[i] = t.dim()
+        check(lib.mzgo_set_weights_device(self._h, keys, data, shapes, ndims, n, stream_of(self.device)))
+
+    def copy_weights_from(self, other):
+        """This engine's packed weights := ``other``'s (same board size and
+        latent_dim): one device-to-device copy on the current stream
+        (mzgo_weights_copy), no repacking."""
+        check(lib.mzgo_weights_copy(self._h, other.handle, stream_of(self.device)))
+
+    def export_weights(self):
+        """Host copy of the packed weight blob (numpy float32; synchronises): a
+        test and diagnostic hook (mzgo_weights_export)."""
+        n = ctypes.c_int64()
+        check(lib.mzgo_weights_export(self._h, None, 0, ctypes.byref(n), stream_of(self.device)))
+        out = np.empty(n.value, np.float32)
+        check(lib.mzgo_weights_export(self._h, ptr(out), n.value, ctypes.byref(n), stream_of(self.device)))
+        return out
+
     # ---- network protocol ----
     def initial_inference(self, obs):
         B = obs.shape[0]

@@ -51,11 +51,31 @@ def board_size_of(action_size):
     return n
 
 
+def refresh_engine_device(net, eng, version):
+    """Give ``eng`` the weights of ``net`` (at ``version`` = ``net._version()``)
+    without the host: a device-to-device copy from another cached engine of
+    the net that already holds them, else one pack launch from the parameters
+    (``Engine.set_parameters_device``).  Stream-ordered, no synchronisation."""
+    for other in net._engines.values():
+        if other is not eng and other._weights_key == version and other.device == eng.device:
+            eng.copy_weights_from(other)
+            return
+    eng.set_parameters_device(net.state_dict())
+
+
 class MuZeroNet(nn.Module):
     """``board_size``: for networks whose embedding table is larger than the
     board's N*N+1 actions (play.py:193 sizes it int(1.5 N^2)); the extra rows
     are kept in the state_dict and never reach the engine (actions >= N*N+1
-    do not exist on the board)."""
+    do not exist on the board).
+
+    ``device_weights`` (default False): a stale engine is refreshed on the
+    device -- the parameters packed by one launch on the current stream, or
+    copied from another engine of this net that already has them -- instead of
+    through host copies of the 22 tensors (``Engine.set_state_dict``).  Same
+    packed weights bit for bit, and ``engine()`` no longer synchronises."""
+
+    device_weights = False
 
     def __init__(self, latent_dim, max_action_size, board_size=None):
         super().__init__()
@@ -92,7 +112,10 @@ class MuZeroNet(nn.Module):
             self._engines[key] = eng
         v = self._version()
         if eng._weights_key != v:
-            eng.set_state_dict(self.state_dict())
+            if self.device_weights:
+                refresh_engine_device(self, eng, v)
+            else:
+                eng.set_state_dict(self.state_dict())
             eng._weights_key = v
         return eng
 

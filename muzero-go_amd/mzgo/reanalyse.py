@@ -92,8 +92,18 @@ class Reanalyser:
             slots = self.slots or torch.cuda.get_device_properties(dev).multi_processor_count
             self._engine = Engine(EngineConfig(board_size=self.N, latent_dim=self.net.latent_dim, num_games=slots,
                                                num_simulations=self.S, device=dev.index or 0, **self.options))
-            self._engine.set_state_dict(self.net.state_dict())
+            self._load()
         return self._engine
+
+    def _load(self):
+        """The net's weights into the engine: on the device (a copy from one of
+        the net's engines that has them, else one pack launch) when the net's
+        ``device_weights`` is set, through the host otherwise."""
+        if getattr(self.net, "device_weights", False):
+            from .net import refresh_engine_device
+            refresh_engine_device(self.net, self._engine, self.net._version())
+        else:
+            self._engine.set_state_dict(self.net.state_dict())
 
     def refresh(self, net=None):
         """Reload the weights (of ``net``, or of the net given before)."""
@@ -102,7 +112,7 @@ class Reanalyser:
                 raise ValueError("refresh: the net's board size / latent_dim differ from the reanalyser's")
             self.net = net
         if self._engine is not None:
-            self._engine.set_state_dict(self.net.state_dict())
+            self._load()
 
     def run(self, trajectories, ids=None):
         """Search the first T = len(actions) observations of every trajectory

@@ -58,6 +58,8 @@ class ResMuZeroNet(nn.Module):
     """Same protocol as ``mzgo.MuZeroNet`` (initial_inference /
     recurrent_inference / engine); defaults are config 5's C=256, 20 blocks."""
 
+    device_weights = False     # (MuZeroNet's switch: refused here, see engine())
+
     def __init__(self, latent_dim=256, max_action_size=362, blocks=20):
         super().__init__()
         if latent_dim % 64:
@@ -76,6 +78,9 @@ class ResMuZeroNet(nn.Module):
 
     def engine(self, num_games=1, num_simulations=1, **cfg):
         """A HIP tower engine with this net's current weights (cached per shape/config)."""
+        if self.device_weights:
+            raise ValueError("device_weights is not supported by the residual tower (ResMuZeroNet, tower = 1): its "
+                             "bf16 weight layout is packed on the host only")
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("ResMuZeroNet runs on the GPU only: call .to('cuda') first")

@@ -107,18 +107,28 @@ class SelfPlay:
         self.G = num_games
         self.S = num_simulations
         self.discount = discount
-        self.engine = net.engine(num_games, num_simulations, seed=seed, compat=compat,
-                                 max_moves=max_moves, temperature=temperature,
+        self._engine_args = dict(seed=seed, compat=compat, max_moves=max_moves, temperature=temperature,
                                  temperature_moves=temperature_moves, komi=float(komi),
                                  game_base=game_base, discount=discount, c_puct=c_puct,
                                  dirichlet_alpha=dirichlet_alpha,
                                  dirichlet_epsilon=dirichlet_epsilon, pass_epsilon=pass_epsilon,
                                  search_variant=search_variant, dynamics=dynamics)
+        self.engine = net.engine(num_games, num_simulations, **self._engine_args)
         self.max_moves = self.engine.M
         self.epoch = 0
         self.game_base = game_base
         self._record_epoch = 0      # the generation of the games in the slots (reset())
         self._mixed_slots = False   # play_games_into() left games of several epochs in the slots
+
+    def refresh(self):
+        """Give the bound engine the net's current weights (after training):
+        ``net.engine`` with the constructor's arguments again, so a net with
+        ``device_weights`` refreshes it on the device -- by a copy when another
+        of its engines already has these weights.  The games in the slots stay
+        (a net moved with ``.to()`` since has dropped its engines: then this
+        binds a new engine, with empty slots)."""
+        self.engine = self.net.engine(self.G, self.S, **self._engine_args)
+        return self.engine
 
     def reset(self, epoch=None):
         if epoch is not None:

@@ -50,6 +50,12 @@ on the device, every game of a batch at once) and trains on it:
   is a launch, and only the totals come back -- on demand (``read_stats``)
   with ``deferred_stats``.  ``importance_beta`` weights the loss by the
   sampler's importance weights, ``priority_alpha`` is the priority exponent.
+  ``TrainConfig.device_weights`` (default off) sets ``MuZeroNet.device_weights``:
+  after an optimizer step the engines take the new weights from the
+  parameters in device memory (one pack launch, ``Engine.set_parameters_device``;
+  a copy for the net's further engines) instead of 22 host copies and the
+  host packers -- the same packed weights bit for bit.  A ``deferred_stats``
+  step synchronises nowhere only with it.
 
 ``initial_inference_torch`` / ``recurrent_inference_torch`` restate
 main.py:72-144 with torch ops on the module's own parameters (reference
@@ -89,6 +95,7 @@ class TrainConfig:
     importance_beta: float = 0.0      # device_sampling: importance-weight exponent (0 = unweighted loss)
     priority_alpha: float = 1.0       # device_sampling: a new priority is loss ** alpha
     deferred_stats: bool = False      # device_sampling: train() returns a device scalar; read_stats() fills last
+    device_weights: bool = False      # the net's engines take new weights on the device (MuZeroNet.device_weights)
 
 
 def reward_value_transform(x, epsilon=0.001):
@@ -376,6 +383,10 @@ class MainSelfPlay:
                            game_base=game_base, c_puct=2.0, dirichlet_alpha=0.03, dirichlet_epsilon=0.25,
                            pass_epsilon=0.05, search_variant="main", dynamics=dynamics)
 
+    def refresh(self):
+        """The net's current weights into the self-play engine (``SelfPlay.refresh``)."""
+        return self.sp.refresh()
+
     def play(self):
         sp = self.sp
         sp.reset()
@@ -445,6 +456,11 @@ class MuZeroTrainer:
                              "(TrainConfig.device_sampling=True)")
         if c.importance_beta < 0 or not c.priority_alpha > 0:
             raise ValueError("importance_beta must be >= 0 and priority_alpha > 0")
+        if c.device_weights:
+            if next(net.parameters()).device.type != "cuda":
+                raise ValueError("device_weights needs the net on the GPU (net.to('cuda')): the engines' weights are "
+                                 "packed from the parameters in device memory")
+            net.device_weights = True
         self.mode = mode
         self.sample_seed = int(sample_seed)   # device_sampling: the sampler's seed; its step is sample_step
         self.sample_step = 0                  # steps taken with device_sampling
@@ -594,7 +610,11 @@ class MuZeroTrainer:
         """``_train_device`` with the store's device ledger: the sample, the
         targets, the step and the priority update are queued on the stream
         without the host seeing an index or a loss; the one copy of the totals
-        is the step's only synchronisation (none with ``deferred_stats``)."""
+        is the step's only synchronisation of its own (none with
+        ``deferred_stats``).  The bootstrap values' ``initial_inference`` still
+        reloads the engine's weights through the host after every optimizer
+        step, with one blocking copy per tensor, unless ``device_weights`` is
+        set: only then is a ``deferred_stats`` step free of synchronisation."""
         from .replay import finish_values
         c, N = self.config, self.net.board_size
         s = replay.sample_batch(batch_size, c.unroll_steps, c.discount, seed=self.sample_seed, step=self.sample_step,
