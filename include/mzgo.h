@@ -647,6 +647,99 @@ int mzgo_unroll_loss_host(const float* logits, const float* value, const float* 
                           float w_reward, int value_transform, float* per_sample, double* totals, float* g_logits,
                           float* g_value, float* g_reward);
 
+/* --------------------------------------------------------------------------
+ * The trainer's whole unroll in one forward and one backward call
+ * (main.py:431-482 unrolls a trajectory step by step through
+ * RepresentationNetwork, main.py:72-84, K times DynamicsNetwork,
+ * main.py:97-113, and PredictionNetwork, main.py:116-144, on every latent;
+ * these calls replace that protocol and its autograd graph for B samples at
+ * once: the 3 + K convs in sequence on the fp32 MFMA kernels of
+ * mzgo_conv3x3_relu_forward / mzgo_conv3x3_backward, the heads of all K + 1
+ * latents in one launch each way).  fp32, deterministic (fixed summation
+ * orders, no atomics: the same inputs give the same bits), everything
+ * enqueued on ``stream``; no call allocates or synchronises.
+ *
+ * Parameters and gradients are key / pointer tables in the convention of
+ * mzgo_set_weights_device: ``keys`` names each of the 22 reference state_dict
+ * tensors once, in any order; ``params[i]`` is the tensor (device f32,
+ * contiguous) with ``shapes[i]`` / ``ndims[i]`` its state_dict shape for
+ * latent_dim C -- the embedding [emb_rows][C] with emb_rows >= N*N + 1 (a
+ * table larger than the board, play.py:193, is taken whole); ``grads[i]``
+ * (backward) receives the gradient of ``keys[i]``, same shape.
+ *
+ * mzgo_unroll_workspace: the sizes of the two caller-owned device buffers,
+ * ``saved`` (written by the forward, read by the backward: the observations,
+ * the representation's two hidden activations, the K + 1 latents
+ * [K+1][B][C][N][N] step-major, the heads' two board means per (step, sample)
+ * and the actions step-major) and ``work`` (the backward's scratch: the
+ * latents' gradients, the conv weight partials, the heads' partial sums).
+ *
+ * mzgo_unroll_forward: obs0 [B][6][N][N], acts i64 [B][K] (the action taken
+ * before step k, sample-major as mzgo_replay_batch returns them; values
+ * 0 <= a < emb_rows are the caller's contract, as in mzgo_dyn_conv_backward).
+ *   latent_0 = representation(obs0); latent_k = relu(conv(latent_{k-1} +
+ *   emb[acts[:, k-1]]) + bias)
+ *   logits [K+1][B][A], A = N*N + 1: policy_conv (C -> 1) per cell, the pass
+ *                       logit in column A - 1
+ *   value [K+1][B]      value_fc(mean over the board of value_conv(latent))
+ *   reward [K][B]       row k - 1, for steps k >= 1: fc_reward_output(relu(
+ *                       fc_reward_hidden(mean of reward_conv(latent_k))))
+ * in mzgo_unroll_loss's step-major layouts.  K + 5 launches.  K == 0 is legal:
+ * acts and reward may be NULL.
+ *
+ * mzgo_unroll_backward: from ``saved`` and the gradients with respect to the
+ * three outputs (same layouts; g_reward may be NULL at K == 0), the gradients
+ * of all 22 parameters; there is no input gradient.
+ *   (a) one launch gives every latent's gradient from its heads,
+ *       G[s][b][c][p] = w_pol[c] g_logits[s,b,p] + (w_val[c] dvmean[s,b] +
+ *       w_rew[c] drmean[s,b]) / N^2, and a row of partial sums per (step,
+ *       sample) for the thirteen head tensors (the weights and biases of
+ *       policy_conv, value_conv, value_fc, reward_conv, fc_reward_hidden and
+ *       fc_reward_output, and pass_logit); a second sums the rows in a fixed
+ *       order.  A hidden reward unit whose pre-activation is <= 0 passes
+ *       nothing back (autograd's relu).
+ *   (b) for s = K .. 1 the dynamics conv's input gradient from G[s] masked by
+ *       latent_s > 0 is added into G[s-1]; its board sums are kept.
+ *   (c) the dynamics conv's weight and bias gradients in ONE pass over the
+ *       K B boards (steps 0..K-1 the inputs, 1..K the outputs and masks):
+ *       mzgo_conv3x3_backward's chunked fixed-order sum, with 8 boards per
+ *       chunk, or the next multiple of 8 that keeps the partials within 32 MiB
+ *       (at most one chunk of all K B boards, whatever that takes: from
+ *       C = 976 a single chunk's C*C*36 bytes exceed it).
+ *   (d) the embedding gradient [emb_rows][C]: a row is the sum, in (step,
+ *       sample) order, of the board sums whose action it is; every other row
+ *       is 0 (nn.Embedding's dense gradient).
+ *   (e) the representation's three layers from the saved activations.
+ * K + 17 launches.  At K == 0 the nine dynamics gradients (embedding, conv,
+ * reward_conv, fc_reward_hidden, fc_reward_output) are not written and their
+ * ``grads`` entries may be NULL.
+ *
+ * MZGO_EINVAL, with the reason in mzgo_last_error(), before any device work:
+ * B < 1; K < 0; C not a multiple of 16; N outside 2..19; emb_rows < N*N + 1;
+ * (K + 1) B above 2^31 - 1; a null required pointer; a missing, duplicate or unexpected key or a shape
+ * that is not the state_dict's; saved_bytes / work_bytes smaller than
+ * mzgo_unroll_workspace reports. */
+int mzgo_unroll_workspace(int B, int K, int C, int N, int emb_rows, int64_t* saved_bytes, int64_t* work_bytes);
+int mzgo_unroll_forward(const char* const* keys, const float* const* params, const int64_t* const* shapes,
+                        const int* ndims, int n_params, const float* obs0, const int64_t* acts, int B, int K, int C,
+                        int N, int emb_rows, void* saved, int64_t saved_bytes, float* logits, float* value,
+                        float* reward, void* stream);
+int mzgo_unroll_backward(const char* const* keys, const float* const* params, const int64_t* const* shapes,
+                         const int* ndims, float* const* grads, int n_params, const void* saved, int64_t saved_bytes,
+                         const float* g_logits, const float* g_value, const float* g_reward, int B, int K, int C, int N,
+                         int emb_rows, void* work, int64_t work_bytes, void* stream);
+/* The heads' host twin: the same scalar functions (csrc/mzgo_unroll.hpp) run
+ * serially over HOST arrays -- forward and backward of the heads of S = K + 1
+ * steps' latents [S][B][C][N][N] (every channel and cell sum in index order).
+ * The tables hold the thirteen head tensors only; ``grads`` receives their
+ * gradients and g_latent [S][B][C][N][N] the latents' (step (a) above).  At
+ * S == 1 reward, g_reward and the reward head's ``grads`` may be NULL.  No
+ * device work.  MZGO_EINVAL as above (S < 1 for K < 0). */
+int mzgo_unroll_heads_host(const char* const* keys, const float* const* params, const int64_t* const* shapes,
+                           const int* ndims, float* const* grads, int n_params, const float* latents, int S, int B,
+                           int C, int N, float* logits, float* value, float* reward, const float* g_logits,
+                           const float* g_value, const float* g_reward, float* g_latent);
+
 #ifdef __cplusplus
 }
 #endif

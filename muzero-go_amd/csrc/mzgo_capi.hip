@@ -78,20 +78,12 @@ struct Spec {
 };
 
 std::vector<Spec> specs(int C, int A) {
-  return {
-      {"representation.conv1.weight", {64, 6, 3, 3}}, {"representation.conv1.bias", {64}},
-      {"representation.conv2.weight", {64, 64, 3, 3}}, {"representation.conv2.bias", {64}},
-      {"representation.conv3.weight", {C, 64, 3, 3}}, {"representation.conv3.bias", {C}},
-      {"dynamics.action_embedding.weight", {A, C}},
-      {"dynamics.conv.weight", {C, C, 3, 3}}, {"dynamics.conv.bias", {C}},
-      {"dynamics.reward_conv.weight", {1, C, 1, 1}}, {"dynamics.reward_conv.bias", {1}},
-      {"dynamics.fc_reward_hidden.weight", {16, 1}}, {"dynamics.fc_reward_hidden.bias", {16}},
-      {"dynamics.fc_reward_output.weight", {1, 16}}, {"dynamics.fc_reward_output.bias", {1}},
-      {"prediction.pass_logit", {1}},
-      {"prediction.value_conv.weight", {1, C, 1, 1}}, {"prediction.value_conv.bias", {1}},
-      {"prediction.value_fc.weight", {1, 1}}, {"prediction.value_fc.bias", {1}},
-      {"prediction.policy_conv.weight", {1, C, 1, 1}}, {"prediction.policy_conv.bias", {1}},
-  };
+  std::vector<Spec> out;                                  // (mzgo_weights.hpp holds the keys and shapes)
+  for (int k = 0; k < WK_COUNT; ++k) {
+    const WeightShape sh = weight_key_shape(k, C, A);
+    out.push_back(Spec{kWeightKeyNames[k], std::vector<int64_t>(sh.d, sh.d + sh.nd)});
+  }
+  return out;
 }
 
 // conv weight W[cout][cin][3][3] -> MFMA A-fragment order of mzgo_conv.hpp:

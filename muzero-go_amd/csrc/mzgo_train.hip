@@ -37,7 +37,7 @@ namespace mzgo {
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-constexpr int kBwdChunk = 8;   // boards per gw partial (a chunk's K = 8 x cells)
+constexpr int kBwdChunk = 8;   // boards per gw partial (a chunk's K = 8 x cells); a caller may ask for more
 constexpr int kMaxN = 19;
 
 // gp at (b, co, cell (y, x)) or 0 off the board
@@ -125,7 +125,7 @@ __global__ void __launch_bounds__(64) k_conv_bwd_input(const float* __restrict__
   }
 }
 
-// partial[chunk][co][ci][tap] over the chunk's boards; grid (coT * ciT, chunks),
+// partial[chunk][co][ci][tap] over the chunk's `cb` boards; grid (coT * ciT, chunks),
 // 9 waves (wave = tap)
 constexpr int kGpStride = kMaxN * kMaxN + 3;            // gp row in LDS (cells, padded to a float4 of K)
 constexpr int kXPlane = (kMaxN + 2) * (kMaxN + 2);      // zero-haloed x plane in LDS
@@ -133,7 +133,7 @@ __global__ void __launch_bounds__(576) k_conv_bwd_weight(const float* __restrict
                                                          const float* __restrict__ x,
                                                          const int64_t* __restrict__ action,
                                                          const float* __restrict__ emb, float* __restrict__ part,
-                                                         int B, int Cin, int Cout, int N) {
+                                                         int B, int Cin, int Cout, int N, int cb) {
   __shared__ float gpl[16 * kGpStride];
   __shared__ float xl[16 * kXPlane];
   const int tid = threadIdx.x, lane = tid & 63, tap = tid >> 6;
@@ -146,8 +146,8 @@ __global__ void __launch_bounds__(576) k_conv_bwd_weight(const float* __restrict
   // zero halo of the x planes (interior rewritten per board) and the K pad of gp
   for (int j = tid; j < 16 * kXPlane; j += 576) xl[j] = 0.f;
   f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-  const int b1 = min(B, (chunk + 1) * kBwdChunk);
-  for (int b = chunk * kBwdChunk; b < b1; ++b) {
+  const int b1 = min(B, (chunk + 1) * cb);
+  for (int b = chunk * cb; b < b1; ++b) {
     __syncthreads();                                  // the previous board's reads are done
     // stage: gp rows of the 16 co, x planes of the 16 ci (row-contiguous loads)
     for (int j = tid; j < 16 * CELLS; j += 576) {
@@ -216,9 +216,13 @@ __global__ void __launch_bounds__(256) k_conv_bwd_bias(const float* __restrict__
   if (tid == 0) gb[co] = red[0];
 }
 
-size_t conv_bwd_workspace_bytes(int B, int Cin, int Cout) {
-  const size_t chunks = (size_t)(B + kBwdChunk - 1) / kBwdChunk;
+size_t conv_bwd_workspace_bytes_chunk(int B, int Cin, int Cout, int cb) {
+  const size_t chunks = (size_t)(B + cb - 1) / cb;
   return chunks * (size_t)Cout * Cin * 9 * sizeof(float);
+}
+
+size_t conv_bwd_workspace_bytes(int B, int Cin, int Cout) {
+  return conv_bwd_workspace_bytes_chunk(B, Cin, Cout, kBwdChunk);
 }
 
 hipError_t conv_forward(const float* x, const int64_t* action, const float* emb, const float* w, const float* bias,
@@ -229,21 +233,30 @@ hipError_t conv_forward(const float* x, const int64_t* action, const float* emb,
   return hipGetLastError();
 }
 
-hipError_t conv_backward(const float* g, const float* out, const float* x, const int64_t* action, const float* emb,
-                         const float* w, int B, int Cin, int Cout, int N, float* gx, float* gw, float* gb,
-                         void* workspace, hipStream_t s) {
+// conv_backward with `cb` boards per gw partial (the workspace holds
+// conv_bwd_workspace_bytes_chunk(B, Cin, Cout, cb)): the partials' order is
+// fixed by (B, cb) alone
+hipError_t conv_backward_chunk(const float* g, const float* out, const float* x, const int64_t* action,
+                               const float* emb, const float* w, int B, int Cin, int Cout, int N, int cb, float* gx,
+                               float* gw, float* gb, void* workspace, hipStream_t s) {
   const int CELLS = N * N;
-  const int chunks = (B + kBwdChunk - 1) / kBwdChunk;
+  const int chunks = (B + cb - 1) / cb;
   if (gx)
     hipLaunchKernelGGL(k_conv_bwd_input, dim3((CELLS + 15) / 16, (Cin + 15) / 16, B), dim3(64), 0, s, g, out, w, gx,
                        Cin, Cout, N);
   hipLaunchKernelGGL(k_conv_bwd_weight, dim3(((Cout + 15) / 16) * ((Cin + 15) / 16), chunks), dim3(576), 0, s, g,
-                     out, x, action, emb, static_cast<float*>(workspace), B, Cin, Cout, N);
+                     out, x, action, emb, static_cast<float*>(workspace), B, Cin, Cout, N, cb);
   const size_t n = (size_t)Cout * Cin * 9;
   hipLaunchKernelGGL(k_conv_bwd_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
                      static_cast<const float*>(workspace), gw, chunks, n);
   hipLaunchKernelGGL(k_conv_bwd_bias, dim3(Cout), dim3(256), 0, s, g, out, gb, B, Cout, N);
   return hipGetLastError();
+}
+
+hipError_t conv_backward(const float* g, const float* out, const float* x, const int64_t* action, const float* emb,
+                         const float* w, int B, int Cin, int Cout, int N, float* gx, float* gw, float* gb,
+                         void* workspace, hipStream_t s) {
+  return conv_backward_chunk(g, out, x, action, emb, w, B, Cin, Cout, N, kBwdChunk, gx, gw, gb, workspace, s);
 }
 
 }  // namespace mzgo

@@ -23,6 +23,42 @@ enum WeightKey {
   WK_COUNT
 };
 
+// Their state_dict keys and shapes (latent_dim C, A embedding rows): the one
+// table behind specs() (mzgo_capi.hip) and the unroll's parameter tables
+// (mzgo_unroll.hip)
+constexpr const char* kWeightKeyNames[] = {
+    "representation.conv1.weight", "representation.conv1.bias", "representation.conv2.weight",
+    "representation.conv2.bias", "representation.conv3.weight", "representation.conv3.bias",
+    "dynamics.action_embedding.weight", "dynamics.conv.weight", "dynamics.conv.bias",
+    "dynamics.reward_conv.weight", "dynamics.reward_conv.bias", "dynamics.fc_reward_hidden.weight",
+    "dynamics.fc_reward_hidden.bias", "dynamics.fc_reward_output.weight", "dynamics.fc_reward_output.bias",
+    "prediction.pass_logit", "prediction.value_conv.weight", "prediction.value_conv.bias",
+    "prediction.value_fc.weight", "prediction.value_fc.bias", "prediction.policy_conv.weight",
+    "prediction.policy_conv.bias"};
+static_assert(sizeof(kWeightKeyNames) / sizeof(kWeightKeyNames[0]) == WK_COUNT, "a name per WeightKey");
+
+struct WeightShape {
+  int nd;
+  long long d[4];
+};
+inline WeightShape weight_key_shape(int k, long long C, long long A) {
+  switch (k) {
+    case WK_CONV1_W: return {4, {64, 6, 3, 3}};
+    case WK_CONV2_W: return {4, {64, 64, 3, 3}};
+    case WK_CONV3_W: return {4, {C, 64, 3, 3}};
+    case WK_CONV1_B: case WK_CONV2_B: return {1, {64}};
+    case WK_CONV3_B: case WK_DYN_B: return {1, {C}};
+    case WK_EMB: return {2, {A, C}};
+    case WK_DYN_W: return {4, {C, C, 3, 3}};
+    case WK_REWARD_W: case WK_VALUE_W: case WK_POLICY_W: return {4, {1, C, 1, 1}};
+    case WK_FC1_W: return {2, {16, 1}};
+    case WK_FC1_B: return {1, {16}};
+    case WK_FC2_W: return {2, {1, 16}};
+    case WK_VFC_W: return {2, {1, 1}};
+    default: return {1, {1}};   // the scalar biases and pass_logit
+  }
+}
+
 // The blob's parts, in blob order
 enum WeightPart {
   WP_CONV1_W, WP_CONV1_B, WP_CONV2_W, WP_CONV2_B, WP_CONV3_W, WP_CONV3_B, WP_DYN_W, WP_DYN_B,

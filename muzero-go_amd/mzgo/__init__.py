@@ -17,6 +17,9 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
   symmetries) and reanalysis in place, without the games visiting the host
 * ``unroll_loss`` -- the trainer's value / policy / reward losses of a whole unroll, their
   per-sample sums and the heads' gradients from one kernel (``TrainConfig.fused_loss``)
+* ``unroll`` -- the trainer's whole K-step unroll (representation, dynamics chain, the heads of
+  every latent) as one autograd node: one HIP forward call, one backward call
+  (``TrainConfig.fused_unroll``)
 * ``mzgo.play`` -- play.py's interactive human-vs-agent loop (``python -m mzgo.play weights.pth``)
 """
 from ._lib import MzgoError
@@ -30,10 +33,11 @@ from .replay import DeviceReplay, queue_key_gids
 from .resnet import ResMuZeroNet
 from .search import MCTS, MainMCTS, MuZeroAgent
 from .selfplay import GameHistory, SelfPlay, history_from_device, save_batches
+from .unroll import unroll, unroll_heads_host
 from .weights import deterministic_res_state_dict, deterministic_state_dict
 
 __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "MuZeroAgent", "SelfPlay",
            "GameHistory", "history_from_device", "save_batches", "deterministic_state_dict", "SelfPlayEvaluator",
            "ResMuZeroNet", "deterministic_res_state_dict", "MzgoError", "Reanalyser",
            "positions_from_planes", "record_ids", "DeviceReplay", "queue_key_gids", "unroll_loss",
-           "unroll_loss_host"]
+           "unroll_loss_host", "unroll", "unroll_heads_host"]

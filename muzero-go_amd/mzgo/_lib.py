@@ -113,6 +113,11 @@ SIGNATURES = {
     "mzgo_replay_skipped_updates": (_I, [_P, _P, _P]),
     "mzgo_unroll_loss": (_I, [_P] * 6 + [_I] * 3 + [ctypes.c_float] * 3 + [_I] + [_P] * 6),
     "mzgo_unroll_loss_host": (_I, [_P] * 6 + [_I] * 3 + [ctypes.c_float] * 3 + [_I] + [_P] * 5),
+    "mzgo_unroll_workspace": (_I, [_I] * 5 + [ctypes.POINTER(ctypes.c_int64)] * 2),
+    "mzgo_unroll_forward": (_I, [_P] * 4 + [_I] + [_P] * 2 + [_I] * 5 + [_P, ctypes.c_int64] + [_P] * 4),
+    "mzgo_unroll_backward": (_I, [_P] * 5 + [_I] + [_P, ctypes.c_int64] + [_P] * 3 + [_I] * 5
+                             + [_P, ctypes.c_int64, _P]),
+    "mzgo_unroll_heads_host": (_I, [_P] * 5 + [_I] + [_P] + [_I] * 4 + [_P] * 7),
 }
 
 

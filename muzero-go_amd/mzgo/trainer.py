@@ -56,6 +56,16 @@ on the device, every game of a batch at once) and trains on it:
   a copy for the net's further engines) instead of 22 host copies and the
   host packers -- the same packed weights bit for bit.  A ``deferred_stats``
   step synchronises nowhere only with it.
+  ``TrainConfig.fused_unroll`` (default off) takes the heads' outputs of all
+  K + 1 steps from ``mzgo.unroll`` (csrc/mzgo_unroll.hip): the representation,
+  the K dynamics steps and every head are ONE autograd node whose forward is
+  one HIP call (K + 5 launches enqueued from C++) and whose backward is another
+  (K + 17) -- the 3x3 convs on the kernels ``hip_forward`` uses for its
+  backward, the heads and their backward on kernels that cover all K + 1
+  latents in one launch each -- instead of some forty torch ops per unroll
+  step.  The loss, the importance weights, the priorities and the device tail
+  are unchanged: ``fused_loss`` reads the stacked outputs as they come, the
+  torch loss ops read their slices.
 
 ``initial_inference_torch`` / ``recurrent_inference_torch`` restate
 main.py:72-144 with torch ops on the module's own parameters (reference
@@ -96,6 +106,7 @@ class TrainConfig:
     priority_alpha: float = 1.0       # device_sampling: a new priority is loss ** alpha
     deferred_stats: bool = False      # device_sampling: train() returns a device scalar; read_stats() fills last
     device_weights: bool = False      # the net's engines take new weights on the device (MuZeroNet.device_weights)
+    fused_unroll: bool = False        # batched mode: the whole unroll, heads included, on mzgo.unroll (one autograd node)
 
 
 def reward_value_transform(x, epsilon=0.001):
@@ -456,6 +467,21 @@ class MuZeroTrainer:
                              "(TrainConfig.device_sampling=True)")
         if c.importance_beta < 0 or not c.priority_alpha > 0:
             raise ValueError("importance_beta must be >= 0 and priority_alpha > 0")
+        if c.fused_unroll:
+            if not isinstance(net, MuZeroNet):
+                raise ValueError(f"fused_unroll runs the reference network (MuZeroNet) only, not {type(net).__name__}: "
+                                 "mzgo.unroll has no kernels for another architecture")
+            if mode != "batched":
+                raise ValueError("fused_unroll needs mode='batched': mode='reference' is main.py's per-trajectory "
+                                 "step, which unrolls one trajectory at a time")
+            if self.hip_forward:
+                raise ValueError("fused_unroll and hip_forward=True are two different HIP paths for the unroll "
+                                 "(one autograd node for all of it / one Function per conv layer): choose one")
+            if net.latent_dim < 16 or net.latent_dim % 16:
+                raise ValueError(f"fused_unroll needs latent_dim to be a multiple of 16, got {net.latent_dim}")
+            if next(net.parameters()).device.type != "cuda":
+                raise ValueError("fused_unroll needs the net on the GPU (net.to('cuda')): mzgo.unroll has no eager "
+                                 "fall-back")
         if c.device_weights:
             if next(net.parameters()).device.type != "cuda":
                 raise ValueError("device_weights needs the net on the GPU (net.to('cuda')): the engines' weights are "
@@ -746,18 +772,17 @@ class MuZeroTrainer:
             return self._unroll_step_fused(obs0, acts, t_val, t_rew, t_pol, device_sample)
         tot = (lambda x: x.detach().sum().double()) if device_totals else (lambda x: x.sum().item())
         self.optimizer.zero_grad()
-        fwd0, fwd = ((initial_inference_hip, recurrent_inference_hip) if self.hip_forward
-                     else (initial_inference_torch, recurrent_inference_torch))
-        latent, value, logits = fwd0(net, obs0)
+        steps = self._head_outputs(obs0, acts)
+        _, value, logits = next(steps)
         kl = lambda lg, tp: F.kl_div(F.log_softmax(lg, dim=1), tp, reduction="none").sum(dim=1)
-        v_l = c.value_loss_weight * self._value_loss(value.squeeze(1), t_val[:, 0])
+        v_l = c.value_loss_weight * self._value_loss(value, t_val[:, 0])
         p_l = c.policy_loss_weight * kl(logits, t_pol[:, 0])
         per = v_l + p_l
         tot_v, tot_p, tot_r = tot(v_l), tot(p_l), 0.0
         for k in range(1, K + 1):
-            latent, reward, value, logits = fwd(net, latent, acts[:, k - 1])
-            r_l = c.reward_loss_weight * F.mse_loss(reward.squeeze(1), t_rew[:, k - 1], reduction="none")
-            v_l = c.value_loss_weight * self._value_loss(value.squeeze(1), t_val[:, k])
+            reward, value, logits = next(steps)
+            r_l = c.reward_loss_weight * F.mse_loss(reward, t_rew[:, k - 1], reduction="none")
+            v_l = c.value_loss_weight * self._value_loss(value, t_val[:, k])
             p_l = c.policy_loss_weight * kl(logits, t_pol[:, k])
             per = per + r_l + v_l + p_l
             tot_r += tot(r_l)
@@ -786,6 +811,28 @@ class MuZeroTrainer:
                          reward_loss=tot_r / B, lr=self.optimizer.param_groups[0]["lr"])
         return total / B
 
+    def _head_outputs(self, obs0, acts):
+        """(reward [B] (None at k = 0), value [B], logits [B, A]) of the unroll's
+        steps k = 0..K, one at a time: from the per-step graph (torch's ops, or
+        ``hip_forward``'s Functions), or with ``fused_unroll`` as slices of
+        ``mzgo.unroll``'s stacked outputs (the whole unroll runs before the
+        first is yielded)."""
+        net = self.net
+        K = acts.shape[1]
+        if self.config.fused_unroll:
+            from .unroll import unroll
+            logits, value, reward = unroll(net, obs0, acts)
+            for k in range(K + 1):
+                yield (reward[k - 1] if k else None), value[k], logits[k]
+            return
+        fwd0, fwd = ((initial_inference_hip, recurrent_inference_hip) if self.hip_forward
+                     else (initial_inference_torch, recurrent_inference_torch))
+        latent, value, logits = fwd0(net, obs0)
+        yield None, value.squeeze(1), logits
+        for k in range(1, K + 1):
+            latent, reward, value, logits = fwd(net, latent, acts[:, k - 1])
+            yield reward.squeeze(1), value.squeeze(1), logits
+
     def _weighted(self, device_sample):
         """Whether the step's loss is the importance-weighted sum (the
         priorities and the reported totals stay unweighted)."""
@@ -793,7 +840,8 @@ class MuZeroTrainer:
 
     def _unroll_step_fused(self, obs0, acts, t_val, t_rew, t_pol, device_sample=None):
         """``_unroll_step`` with the loss on the HIP kernel: the K + 1 steps'
-        head outputs are collected and stacked once, ``mzgo.unroll_loss`` gives
+        head outputs are collected and stacked once (``fused_unroll``:
+        they come stacked from ``mzgo.unroll``), ``mzgo.unroll_loss`` gives
         ``per`` and the f64 totals in one call, and autograd enters the network
         through its saved head gradients.  One copy brings the totals (and,
         with ``sample_priorities``, the per-sample losses) back."""
@@ -801,17 +849,18 @@ class MuZeroTrainer:
         c, net = self.config, self.net
         B, K = acts.shape
         self.optimizer.zero_grad()
-        fwd0, fwd = ((initial_inference_hip, recurrent_inference_hip) if self.hip_forward
-                     else (initial_inference_torch, recurrent_inference_torch))
-        latent, value, logits = fwd0(net, obs0)
-        lgs, vals, rews = [logits], [value.squeeze(1)], []
-        for k in range(1, K + 1):
-            latent, reward, value, logits = fwd(net, latent, acts[:, k - 1])
-            lgs.append(logits)
-            vals.append(value.squeeze(1))
-            rews.append(reward.squeeze(1))
-        per, totals = unroll_loss(torch.stack(lgs), torch.stack(vals), torch.stack(rews) if rews else None,
-                                  t_pol, t_val, t_rew, value_loss_weight=c.value_loss_weight,
+        if c.fused_unroll:
+            from .unroll import unroll
+            lgs, vals, rews = unroll(net, obs0, acts)          # stacked as they come
+        else:
+            lgs, vals, rews = [], [], []
+            for reward, value, logits in self._head_outputs(obs0, acts):
+                lgs.append(logits)
+                vals.append(value)
+                if reward is not None:
+                    rews.append(reward)
+            lgs, vals, rews = torch.stack(lgs), torch.stack(vals), torch.stack(rews) if rews else None
+        per, totals = unroll_loss(lgs, vals, rews, t_pol, t_val, t_rew, value_loss_weight=c.value_loss_weight,
                                   policy_loss_weight=c.policy_loss_weight, reward_loss_weight=c.reward_loss_weight,
                                   value_transform=c.use_value_transform)
         loss = per.sum() if not self._weighted(device_sample) else (per * device_sample[1]["weight"]).sum()
