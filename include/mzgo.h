@@ -318,7 +318,9 @@ int mzgo_tower_timing(mzgo_engine* eng, int enable, double* tower_ms_host, int64
  * padding 1.  In: grad_out, out, latent [B][C][N][N] f32, action [B] i64,
  * emb [A][C], weight [C][C][3][3].  Out: grad_latent [B][C][N][N] (= the
  * conv input's gradient), grad_weight [C][C][3][3], grad_bias [C]; fp32 MFMA,
- * deterministic.  C a multiple of 16, 2 <= N <= 19; workspace of at least
+ * deterministic.  C a multiple of 16, 2 <= N <= 19, 1 <= B <= 65535 (the
+ * input gradient's launch has the batch in the grid's z dimension; a larger B
+ * is MZGO_EINVAL before any device work); workspace of at least
  * mzgo_dyn_conv_backward_workspace(B, C) bytes (device). */
 int mzgo_dyn_conv_backward_workspace(int B, int C, int64_t* bytes_host);
 int mzgo_dyn_conv_backward(const float* grad_out, const float* out, const float* latent, const int64_t* action,
@@ -335,8 +337,10 @@ int mzgo_dyn_conv_backward(const float* grad_out, const float* out, const float*
  * (may be NULL: the first layer), grad_weight [Cout][Cin][3][3], grad_bias
  * [Cout]; deterministic (fixed summation order).  Replaces
  * torch.nn.grad.conv2d_input / conv2d_weight in the trainer's autograd
- * Functions.  Any Cin, Cout >= 1; 2 <= N <= 19; device workspace of at least
- * mzgo_conv3x3_backward_workspace(B, Cin, Cout) bytes. */
+ * Functions.  Any Cin, Cout >= 1; 2 <= N <= 19; 1 <= B <= 65535 (the forward
+ * and the input gradient launch a grid with z = B: a larger batch is
+ * MZGO_EINVAL, naming the limit, before any device work); device workspace of
+ * at least mzgo_conv3x3_backward_workspace(B, Cin, Cout) bytes. */
 int mzgo_conv3x3_relu_forward(const float* x, const int64_t* action, const float* emb, const float* weight,
                               const float* bias, int B, int Cin, int Cout, int N, float* out, void* stream);
 int mzgo_conv3x3_backward_workspace(int B, int Cin, int Cout, int64_t* bytes_host);
@@ -716,7 +720,8 @@ int mzgo_unroll_loss_host(const float* logits, const float* value, const float* 
  *
  * MZGO_EINVAL, with the reason in mzgo_last_error(), before any device work:
  * B < 1; K < 0; C not a multiple of 16; N outside 2..19; emb_rows < N*N + 1;
- * (K + 1) B above 2^31 - 1; a null required pointer; a missing, duplicate or unexpected key or a shape
+ * (K + 1) B above 2^31 - 1; B above 65535 (the convs and the chain launch a
+ * grid with z = B); a null required pointer; a missing, duplicate or unexpected key or a shape
  * that is not the state_dict's; saved_bytes / work_bytes smaller than
  * mzgo_unroll_workspace reports. */
 int mzgo_unroll_workspace(int B, int K, int C, int N, int emb_rows, int64_t* saved_bytes, int64_t* work_bytes);

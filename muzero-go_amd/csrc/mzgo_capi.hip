@@ -22,6 +22,7 @@ extern const KernelSet kernels_n5_c96, kernels_n6_c96, kernels_n9_c96, kernels_n
     kernels_n6_c64;
 
 // the trainer's conv layers (mzgo_train.hip)
+extern const int kConvMaxBatch;
 size_t conv_bwd_workspace_bytes(int B, int Cin, int Cout);
 hipError_t conv_forward(const float* x, const int64_t* action, const float* emb, const float* w, const float* bias,
                         int B, int Cin, int Cout, int N, float* y, hipStream_t s);
@@ -1080,6 +1081,8 @@ int mzgo_dyn_conv_backward(const float* grad_out, const float* out, const float*
   if (!grad_out || !out || !latent || !action || !emb || !weight || !grad_latent || !grad_weight || !grad_bias ||
       !workspace || B < 1 || C < 16 || C % 16 || N < 2 || N > 19)
     return fail(MZGO_EINVAL, "bad argument (B=%d, C=%d, N=%d)", B, C, N);
+  if (B > kConvMaxBatch)
+    return fail(MZGO_EINVAL, "mzgo_dyn_conv_backward: B = %d exceeds the launch grid's z limit of %d", B, kConvMaxBatch);
   if (workspace_bytes < (int64_t)conv_bwd_workspace_bytes(B, C, C))
     return fail(MZGO_EINVAL, "workspace too small: %lld < %lld bytes", (long long)workspace_bytes,
                 (long long)conv_bwd_workspace_bytes(B, C, C));
@@ -1092,6 +1095,9 @@ int mzgo_conv3x3_relu_forward(const float* x, const int64_t* action, const float
                               const float* bias, int B, int Cin, int Cout, int N, float* out, void* stream) {
   if (!x || !weight || !bias || !out || (emb && !action) || B < 1 || Cin < 1 || Cout < 1 || N < 2 || N > 19)
     return fail(MZGO_EINVAL, "bad argument (B=%d, Cin=%d, Cout=%d, N=%d)", B, Cin, Cout, N);
+  if (B > kConvMaxBatch)
+    return fail(MZGO_EINVAL, "mzgo_conv3x3_relu_forward: B = %d exceeds the launch grid's z limit of %d", B,
+                kConvMaxBatch);
   HIPCHK(conv_forward(x, action, emb, weight, bias, B, Cin, Cout, N, out, (hipStream_t)stream));
   return MZGO_OK;
 }
@@ -1110,6 +1116,8 @@ int mzgo_conv3x3_backward(const float* grad_out, const float* out, const float* 
   if (!grad_out || !out || !x || (emb && !action) || !weight || !grad_weight || !grad_bias || !workspace || B < 1 ||
       Cin < 1 || Cout < 1 || N < 2 || N > 19)
     return fail(MZGO_EINVAL, "bad argument (B=%d, Cin=%d, Cout=%d, N=%d)", B, Cin, Cout, N);
+  if (B > kConvMaxBatch)
+    return fail(MZGO_EINVAL, "mzgo_conv3x3_backward: B = %d exceeds the launch grid's z limit of %d", B, kConvMaxBatch);
   if (workspace_bytes < (int64_t)conv_bwd_workspace_bytes(B, Cin, Cout))
     return fail(MZGO_EINVAL, "workspace too small: %lld < %lld bytes", (long long)workspace_bytes,
                 (long long)conv_bwd_workspace_bytes(B, Cin, Cout));

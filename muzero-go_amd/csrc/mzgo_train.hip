@@ -39,6 +39,9 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kBwdChunk = 8;   // boards per gw partial (a chunk's K = 8 x cells); a caller may ask for more
 constexpr int kMaxN = 19;
+// k_conv_fwd, k_conv_bwd_input (and mzgo_unroll.hip's k_unroll_chain) put the batch in gridDim.z: HIP's
+// portable limit of that dimension.  The entry points refuse a larger batch before any launch.
+extern const int kConvMaxBatch = 65535;
 
 // gp at (b, co, cell (y, x)) or 0 off the board
 __device__ __forceinline__ float masked_grad(const float* __restrict__ g, const float* __restrict__ out,

@@ -41,6 +41,7 @@
 
 namespace mzgo {
 // mzgo_train.hip
+extern const int kConvMaxBatch;
 size_t conv_bwd_workspace_bytes(int B, int Cin, int Cout);
 size_t conv_bwd_workspace_bytes_chunk(int B, int Cin, int Cout, int cb);
 hipError_t conv_forward(const float* x, const int64_t* action, const float* emb, const float* w, const float* bias,
@@ -123,6 +124,8 @@ int check_dims(const char* fn, int B, int K, int C, int N, int emb_rows) {
     return set_error(MZGO_EINVAL, "%s: emb_rows %d < N*N + 1 = %d actions", fn, emb_rows, N * N + 1);
   if (((int64_t)K + 1) * B > INT32_MAX)                  // a workgroup per (step, sample); int indices
     return set_error(MZGO_EINVAL, "%s: (K + 1) B = %lld exceeds 2^31 - 1", fn, (long long)(((int64_t)K + 1) * B));
+  if (B > kConvMaxBatch)                                 // the convs and the chain launch a grid with z = B
+    return set_error(MZGO_EINVAL, "%s: B = %d exceeds the launch grid's z limit of %d", fn, B, kConvMaxBatch);
   return MZGO_OK;
 }
 

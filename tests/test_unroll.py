@@ -174,7 +174,10 @@ def _backward(B=2, K=1, C=16, N=5, emb_rows=26, saved_bytes=None, work_bytes=Non
 
 DIM_REFUSALS = [(dict(B=0), "B must be >= 1"), (dict(K=-1), "K must be >= 0"), (dict(C=24), "multiple of 16"),
                 (dict(C=0), "multiple of 16"), (dict(N=1), "N 1 out of range (2..19)"),
-                (dict(N=20), "N 20 out of range (2..19)"), (dict(emb_rows=25), "emb_rows 25 < N*N + 1 = 26")]
+                (dict(N=20), "N 20 out of range (2..19)"), (dict(emb_rows=25), "emb_rows 25 < N*N + 1 = 26"),
+                # the convs and the chain put the batch in the launch grid's z dimension
+                (dict(B=65536), "B = 65536 exceeds the launch grid's z limit of 65535"),
+                (dict(B=1 << 20, K=0), "B = 1048576 exceeds the launch grid's z limit of 65535")]
 
 
 def test_workspace_sizes_and_refusals():
@@ -238,6 +241,34 @@ def test_backward_refusals():
     for over, text in cases:
         rc, msg = _backward(**over)
         assert rc == _lib.MZGO_EINVAL and text in msg and "mzgo_unroll_backward" in msg, (over, msg)
+
+
+def test_batch_above_the_grid_limit_is_refused_before_any_launch():
+    """k_conv_fwd, k_conv_bwd_input and k_unroll_chain launch a grid with z =
+    B: 65536 boards are MZGO_EINVAL from the unroll and from the three layer
+    entry points, 65535 pass that check (and fail a later one here)."""
+    from mzgo import _lib
+    lib, EINVAL = _lib.lib, _lib.MZGO_EINVAL
+    buf = np.zeros(16, np.float32)                        # never dereferenced: every call here is refused
+    p = _lib.ptr(buf)
+    limit = "exceeds the launch grid's z limit of 65535"
+    rc = lib.mzgo_conv3x3_relu_forward(p, None, None, p, p, 65536, 6, 64, 5, p, None)
+    assert rc == EINVAL and b"mzgo_conv3x3_relu_forward: B = 65536 " + limit.encode() in lib.mzgo_last_error()
+    rc = lib.mzgo_conv3x3_relu_forward(p, p, p, p, p, 1 << 30, 16, 16, 2, p, None)
+    assert rc == EINVAL and limit.encode() in lib.mzgo_last_error()
+    rc = lib.mzgo_conv3x3_backward(p, p, p, None, None, p, 65536, 6, 64, 5, None, p, p, p, 1 << 40, None)
+    assert rc == EINVAL and b"mzgo_conv3x3_backward: B = 65536 " + limit.encode() in lib.mzgo_last_error()
+    rc = lib.mzgo_dyn_conv_backward(p, p, p, p, p, p, 65536, 16, 5, p, p, p, p, 1 << 40, None)
+    assert rc == EINVAL and b"mzgo_dyn_conv_backward: B = 65536 " + limit.encode() in lib.mzgo_last_error()
+    # one board fewer is not refused for its batch: the next check is the workspace's size
+    rc = lib.mzgo_conv3x3_backward(p, p, p, None, None, p, 65535, 6, 64, 5, None, p, p, p, 64, None)
+    assert rc == EINVAL and b"workspace too small: 64 <" in lib.mzgo_last_error()
+    rc = lib.mzgo_dyn_conv_backward(p, p, p, p, p, p, 65535, 16, 5, p, p, p, p, 64, None)
+    assert rc == EINVAL and b"workspace too small: 64 <" in lib.mzgo_last_error()
+    rc, msg = _forward(B=65535, saved_bytes=64)
+    assert rc == EINVAL and "saved too small: 64 <" in msg
+    rc, msg = _backward(B=65535, work_bytes=128, saved_bytes=1 << 40)
+    assert rc == EINVAL and "work too small: 128 <" in msg
 
 
 def test_heads_host_refusals():
