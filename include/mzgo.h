@@ -574,6 +574,45 @@ int mzgo_replay_sample_batch(mzgo_replay* replay, int B, int unroll_steps, doubl
                              uint32_t step, int symmetries, double beta, int32_t* items, int32_t* index,
                              uint32_t* gen, float* weight, float* obs0, float* boot_obs, int64_t* acts, float* t_rew,
                              float* t_pol, double* val, double* factor, uint8_t* has_boot, void* stream);
+/* k_replay_batch on device items the caller holds (i32 [B][3]: slot, start,
+ * symmetry, as mzgo_replay_sample wrote them): the second half of
+ * mzgo_replay_sample_batch, so that a reanalysis of the sampled windows can
+ * run between the draw and the assembly.  The items are not checked (they
+ * are the sampler's).  No host staging, no synchronisation.  MZGO_EINVAL:
+ * null replay, items or outputs; B < 1; unroll_steps outside 1..63. */
+int mzgo_replay_batch_items(mzgo_replay* replay, const int32_t* items, int B, int unroll_steps, double discount,
+                            float* obs0, float* boot_obs, int64_t* acts, float* t_rew, float* t_pol, double* val,
+                            double* factor, uint8_t* has_boot, void* stream);
+/* Reanalysis of a sampled batch's windows, in place and without the host.  A
+ * sample (slot, start, symmetry) with K = unroll_steps on a game of L moves
+ * reads the stored policy rows t = start .. min(start + K, L - 1) (rows past
+ * the end are the uniform row and are not stored): its window.  A triple whose
+ * slot is outside 0..capacity-1, whose game has L <= 0 or whose start is
+ * outside 0..L-1 has none.  The call enqueues, in order: k_replay_window_items
+ * (one workgroup, no atomics) writing every (slot, t) of every window by
+ * falling t, equal t by batch position, and their count n into memory the
+ * store owns (and n into *n_searched unless NULL); a memset of the engine's
+ * queue head; and the in-place reanalysis queue on min(B (K + 1), CUs, tree
+ * slots) workgroups, which searches exactly those n positions under ``eng``'s
+ * weights and search parameters -- position t of a game keyed (seed, key_gid,
+ * t), as mzgo_replay_reanalyse keys it -- reading each position from the
+ * store's rows and writing the visit-count policy row and the root value into
+ * the store's.  Rows outside the windows, and every other field, stay as they
+ * are.  No index, position or policy crosses the bus; no synchronisation
+ * (after the first call of a size, which allocates the list).  Calls on one
+ * store or engine must be ordered.
+ * MZGO_EINVAL: null replay, engine or items; B < 1; unroll_steps outside
+ * 1..63; board-size mismatch; a board-only engine; a tower engine.
+ * MZGO_ENOWEIGHTS as mzgo_search. */
+int mzgo_replay_reanalyse_sample(mzgo_replay* replay, mzgo_engine* eng, const int32_t* items, int B,
+                                 int unroll_steps, int32_t* n_searched, void* stream);
+/* The window rule's host twin (no device work; csrc/mzgo_replay.hpp's functions
+ * run serially): length i32 [cap] in slot order, items i32 [B][3]; out i32
+ * [B (K + 1)][2] receives the (slot, t) list in the order above and *n its
+ * length.  MZGO_EINVAL: a null pointer; cap < 1; B < 1; unroll_steps outside
+ * 1..63. */
+int mzgo_replay_window_items_host(const int32_t* length, int cap, const int32_t* items, int B, int unroll_steps,
+                                  int32_t* out, int32_t* n);
 /* The sampler's host twin (no device work): prio f64 [cap] and length i32
  * [cap] in slot order, ``head`` the slot of logical game 0; host outputs
  * items, index and (unless NULL) weight as above.  MZGO_EINVAL: a null

@@ -991,6 +991,23 @@ int mzgo::engine_play_games(mzgo_engine* e, const GamesArgs& ga, hipStream_t s) 
   return MZGO_OK;
 }
 
+// the device replay store's window reanalysis (mzgo_replay_reanalyse_sample, mzgo_replay.hip):
+// mzgo_reanalyse's schedule, the item count known to the device only (the caller
+// has refused board-only and tower engines)
+int mzgo::engine_reanalyse_store(mzgo_engine* e, const ReanalyseStoreArgs& ra_arg, int max_items, hipStream_t s) {
+  int rc = e->sync_weights();
+  if (rc) return rc;
+  const SearchParams sp = e->search_params();          // (self-play's row laziness; no helpers, network 0)
+  const int ncu = device_cus();
+  int wg = ncu > 0 && ncu < e->TS ? ncu : e->TS;       // one tree slot per workgroup
+  if (max_items < wg) wg = max_items;
+  ReanalyseStoreArgs ra = ra_arg;
+  ra.head = e->rq_head;
+  HIPCHK(hipMemsetAsync(e->rq_head, 0, sizeof(unsigned), s));
+  HIPCHK(e->ks->reanalyse_store(e->np, sp, e->E, ra, wg, s));
+  return MZGO_OK;
+}
+
 extern "C" {
 
 int mzgo_selfplay_move(mzgo_engine* e, void* stream) { return mzgo_selfplay_moves(e, 1, stream); }

@@ -31,6 +31,8 @@ struct KernelSet {
                              int G, int workgroups, hipStream_t);
   hipError_t (*reanalyse)(const NetParams& np, const SearchParams&, const EngineArrays&, const ReanalyseArgs&,
                           int workgroups, hipStream_t);
+  hipError_t (*reanalyse_store)(const NetParams& np, const SearchParams&, const EngineArrays&,
+                                const ReanalyseStoreArgs&, int workgroups, hipStream_t);
   hipError_t (*selfplay_games)(const NetParams& np, const SearchParams&, const PlayParams&, const EngineArrays&,
                                const GamesArgs&, int workgroups, hipStream_t);
 };
@@ -91,6 +93,11 @@ struct Launch {
     hipLaunchKernelGGL((k_reanalyse_queue<N, C>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, E, ra);
     return hipGetLastError();
   }
+  static hipError_t reanalyse_store(const NetParams& np, const SearchParams& sp, const EngineArrays& E,
+                                    const ReanalyseStoreArgs& ra, int workgroups, hipStream_t s) {
+    hipLaunchKernelGGL((k_reanalyse_queue<N, C, true>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, E, ra);
+    return hipGetLastError();
+  }
   static hipError_t games(const NetParams& np, const SearchParams& sp, const PlayParams& pp, const EngineArrays& E,
                           const GamesArgs& ga, int workgroups, hipStream_t s) {
     hipLaunchKernelGGL((k_selfplay_games<N, C>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, pp, E, ga);
@@ -103,7 +110,7 @@ struct Launch {
                      G::TREE_CAP > 0 && decltype(Smem<G>::u.f)::BATCH && decltype(Smem<G>::u.f)::CACHE ? G::TREE_CAP : 0,
                      &ii, &ri, &search, &breset, &bstep,
                      &bplanes,
-                     &move, &boards, &queue, &reanalyse, &games};
+                     &move, &boards, &queue, &reanalyse, &reanalyse_store, &games};
   }
 };
 

@@ -2004,14 +2004,62 @@ struct ReanalyseArgs {
   double* policy;          // [n][A], or null
 };
 
-template <int N, int C>
+// ---------------------------------------------------------------------------
+// INPLACE (mzgo_replay_reanalyse_sample): the items are rows of the device
+// replay store, ReanalyseStoreArgs (mzgo_replay.hpp).  Item i = (slot, t) of
+// the list a launch before this one built, whose length is a device word: the
+// grid is the host's upper bound, and a workgroup that claims i >= *n leaves.
+// The position is read from the store's own rows, the key is (seed,
+// key_gid[slot], t) -- mzgo_replay_reanalyse's for the same position -- and the
+// policy row and root value go straight into the store's: no visits, no
+// staging.  A search reads position rows and writes policy and value rows,
+// never the other way round, so distinct items share nothing; the queue head
+// stays the only word two workgroups touch.
+// ---------------------------------------------------------------------------
+template <int N, int C, bool INPLACE = false>
 __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_waves_per_eu(Geo<N, C>::WPE, Geo<N, C>::WPE))) k_reanalyse_queue(NetParams np_arg, SearchParams sp,
-                                                               EngineArrays E_arg, ReanalyseArgs ra) {
+                                                               EngineArrays E_arg, typename std::conditional<INPLACE, ReanalyseStoreArgs, ReanalyseArgs>::type ra) {
   typedef Geo<N, C> G;
   __shared__ Smem<G> sm;
   static_assert(sizeof(Smem<G>) <= 160 * 1024, "one workgroup per CU: the whole LDS at most");
   if constexpr (G::WINO) wino_raw_zero<G>(sm.raw);        // zero halo of the conv input planes
   const int slot = blockIdx.x;
+  if constexpr (INPLACE) {
+    for (;;) {
+      if (tid_local() == 0) sm.bc[0] = (int)atomicAdd(ra.head, 1u);
+      __syncthreads();
+      const int i = sm.bc[0];
+      __syncthreads();                             // (sm.bc is the search's scratch too)
+      if (i >= *launder_global(ra.n)) break;
+      const EngineArrays E = launder_arrays(E_arg);
+      const NetParams np = launder_params(np_arg);
+      const int* it = launder_global(ra.items) + 2 * (size_t)i;
+      const int rs = it[0], t = it[1];             // ring slot, move
+      const size_t q = (size_t)rs * (ra.R.M + 1) + t;
+      const int8_t* st = launder_global(ra.R.stones) + q * G::CELLS;
+      const uint8_t* iv = launder_global(ra.R.invd) + q * G::CELLS;
+      for (int c = tid_local(); c < G::CELLS; c += G::THREADS) {
+        sm.stone[c] = st[c];
+        sm.invd[c] = iv[c];
+      }
+      const BoardMeta m0 = flags_unpack(launder_global(ra.R.flags)[q], t);
+      __syncthreads();
+      const uint64_t key = stream_key(sp.seed, (uint32_t)launder_global(ra.R.key_gid)[rs], (uint32_t)t);
+      SearchParams spm = launder_search(sp);
+      spm.net = 0;
+      spm.helpers = 0;
+      run_search<G>(sm, np, spm, E, slot, [&](int c, int jj) { return board_plane<G>(sm.stone, sm.invd, m0, c, jj); },
+                    nullptr, key);
+      const TreeView T = TreeViewOf<G>::make(E, slot);
+      const size_t o = (size_t)rs * ra.R.M + t;
+      if (tid_local() == 0) launder_global(ra.R.root_value)[o] = root_value(T);
+      if (wave_id() == 0) {
+        double vc[G::AP], msum;
+        visit_policy<G>(sm.t, T, sp.variant, 1, launder_global(ra.R.policy) + o * G::A, vc, msum);
+      }
+      __syncthreads();                             // this search's LDS reads before the next board
+    }
+  } else
   for (;;) {
     if (tid_local() == 0) sm.bc[0] = (int)atomicAdd(ra.head, 1u);
     __syncthreads();

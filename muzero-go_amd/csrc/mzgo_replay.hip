@@ -10,7 +10,9 @@
 // opts for the device ledger (a weight and a generation per slot) and its
 // sampler further down: successive sampling without replacement from a 64-ary
 // sum tree (k_replay_sample_build, k_replay_sample_draw), batches assembled
-// from the sampler's device items, priorities written back by a launch.
+// from the sampler's device items, priorities written back by a launch -- and,
+// between the draw and the assembly, the sampled windows' positions searched
+// again in place (k_replay_window_items, then the engine's in-place queue).
 //
 // Kernels here use plain vector loads and stores only (and one vector atomic,
 // the count of refused priority updates); workgroups never communicate.  Compiled with -ffp-contract=off like every unit: the value
@@ -172,6 +174,64 @@ __global__ void __launch_bounds__(64) k_replay_scatter(Store R, const int* items
 }
 
 // ---------------------------------------------------------------------------
+// The item list of a sampled batch's windows (mzgo_replay.hpp: window_rows,
+// window_has), latest first, built where the sampler left its triples.  One
+// workgroup and no atomics: thread t % 256 owns move t, counts the windows
+// that hold it, takes the sum of the later moves' counts as its first index and
+// writes its (slot, t) pairs in batch order -- the list is a function of the
+// inputs alone.  The B windows pass through LDS 256 at a time.
+//   cnt [2][M]   scratch: the counts, then each move's next free index
+//   out [B (K + 1)][2], n_out [1]; n_copy: a second word for the count, or null
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) k_replay_window_items(Store R, const int* items, int B, int K, int* cnt,
+                                                                  int* out, int* n_out, int* n_copy) {
+  __shared__ int w_slot[kThreads], w_start[kThreads], w_rows[kThreads];
+  const int tid = threadIdx.x, M = R.M;
+  int* next = cnt + M;
+  for (int t = tid; t < M; t += kThreads) cnt[t] = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int b0 = 0; b0 < B; b0 += kThreads) {
+      const int nb = min(kThreads, B - b0);
+      __syncthreads();                                     // (the chunk before: every thread has read it)
+      if (tid < nb) {
+        const int slot = items[3 * (b0 + tid)], start = items[3 * (b0 + tid) + 1];
+        w_slot[tid] = slot;
+        w_start[tid] = start;
+        w_rows[tid] = window_rows(R.length, R.cap, slot, start, K);
+      }
+      __syncthreads();
+      for (int t = tid; t < M; t += kThreads) {            // (a game holds at most M moves: t < M)
+        if (pass == 0) {
+          int c = cnt[t];
+          for (int i = 0; i < nb; ++i) c += window_has(w_start[i], w_rows[i], t);
+          cnt[t] = c;
+        } else {
+          int at = next[t];
+          for (int i = 0; i < nb; ++i)
+            if (window_has(w_start[i], w_rows[i], t)) {
+              out[2 * (size_t)at] = w_slot[i];
+              out[2 * (size_t)at + 1] = t;
+              ++at;
+            }
+          next[t] = at;
+        }
+      }
+    }
+    if (pass == 1) break;
+    __syncthreads();                                       // every move's count, workgroup-wide
+    for (int t = tid; t < M; t += kThreads) {
+      int first = 0;
+      for (int u = t + 1; u < M; ++u) first += cnt[u];
+      next[t] = first;
+      if (t == 0) {
+        *n_out = first + cnt[0];
+        if (n_copy) *n_copy = first + cnt[0];
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // The priority ledger.  New games: weight 1.0 and the slot's generation + 1,
 // a thread per game, after the launch (or copies) that wrote them.
 // ---------------------------------------------------------------------------
@@ -318,6 +378,11 @@ struct mzgo_replay {
   void* stage = nullptr;
   size_t stage_bytes = 0;
   unsigned* games_q = nullptr;            // mzgo_replay_play_games: the queue head, then the error word
+  // mzgo_replay_reanalyse_sample: the window items' count, the builder's scratch [2][M], the list (grown on demand)
+  int* win_n = nullptr;
+  int* win_cnt = nullptr;
+  int* win_items = nullptr;
+  size_t win_cap = 0;                     // pairs win_items holds
   Ledger L{};                             // device priorities, generations and the sampler's scratch
   int n_valid = 0;                        // slots whose mirrored length is > 0 (the sampler's population)
 
@@ -348,6 +413,7 @@ struct mzgo_replay {
     if (d_items) (void)hipFree(d_items);
     if (h_items) (void)hipHostFree(h_items);
     if (stage) (void)hipFree(stage);
+    if (win_items) (void)hipFree(win_items);
     if (items_read) (void)hipEventDestroy(items_read);
   }
 
@@ -408,6 +474,8 @@ int mzgo_replay_create(int board_size, int capacity, int max_moves, int device, 
   chk(r->alloc(&R.length, cap));
   chk(r->alloc(&R.key_gid, cap));
   chk(r->alloc(&r->games_q, 2));
+  chk(r->alloc(&r->win_n, 1));
+  chk(r->alloc(&r->win_cnt, 2 * M));
   Ledger& L = r->L;
   L.cap = capacity;
   L.n1 = (capacity + 63) / 64;
@@ -686,6 +754,83 @@ int mzgo_replay_reanalyse(mzgo_replay* r, mzgo_engine* eng, const int32_t* games
   RHIPCHK(hipGetLastError());
   if (int rc = mzgo_reanalyse(eng, st, iv, fl, ids, nullptr, (int)n, visits, value, policy, stream)) return rc;
   hipLaunchKernelGGL(k_replay_scatter, dim3((unsigned)n), dim3(64), 0, s, r->R, r->d_items, policy, value);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+int mzgo_replay_window_items_host(const int32_t* length, int cap, const int32_t* items, int B, int unroll_steps,
+                                  int32_t* out, int32_t* n) {
+  const char* who = "mzgo_replay_window_items_host";
+  if (!length || !items || !out || !n)
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !length ? "length" : !items ? "items" : !out ? "out" : "n");
+  if (cap < 1) return set_error(MZGO_EINVAL, "%s: capacity must be >= 1, got %d", who, cap);
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
+  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (1..%d)", who, unroll_steps, kMaxUnroll);
+  std::vector<int> rows((size_t)B);
+  int t_max = -1;
+  for (int b = 0; b < B; ++b) {
+    rows[b] = window_rows(length, cap, items[3 * b], items[3 * b + 1], unroll_steps);
+    if (rows[b] > 0) t_max = std::max(t_max, items[3 * b + 1] + rows[b] - 1);
+  }
+  int at = 0;
+  for (int t = t_max; t >= 0; --t)
+    for (int b = 0; b < B; ++b)
+      if (window_has(items[3 * b + 1], rows[b], t)) {
+        out[2 * at] = items[3 * b];
+        out[2 * at + 1] = t;
+        ++at;
+      }
+  *n = at;
+  return MZGO_OK;
+}
+
+int mzgo_replay_reanalyse_sample(mzgo_replay* r, mzgo_engine* eng, const int32_t* items, int B, int unroll_steps,
+                                 int32_t* n_searched, void* stream) {
+  const char* who = "mzgo_replay_reanalyse_sample";
+  if (!r || !eng || !items)
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !r ? "replay" : !eng ? "engine" : "items");
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
+  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (1..%d)", who, unroll_steps, kMaxUnroll);
+  ReplayEngineView E;
+  replay_engine_view(eng, &E);
+  if (E.N != r->R.N) return set_error(MZGO_EINVAL, "%s: board size mismatch (store %d, engine %d)", who, r->R.N, E.N);
+  if (E.latent_dim == 0) return set_error(MZGO_EINVAL, "%s: board-only engine (latent_dim 0) has no network", who);
+  if (E.tower) return set_error(MZGO_EINVAL, "%s: tower engines (tower = 1) are not supported", who);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t most = (size_t)B * (unroll_steps + 1);     // the host's bound on the list
+  if (most > r->win_cap) {
+    RHIPCHK(hipStreamSynchronize(s));                      // (a launch may still read the list)
+    if (r->win_items) RHIPCHK(hipFree(r->win_items));
+    r->win_items = nullptr;
+    r->win_cap = 0;
+    RHIPCHK(hipMalloc((void**)&r->win_items, most * 2 * sizeof(int)));
+    r->win_cap = most;
+  }
+  hipLaunchKernelGGL(k_replay_window_items, dim3(1), dim3(kThreads), 0, s, r->R, items, B, unroll_steps, r->win_cnt,
+                     r->win_items, r->win_n, n_searched);
+  RHIPCHK(hipGetLastError());
+  // (an engine without weights is refused below: the builder wrote the store's scratch only)
+  const ReanalyseStoreArgs ra{r->win_items, r->win_n, nullptr, r->R};
+  return engine_reanalyse_store(eng, ra, (int)std::min<size_t>(most, 1u << 30), s);
+}
+
+int mzgo_replay_batch_items(mzgo_replay* r, const int32_t* items, int B, int unroll_steps, double discount,
+                            float* obs0, float* boot_obs, int64_t* acts, float* t_rew, float* t_pol, double* val,
+                            double* factor, uint8_t* has_boot, void* stream) {
+  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_batch_items: null replay");
+  if (B < 1) return set_error(MZGO_EINVAL, "mzgo_replay_batch_items: B must be >= 1, got %d", B);
+  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "mzgo_replay_batch_items: unroll_steps %d out of range (1..%d)", unroll_steps,
+                     kMaxUnroll);
+  if (!items || !obs0 || !boot_obs || !acts || !t_rew || !t_pol || !val || !factor || !has_boot)
+    return set_error(MZGO_EINVAL, "mzgo_replay_batch_items: null %s",
+                     !items ? "items" : !obs0 ? "obs0" : !boot_obs ? "boot_obs" : !acts ? "acts" : !t_rew ? "t_rew"
+                     : !t_pol ? "t_pol" : !val ? "val" : !factor ? "factor" : "has_boot");
+  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot};
+  hipLaunchKernelGGL(k_replay_batch, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, r->R, items, unroll_steps,
+                     discount, O);
   RHIPCHK(hipGetLastError());
   return MZGO_OK;
 }

@@ -4,7 +4,9 @@
 // ring's arrays and the ingest of one game (a device function: the store's
 // own ingest kernel and k_selfplay_games run the same text), the device
 // priority ledger and the sampler's order of additions, descent rule and
-// fallback (host and device: the sampler's host twin runs them), and the engine's
+// fallback (host and device: the sampler's host twin runs them), the window
+// of a sample and the item list of a batch's windows (host and device
+// likewise) with the in-place reanalysis queue's arguments, and the engine's
 // side of the store's engine-facing calls (mzgo_capi.hip owns struct
 // mzgo_engine and the thread-local error string).
 #pragma once
@@ -136,6 +138,41 @@ struct GamesArgs {
 };
 
 // ---------------------------------------------------------------------------
+// The window of a sample (slot, start, symmetry) under K unroll steps: the
+// stored policy rows k_replay_batch reads for it, t = start .. min(start + K,
+// L - 1) with L = length[slot] (rows past the game's end are the uniform row
+// and are not stored).  A triple whose slot is outside 0 .. cap - 1, whose game
+// is empty (L <= 0) or whose start is outside 0 .. L - 1 has no window.  The
+// item list of a batch is every (slot, t) of every window by falling t, equal
+// t by batch position b: latest first (mzgo.reanalyse.latest_first), the order
+// mzgo_replay_reanalyse queues whole games in.  Host and device: the builder
+// kernel (k_replay_window_items) and its host twin run these.
+// ---------------------------------------------------------------------------
+// the window's rows (its first is ``start``); 0 = the triple contributes nothing
+__host__ __device__ __forceinline__ int window_rows(const int* length, int cap, int slot, int start, int K) {
+  if (slot < 0 || slot >= cap) return 0;
+  const int L = length[slot];
+  if (L <= 0 || start < 0 || start >= L) return 0;
+  const int last = start + K < L - 1 ? start + K : L - 1;
+  return last - start + 1;
+}
+// whether row t belongs to the window of ``rows`` rows from ``start`` (rows > 0: 0 <= start)
+__host__ __device__ __forceinline__ bool window_has(int start, int rows, int t) {
+  return rows > 0 && t >= start && t - start < rows;
+}
+
+// One mzgo_replay_reanalyse_sample call: the in-place form of the reanalysis
+// queue (k_reanalyse_queue<N, C, true>, mzgo_kernels.hpp).  Item i is row
+// items[i][1] of ring slot items[i][0]: the position is read from R's rows, the
+// fresh policy row and root value are written into R's.
+struct ReanalyseStoreArgs {
+  const int* items;  // [*n][2] (slot, t): k_replay_window_items' list
+  const int* n;      // the list's length, a device word
+  unsigned* head;    // the queue head (zeroed before the launch)
+  Store R;
+};
+
+// ---------------------------------------------------------------------------
 // The device priority ledger and its sampler (mzgo_replay.hip: k_replay_sample_*,
 // k_replay_update_priorities; mzgo.h: mzgo_replay_sample).  Kept apart from
 // Store, which the ingest and self-play kernels take by value.
@@ -218,6 +255,11 @@ bool engine_noise_hooked(const mzgo_engine* eng);
 // mzgo_capi.hip: enqueue k_selfplay_games for ga (head and error are set here)
 // and move the engine's epoch to the last one the call plays
 int engine_play_games(mzgo_engine* eng, const GamesArgs& ga, hipStream_t s);
+// mzgo_capi.hip: enqueue the in-place reanalysis queue for ra (the head is set
+// here) on min(max_items, CUs, tree slots) workgroups, after the weights'
+// upload if one is due (MZGO_ENOWEIGHTS as mzgo_search); a reference-network
+// engine only (the caller refuses the others)
+int engine_reanalyse_store(mzgo_engine* eng, const ReanalyseStoreArgs& ra, int max_items, hipStream_t s);
 // mzgo_capi.hip: set mzgo_last_error()'s text and return ``code``
 int set_error(int code, const char* fmt, ...);
 

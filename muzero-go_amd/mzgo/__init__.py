@@ -14,7 +14,9 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
 * ``Reanalyser``, ``Engine.reanalyse`` -- stored positions searched again under the
   current weights, from one device work queue (fresh policy targets for a trainer)
 * ``DeviceReplay`` -- finished games kept in HBM: the trainer's batches (with board
-  symmetries) and reanalysis in place, without the games visiting the host
+  symmetries) and reanalysis in place, without the games visiting the host -- whole games
+  (``reanalyse``) or exactly the rows a drawn sample reads (``reanalyse_sample``,
+  ``TrainConfig.reanalyse_sample``; ``window_items_host`` states the rule on the host)
 * ``unroll_loss`` -- the trainer's value / policy / reward losses of a whole unroll, their
   per-sample sums and the heads' gradients from one kernel (``TrainConfig.fused_loss``)
 * ``unroll`` -- the trainer's whole K-step unroll (representation, dynamics chain, the heads of
@@ -29,7 +31,7 @@ from .env import GoEnv
 from .loss import unroll_loss, unroll_loss_host
 from .net import MuZeroNet
 from .reanalyse import Reanalyser, positions_from_planes, record_ids
-from .replay import DeviceReplay, queue_key_gids
+from .replay import DeviceReplay, queue_key_gids, window_items_host
 from .resnet import ResMuZeroNet
 from .search import MCTS, MainMCTS, MuZeroAgent
 from .selfplay import GameHistory, SelfPlay, history_from_device, save_batches
@@ -40,4 +42,4 @@ __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "
            "GameHistory", "history_from_device", "save_batches", "deterministic_state_dict", "SelfPlayEvaluator",
            "ResMuZeroNet", "deterministic_res_state_dict", "MzgoError", "Reanalyser",
            "positions_from_planes", "record_ids", "DeviceReplay", "queue_key_gids", "unroll_loss",
-           "unroll_loss_host", "unroll", "unroll_heads_host"]
+           "unroll_loss_host", "unroll", "unroll_heads_host", "window_items_host"]

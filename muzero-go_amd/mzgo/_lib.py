@@ -105,6 +105,9 @@ SIGNATURES = {
     "mzgo_replay_sample": (_I, [_P, _I, ctypes.c_uint64, ctypes.c_uint32, _I, ctypes.c_double, _P, _P, _P, _P, _P]),
     "mzgo_replay_sample_batch": (_I, [_P, _I, _I, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _I,
                                       ctypes.c_double] + [_P] * 13),
+    "mzgo_replay_batch_items": (_I, [_P, _P, _I, _I, ctypes.c_double] + [_P] * 9),
+    "mzgo_replay_reanalyse_sample": (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    "mzgo_replay_window_items_host": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "mzgo_replay_sample_host": (_I, [_P, _P, _I, _I, _I, ctypes.c_uint64, ctypes.c_uint32, _I, ctypes.c_double, _P, _P,
                                      _P]),
     "mzgo_replay_update_priorities": (_I, [_P, _P, _P, _P, _P, _I, ctypes.c_double, _P]),

@@ -11,7 +11,10 @@ and serves both consumers of stored games from there:
 * ``batch``     -- one launch (k_replay_batch) writes the trainer's targets for
   B (game, start, symmetry) samples; ``finish_values`` adds the bootstrap;
 * ``reanalyse`` -- the stored positions searched again under a ``Reanalyser``'s
-  engine, the fresh policies and root values written into the store.
+  engine, the fresh policies and root values written into the store;
+  ``reanalyse_sample`` -- the same for exactly the rows a drawn sample is about
+  to read, from the sampler's device items (``sample`` -> ``reanalyse_sample``
+  -> ``batch_from``; ``TrainConfig.reanalyse_sample``).
 
 Ingest is ``add_games(engine)`` (device to device, one launch; what
 ``MainSelfPlay.play_into`` calls), the playing launch itself
@@ -134,6 +137,23 @@ def sample_host(prio, length, head, batch_size, *, seed, step, symmetries=False,
                                       int(step) & 0xFFFFFFFF, int(bool(symmetries)), float(beta), ptr(items),
                                       ptr(index), ptr(weight)))
     return dict(items=items, index=index, weight=weight)
+
+
+def window_items_host(length, items, unroll_steps):
+    """The item list of a batch's windows on the host (mzgo_replay_window_items_host:
+    the builder kernel's own rule, no GPU).  ``length`` i32 per ring SLOT,
+    ``items`` i32 [B,3] (slot, start, symmetry).  Sample b reads the stored
+    policy rows t = start .. min(start + K, L - 1) of its slot; a triple whose
+    slot is outside the store, whose game is empty or whose start is outside
+    0 .. L - 1 contributes nothing.  Returns i32 [n,2] rows (slot, t) by
+    falling t, equal t by batch position."""
+    length = np.ascontiguousarray(np.asarray(length, dtype=np.int32).reshape(-1))
+    items = np.ascontiguousarray(np.asarray(items, dtype=np.int32).reshape(-1, 3))
+    B, K = len(items), int(unroll_steps)
+    out = np.empty((max(B, 0) * (max(K, 0) + 1), 2), np.int32)
+    n = ctypes.c_int32()
+    check(lib.mzgo_replay_window_items_host(ptr(length), len(length), ptr(items), B, K, ptr(out), ctypes.byref(n)))
+    return out[:n.value].copy()
 
 
 class DeviceReplay:
@@ -360,6 +380,28 @@ class DeviceReplay:
                                            stream_of(self.device)))
         return out
 
+    def batch_from(self, sample, unroll_steps, discount):
+        """``batch``'s dict for a drawn ``sample`` (what ``sample`` returned, or
+        its ``items`` tensor): the assembly half of ``sample_batch``
+        (mzgo_replay_batch_items), so that ``reanalyse_sample`` can run between
+        the draw and the assembly.  ``sample`` then ``batch_from`` gives
+        ``sample_batch``'s tensors bit for bit.  No synchronisation."""
+        items = self._items_of(sample)
+        B, K = items.shape[0], int(unroll_steps)
+        out = self._batch_out(B, K)
+        check(lib.mzgo_replay_batch_items(self._h, ptr(items), B, K, float(discount), ptr(out["obs0"]),
+                                          ptr(out["boot_obs"]), ptr(out["acts"]), ptr(out["t_rew"]), ptr(out["t_pol"]),
+                                          ptr(out["val"]), ptr(out["factor"]), ptr(out["has_boot"]),
+                                          stream_of(self.device)))
+        return out
+
+    def _items_of(self, sample):
+        items = sample["items"] if isinstance(sample, dict) else sample
+        if not (isinstance(items, torch.Tensor) and items.is_cuda and items.dtype == torch.int32
+                and items.dim() == 2 and items.shape[1] == 3):
+            raise ValueError("a sample's items are a CUDA int32 tensor [B, 3] (slot, start, symmetry)")
+        return items.contiguous()
+
     def update_device_priorities(self, sample, per=None, alpha=1.0, *, mean=None):
         """New device weights for a sampled batch (``sample``: what ``sample``
         or ``sample_batch`` returned): ``max(per[b], FLT_MIN) ** alpha`` for
@@ -433,3 +475,37 @@ class DeviceReplay:
         g = None if games is None else np.ascontiguousarray(np.asarray(games, dtype=np.int32).reshape(-1))
         check(lib.mzgo_replay_reanalyse(self._h, reanalyser.engine.handle, ptr(g), 0 if g is None else len(g),
                                         stream_of(self.device)))
+
+    def reanalyse_sample(self, reanalyser, sample, unroll_steps):
+        """MuZero Reanalyse for a drawn ``sample`` (what ``sample`` returned, or
+        its ``items`` tensor), without the host: the stored policy rows the
+        batch is about to read -- sample b's rows start .. min(start + K, L - 1)
+        -- are searched under ``reanalyser``'s engine and weights, keyed as
+        ``reanalyse`` keys them, latest moves first, by one persistent queue
+        launch that reads each position from the store and writes the fresh
+        policy row and root value into it (mzgo_replay_reanalyse_sample).
+        Rows outside the windows stay as they are.  Returns the number of
+        positions searched as a CUDA int32 tensor of one element; nothing is
+        copied back and nothing synchronises."""
+        if reanalyser.N != self.N:
+            raise ValueError(f"the reanalyser plays {reanalyser.N}x{reanalyser.N}, the store holds {self.N}x{self.N}")
+        items = self._items_of(sample)
+        n = torch.empty(1, dtype=torch.int32, device=self.device)
+        check(lib.mzgo_replay_reanalyse_sample(self._h, reanalyser.engine.handle, ptr(items), items.shape[0],
+                                               int(unroll_steps), ptr(n), stream_of(self.device)))
+        return n
+
+    def window_items_host(self, items, unroll_steps):
+        """``window_items_host`` on this store's lengths (the host mirror's,
+        in slot order): numpy i32 [n,2] rows (slot, t).  ``items``: [B,3]
+        (slot, start, symmetry), a tensor or an array."""
+        size, head = ctypes.c_int32(), ctypes.c_int32()
+        check(lib.mzgo_replay_info(self._h, ctypes.byref(size), ctypes.byref(head), None, None))
+        lengths, _ = self._info()
+        length = np.zeros(self.capacity, np.int32)
+        length[(head.value + np.arange(size.value)) % self.capacity] = lengths
+        if isinstance(items, dict):
+            items = items["items"]
+        if isinstance(items, torch.Tensor):
+            items = items.cpu().numpy()
+        return window_items_host(length, items, unroll_steps)

@@ -66,6 +66,12 @@ on the device, every game of a batch at once) and trains on it:
   step.  The loss, the importance weights, the priorities and the device tail
   are unchanged: ``fused_loss`` reads the stacked outputs as they come, the
   torch loss ops read their slices.
+  ``TrainConfig.reanalyse_sample`` (default off; ``device_sampling`` and a
+  ``Reanalyser`` on the trainer's net) is MuZero Reanalyse inside the step:
+  between the draw and the target assembly one queue launch searches exactly
+  the stored positions whose policy rows the batch reads and writes the fresh
+  rows into the store (``DeviceReplay.reanalyse_sample``), every
+  ``reanalyse_every``-th step.
 
 ``initial_inference_torch`` / ``recurrent_inference_torch`` restate
 main.py:72-144 with torch ops on the module's own parameters (reference
@@ -107,6 +113,8 @@ class TrainConfig:
     deferred_stats: bool = False      # device_sampling: train() returns a device scalar; read_stats() fills last
     device_weights: bool = False      # the net's engines take new weights on the device (MuZeroNet.device_weights)
     fused_unroll: bool = False        # batched mode: the whole unroll, heads included, on mzgo.unroll (one autograd node)
+    reanalyse_sample: bool = False    # device_sampling: search the sampled windows' positions before the targets
+    reanalyse_every: int = 1          # reanalyse_sample: on the steps with sample_step % reanalyse_every == 0
 
 
 def reward_value_transform(x, epsilon=0.001):
@@ -443,7 +451,7 @@ class MuZeroTrainer:
     ``random.randint(0, T - 1)``; tests pass a fixed sequence)."""
 
     def __init__(self, net: MuZeroNet, config: TrainConfig = None, mode="reference", start_index=None,
-                 hip_forward=None, sample_seed=0):
+                 hip_forward=None, sample_seed=0, reanalyser=None):
         if mode not in ("reference", "batched"):
             raise ValueError(f"mode must be 'reference' or 'batched', not {mode!r}")
         self.net = net
@@ -487,11 +495,25 @@ class MuZeroTrainer:
                 raise ValueError("device_weights needs the net on the GPU (net.to('cuda')): the engines' weights are "
                                  "packed from the parameters in device memory")
             net.device_weights = True
+        if c.reanalyse_sample:
+            if not c.device_sampling:
+                raise ValueError("reanalyse_sample needs device_sampling (TrainConfig.device_sampling=True): the "
+                                 "windows are searched from the sampler's device items")
+            if reanalyser is None or getattr(reanalyser, "net", None) is not net:
+                raise ValueError("reanalyse_sample needs a Reanalyser on the trainer's net "
+                                 "(MuZeroTrainer(net, ..., reanalyser=Reanalyser(net, num_simulations)))")
+            if int(c.reanalyse_every) < 1:
+                raise ValueError(f"reanalyse_every must be >= 1, got {c.reanalyse_every}")
+        elif reanalyser is not None or c.reanalyse_every != 1:
+            raise ValueError("reanalyser and reanalyse_every belong to reanalyse_sample "
+                             "(TrainConfig.reanalyse_sample=True)")
+        self.reanalyser = reanalyser
         self.mode = mode
         self.sample_seed = int(sample_seed)   # device_sampling: the sampler's seed; its step is sample_step
         self.sample_step = 0                  # steps taken with device_sampling
         self._pending = None                  # device_sampling: the last step's totals, still on the device
         self.last_per_sample_device = None    # device_sampling + sample_priorities: the per-sample losses (CUDA)
+        self.last_searched_device = None      # reanalyse_sample: the positions the last searched step searched (CUDA i32 [1])
         self.action_size = net.board_size ** 2 + 1
         self.optimizer = torch.optim.Adam(net.parameters(), lr=self.config.learning_rate)
         self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=self.config.lr_step_size,
@@ -640,11 +662,27 @@ class MuZeroTrainer:
         ``deferred_stats``).  The bootstrap values' ``initial_inference`` still
         reloads the engine's weights through the host after every optimizer
         step, with one blocking copy per tensor, unless ``device_weights`` is
-        set: only then is a ``deferred_stats`` step free of synchronisation."""
+        set: only then is a ``deferred_stats`` step free of synchronisation.
+
+        With ``reanalyse_sample`` the step is sample -> ``reanalyser.refresh()``
+        -> ``reanalyse_sample`` -> ``batch_from`` (on the steps with
+        ``sample_step % reanalyse_every == 0``; ``sample_batch`` on the others):
+        the policy rows the batch is about to read are searched under the
+        current weights, in the store, before the targets are assembled.  The
+        refresh goes through the host (one blocking copy per tensor) without
+        ``device_weights`` and is a device copy with it; the searches and the
+        assembly never synchronise."""
         from .replay import finish_values
         c, N = self.config, self.net.board_size
-        s = replay.sample_batch(batch_size, c.unroll_steps, c.discount, seed=self.sample_seed, step=self.sample_step,
-                                symmetries=c.symmetries, beta=c.importance_beta)
+        if c.reanalyse_sample and self.sample_step % c.reanalyse_every == 0:
+            s = replay.sample(batch_size, seed=self.sample_seed, step=self.sample_step, symmetries=c.symmetries,
+                              beta=c.importance_beta)
+            self.reanalyser.refresh()
+            self.last_searched_device = replay.reanalyse_sample(self.reanalyser, s, c.unroll_steps)
+            s.update(replay.batch_from(s, c.unroll_steps, c.discount))
+        else:
+            s = replay.sample_batch(batch_size, c.unroll_steps, c.discount, seed=self.sample_seed,
+                                    step=self.sample_step, symmetries=c.symmetries, beta=c.importance_beta)
         self.sample_step += 1
         with torch.no_grad():
             _, v, _ = self.net.initial_inference(s["boot_obs"].view(-1, 6, N, N))
