@@ -17,6 +17,8 @@
  *   mzgo_selfplay_move        one iteration of run_self_play_game's loop,
  *                             for every game slot              self_play.py:465-507
  *   mzgo_records_export       GameHistory / the pickle writer  self_play.py:415-450, :561-583
+ *   mzgo_optim_step           clip_grad_norm_ + Adam.step +    main.py:481-484, :379
+ *                             StepLR.step over the parameters
  *
  * Conventions
  *   - All tensor arguments are DEVICE pointers (hipMalloc / torch CUDA tensors)
@@ -783,6 +785,104 @@ int mzgo_unroll_heads_host(const char* const* keys, const float* const* params, 
                            const int* ndims, float* const* grads, int n_params, const float* latents, int S, int B,
                            int C, int N, float* logits, float* value, float* reward, const float* g_logits,
                            const float* g_value, const float* g_reward, float* g_latent);
+
+/* --------------------------------------------------------------------------
+ * The trainer's optimizer tail in one call (main.py:481-484 and :379:
+ * clip_grad_norm_, torch.optim.Adam.step and StepLR.step over the parameter
+ * tensors, some two dozen small torch launches; this call replaces that
+ * protocol for n float32 tensors of any shapes).
+ *
+ * An optimizer is created for n tensors of numels[i] >= 0 elements and owns,
+ * on its device: a segment table (every tensor cut into chunks of
+ * mzgo_optim_chunk() elements; an empty tensor has one empty chunk), one f64
+ * partial per chunk, the per-tensor step counts (int64, torch's state["step"]),
+ * the scheduler count, the skipped-step count and the step record.  The
+ * parameters and both moments stay the caller's tensors.
+ *
+ * mzgo_optim_step: params / grads / exp_avg / exp_avg_sq are HOST tables of n
+ * DEVICE pointers (f32, contiguous, numels[i] elements, 4-byte aligned; 16-byte
+ * accesses are used per chunk where all of a chunk's pointers allow them).
+ * grads[i] == NULL means tensor i has no gradient this step: it is left out of
+ * the norm and stays untouched, its step count included (as torch skips a
+ * parameter whose .grad is None).  The tables are read during the call and
+ * travel to the kernels by value, so they may change from call to call and
+ * nothing of an earlier step that is still in flight is overwritten.  Three
+ * launches for n <= 96; beyond that (a) and (c) are launched once per 96
+ * tensors, 2 ceil(n / 96) + 1 in all:
+ *   (a) a workgroup per (tensor, chunk) sums (double)g * (double)g in a fixed
+ *       order (a thread's four elements in order, then a tree over the 256
+ *       threads) into its own partial; no atomics.
+ *   (b) one workgroup sums the partials in index order, norm = sqrt(sum), and
+ *       writes the step record {norm, coef, lr, applied} as f64[4]:
+ *       applied = isfinite(norm); coef = (float)min(1, max_norm / (norm + 1e-6))
+ *       (max_norm <= 0: no clipping, coef = 1); lr = lr0 * gamma **
+ *       (sched_count / step_size) in f64 (integer division, integer power by
+ *       squaring).  If applied, every tensor with a gradient gets step += 1 and
+ *       bc1 = 1 - beta1 ** step, bc2 = 1 - beta2 ** step; else skipped += 1.
+ *       sched_count += 1 on every call.
+ *   (c) elementwise over the same segments, nothing when applied == 0; in f64
+ *       on the f32 values, p / m / v stored rounded to f32:
+ *         gc = (double)((float)g * coef)           (+ weight_decay * p, classic)
+ *         m' = m + (gc - m) (1 - beta1);  v' = beta2 v + (1 - beta2) gc gc
+ *         p *= 1 - lr weight_decay                 (decoupled, AdamW)
+ *         p' = p - (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps)
+ *       The gradients are only READ: the clipped values are not written back,
+ *       unlike clip_grad_norm_, which scales .grad in place.
+ * So a non-finite gradient entry changes no parameter, moment or step count;
+ * the step is refused on the device and counted.  Deterministic (the same
+ * inputs give the same bits); everything is enqueued on ``stream``; no
+ * allocation, no blocking copy, no synchronisation.  Calls on one optimizer
+ * must be ordered (one stream, or synchronised by the caller), and the
+ * optimizer's device must be current.
+ *
+ * mzgo_optim_record: the device address of the f64[4] record of the latest
+ * step (valid until destroy; does not synchronise).
+ * mzgo_optim_counts / mzgo_optim_set_counts: the step counts (HOST int64[n]),
+ * the scheduler count and the skipped-step count, read or written in stream
+ * order; both synchronise ``stream``.  Any out pointer of mzgo_optim_counts may
+ * be NULL; mzgo_optim_set_counts takes steps_host == NULL as all zeros.
+ * mzgo_optim_step_host: the host twin: the same scalar functions
+ * (csrc/mzgo_optim.hpp) over HOST arrays with the same chunking and summation
+ * orders, the counts passed in and out (steps int64[n], *sched, *skipped) and
+ * the record written to record[4].  No device work.
+ * mzgo_optim_lr: lr0 * gamma ** (sched_count / step_size), the rate the step
+ * taken at that scheduler count uses.
+ *
+ * MZGO_EINVAL, with the reason in mzgo_last_error(), before any device work:
+ *   create     n < 1; a null numels table or out; a negative numel; more than
+ *              2^31 - 1 chunks in all
+ *   step, step_host   a null optimizer (step) / n < 1, null numels, a negative
+ *              numel, null steps, sched, skipped or record (step_host); a null
+ *              params, grads, exp_avg or exp_avg_sq table; a null params[i],
+ *              exp_avg[i] or exp_avg_sq[i]; a null hyper; lr0, weight_decay or
+ *              gamma negative or not finite; beta1 or beta2 outside [0, 1);
+ *              eps <= 0 or not finite; max_norm NaN; step_size < 1
+ *   record, counts, set_counts   a null optimizer or (record) out pointer; a
+ *              negative count
+ *   lr         a null hyper or out; step_size < 1; sched_count < 0 */
+typedef struct mzgo_optim mzgo_optim;
+typedef struct mzgo_optim_hyper {
+  double lr0;           /* the initial learning rate (StepLR's base) */
+  double beta1, beta2;  /* Adam's betas, each in [0, 1) */
+  double eps;           /* > 0 */
+  double weight_decay;  /* >= 0; 0 = none */
+  int decoupled;        /* weight decay: 0 = classic (Adam), 1 = decoupled (AdamW) */
+  double max_norm;      /* clip_grad_norm_'s max_norm; <= 0 = no clipping */
+  int64_t step_size;    /* StepLR's step_size, >= 1 */
+  double gamma;         /* StepLR's gamma (1 = constant rate) */
+} mzgo_optim_hyper;
+int mzgo_optim_chunk(void);
+int mzgo_optim_create(int n, const int64_t* numels, int device, mzgo_optim** out);
+void mzgo_optim_destroy(mzgo_optim* opt);
+int mzgo_optim_step(mzgo_optim* opt, float* const* params, const float* const* grads, float* const* exp_avg,
+                    float* const* exp_avg_sq, const mzgo_optim_hyper* hyper, void* stream);
+int mzgo_optim_record(mzgo_optim* opt, double** dev_ptr);
+int mzgo_optim_counts(mzgo_optim* opt, int64_t* steps_host, int64_t* sched, int64_t* skipped, void* stream);
+int mzgo_optim_set_counts(mzgo_optim* opt, const int64_t* steps_host, int64_t sched, int64_t skipped, void* stream);
+int mzgo_optim_step_host(int n, const int64_t* numels, float* const* params, const float* const* grads,
+                         float* const* exp_avg, float* const* exp_avg_sq, const mzgo_optim_hyper* hyper,
+                         int64_t* steps, int64_t* sched, int64_t* skipped, double* record);
+int mzgo_optim_lr(const mzgo_optim_hyper* hyper, int64_t sched_count, double* lr);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,9 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
 * ``unroll`` -- the trainer's whole K-step unroll (representation, dynamics chain, the heads of
   every latent) as one autograd node: one HIP forward call, one backward call
   (``TrainConfig.fused_unroll``)
+* ``DeviceAdam`` -- the optimizer tail (gradient-norm clip, Adam / AdamW, StepLR) of any float32
+  module in one stream-ordered HIP call that refuses and counts a non-finite gradient
+  (``TrainConfig.device_optimizer``); ``adam_step_host`` is its host twin on numpy arrays
 * ``mzgo.play`` -- play.py's interactive human-vs-agent loop (``python -m mzgo.play weights.pth``)
 """
 from ._lib import MzgoError
@@ -30,6 +33,7 @@ from .engine import Engine, EngineConfig
 from .env import GoEnv
 from .loss import unroll_loss, unroll_loss_host
 from .net import MuZeroNet
+from .optim import DeviceAdam, adam_step_host, optim_chunk
 from .reanalyse import Reanalyser, positions_from_planes, record_ids
 from .replay import DeviceReplay, queue_key_gids, window_items_host
 from .resnet import ResMuZeroNet
@@ -42,4 +46,4 @@ __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "
            "GameHistory", "history_from_device", "save_batches", "deterministic_state_dict", "SelfPlayEvaluator",
            "ResMuZeroNet", "deterministic_res_state_dict", "MzgoError", "Reanalyser",
            "positions_from_planes", "record_ids", "DeviceReplay", "queue_key_gids", "unroll_loss",
-           "unroll_loss_host", "unroll", "unroll_heads_host", "window_items_host"]
+           "unroll_loss_host", "unroll", "unroll_heads_host", "window_items_host", "DeviceAdam", "adam_step_host", "optim_chunk"]

@@ -45,9 +45,26 @@ class Config(ctypes.Structure):
     ]
 
 
+class OptimHyper(ctypes.Structure):
+    """``mzgo_optim_hyper`` (field order and types must match include/mzgo.h)."""
+
+    _fields_ = [
+        ("lr0", ctypes.c_double),
+        ("beta1", ctypes.c_double),
+        ("beta2", ctypes.c_double),
+        ("eps", ctypes.c_double),
+        ("weight_decay", ctypes.c_double),
+        ("decoupled", ctypes.c_int),
+        ("max_norm", ctypes.c_double),
+        ("step_size", ctypes.c_int64),
+        ("gamma", ctypes.c_double),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/mzgo.h declares
 _P = ctypes.c_void_p
 _I = ctypes.c_int
+_L = ctypes.c_int64
 SIGNATURES = {
     "mzgo_default_config": (None, [ctypes.POINTER(Config), _I]),
     "mzgo_engine_create": (_I, [ctypes.POINTER(Config), ctypes.POINTER(_P)]),
@@ -121,6 +138,16 @@ SIGNATURES = {
     "mzgo_unroll_backward": (_I, [_P] * 5 + [_I] + [_P, ctypes.c_int64] + [_P] * 3 + [_I] * 5
                              + [_P, ctypes.c_int64, _P]),
     "mzgo_unroll_heads_host": (_I, [_P] * 5 + [_I] + [_P] + [_I] * 4 + [_P] * 7),
+    "mzgo_optim_chunk": (_I, []),
+    "mzgo_optim_create": (_I, [_I, _P, _I, ctypes.POINTER(_P)]),
+    "mzgo_optim_destroy": (None, [_P]),
+    "mzgo_optim_step": (_I, [_P] * 5 + [ctypes.POINTER(OptimHyper), _P]),
+    "mzgo_optim_record": (_I, [_P, ctypes.POINTER(_P)]),
+    "mzgo_optim_counts": (_I, [_P, _P, ctypes.POINTER(_L), ctypes.POINTER(_L), _P]),
+    "mzgo_optim_set_counts": (_I, [_P, _P, _L, _L, _P]),
+    "mzgo_optim_step_host": (_I, [_I] + [_P] * 5 + [ctypes.POINTER(OptimHyper), _P, ctypes.POINTER(_L),
+                                  ctypes.POINTER(_L), _P]),
+    "mzgo_optim_lr": (_I, [ctypes.POINTER(OptimHyper), _L, ctypes.POINTER(ctypes.c_double)]),
 }
 
 

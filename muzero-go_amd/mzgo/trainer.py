@@ -73,6 +73,16 @@ on the device, every game of a batch at once) and trains on it:
   rows into the store (``DeviceReplay.reanalyse_sample``), every
   ``reanalyse_every``-th step.
 
+  ``TrainConfig.device_optimizer`` (default off; the net on the GPU) replaces
+  the step's tail -- ``clip_grad_norm_``, ``Adam.step`` and ``StepLR.step``, some
+  two dozen small torch launches over the 22 tensors -- by ``mzgo.DeviceAdam``:
+  one stream-ordered call of three launches (csrc/mzgo_optim.hip) that also
+  refuses a step whose gradient norm is not finite, on the device, and counts
+  it (``skipped_steps``) -- with ``device_sampling`` + ``deferred_stats`` +
+  ``device_weights`` no gradient visits the host, and ``clip_grad_norm_`` would
+  turn one such entry into NaN in every parameter and, at the next pack, in
+  every engine.  ``p.grad`` keeps the unclipped gradient.
+
 ``initial_inference_torch`` / ``recurrent_inference_torch`` restate
 main.py:72-144 with torch ops on the module's own parameters (reference
 mode, and the CPU).  Replay buffers restate main.py:158-244.
@@ -115,6 +125,7 @@ class TrainConfig:
     fused_unroll: bool = False        # batched mode: the whole unroll, heads included, on mzgo.unroll (one autograd node)
     reanalyse_sample: bool = False    # device_sampling: search the sampled windows' positions before the targets
     reanalyse_every: int = 1          # reanalyse_sample: on the steps with sample_step % reanalyse_every == 0
+    device_optimizer: bool = False    # batched mode: clip + Adam + StepLR as one HIP call (mzgo.DeviceAdam)
 
 
 def reward_value_transform(x, epsilon=0.001):
@@ -507,6 +518,13 @@ class MuZeroTrainer:
         elif reanalyser is not None or c.reanalyse_every != 1:
             raise ValueError("reanalyser and reanalyse_every belong to reanalyse_sample "
                              "(TrainConfig.reanalyse_sample=True)")
+        if c.device_optimizer:
+            if mode != "batched":
+                raise ValueError("device_optimizer needs mode='batched': mode='reference' is main.py's per-trajectory "
+                                 "step, which clips and steps the optimizer once per trajectory")
+            if next(net.parameters()).device.type != "cuda":
+                raise ValueError("device_optimizer needs the net on the GPU (net.to('cuda')): mzgo.DeviceAdam has no "
+                                 "eager fall-back")
         self.reanalyser = reanalyser
         self.mode = mode
         self.sample_seed = int(sample_seed)   # device_sampling: the sampler's seed; its step is sample_step
@@ -515,9 +533,16 @@ class MuZeroTrainer:
         self.last_per_sample_device = None    # device_sampling + sample_priorities: the per-sample losses (CUDA)
         self.last_searched_device = None      # reanalyse_sample: the positions the last searched step searched (CUDA i32 [1])
         self.action_size = net.board_size ** 2 + 1
-        self.optimizer = torch.optim.Adam(net.parameters(), lr=self.config.learning_rate)
-        self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=self.config.lr_step_size,
-                                                         gamma=self.config.lr_gamma)
+        if c.device_optimizer:
+            from .optim import DeviceAdam
+            # clip_grad_norm_, Adam and StepLR in one: ``scheduler`` has nothing left to step
+            self.optimizer = DeviceAdam(net.parameters(), lr=c.learning_rate, max_grad_norm=c.max_grad_norm,
+                                        lr_step_size=c.lr_step_size, lr_gamma=c.lr_gamma)
+            self.scheduler = None
+        else:
+            self.optimizer = torch.optim.Adam(net.parameters(), lr=self.config.learning_rate)
+            self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=self.config.lr_step_size,
+                                                             gamma=self.config.lr_gamma)
         self.start_index = start_index or (lambda T: random.randint(0, T - 1))
         self.symmetry_index = lambda: random.randrange(8)      # TrainConfig.symmetries
         self.last = {}
@@ -577,8 +602,33 @@ class MuZeroTrainer:
         avg = self._train_reference(batch) if self.mode == "reference" else self._train_batched(batch)
         if indices is not None:
             replay_buffer.update_priorities(indices, self._priorities(avg, len(indices)))
-        self.scheduler.step()
+        self._scheduler_step()
         return avg
+
+    def _scheduler_step(self):
+        """StepLR once per batch (main.py:500); ``device_optimizer``'s step has done it."""
+        if self.scheduler is not None:
+            self.scheduler.step()
+
+    def _optimizer_step(self):
+        """The step's tail after ``backward()``: ``clip_grad_norm_`` and Adam's
+        step, or with ``device_optimizer`` the one call that is both (and
+        StepLR's).  Returns the learning rate the step used."""
+        if self.config.device_optimizer:
+            lr = self.optimizer.lr
+            self.optimizer.step()
+            return lr
+        torch.nn.utils.clip_grad_norm_(self.net.parameters(), max_norm=self.config.max_grad_norm)
+        self.optimizer.step()
+        return self.optimizer.param_groups[0]["lr"]
+
+    def skipped_steps(self):
+        """``device_optimizer``: the optimizer steps refused so far because the
+        gradient norm was not finite (synchronises)."""
+        if not self.config.device_optimizer:
+            raise ValueError("skipped_steps belongs to device_optimizer (TrainConfig.device_optimizer=True): "
+                             "torch's Adam refuses nothing")
+        return self.optimizer.skipped()
 
     def _priorities(self, avg, n):
         """The sampled games' new priorities: the batch's mean loss for every
@@ -651,7 +701,7 @@ class MuZeroTrainer:
         syms = [self.symmetry_index() for _ in indices] if self.config.symmetries else None
         avg = self._unroll_step(*self.device_targets(replay, indices, starts, syms), device_totals=True)
         replay.update_priorities(indices, self._priorities(avg, len(indices)))
-        self.scheduler.step()
+        self._scheduler_step()
         return avg
 
     def _train_device_sampled(self, replay, batch_size):
@@ -689,10 +739,10 @@ class MuZeroTrainer:
         t_val = finish_values(s["val"], s["factor"], s["has_boot"], v)
         avg = self._unroll_step(s["obs0"], s["acts"], t_val, s["t_rew"], s["t_pol"], device_totals=True,
                                 device_sample=(replay, s))
-        self.scheduler.step()
+        self._scheduler_step()
         return avg
 
-    def _finish_device(self, device_sample, per, totals, B):
+    def _finish_device(self, device_sample, per, totals, B, lr):
         """The tail of a device-sampled step: the priorities from ``per`` (f32
         [B], unweighted) or the batch mean, and the totals (f64 [4], unweighted)
         left on the device for ``read_stats``."""
@@ -704,7 +754,7 @@ class MuZeroTrainer:
             replay.update_device_priorities(sample, alpha=c.priority_alpha, mean=totals[:1] / B)
         self.last_per_sample = None
         self.last_per_sample_device = per if c.sample_priorities else None
-        self._pending = (totals, B, self.optimizer.param_groups[0]["lr"])
+        self._pending = (totals, B, lr)
         if c.deferred_stats:
             self.last = {}
             return totals[0] / B
@@ -828,12 +878,12 @@ class MuZeroTrainer:
             tot_p += tot(p_l)
         loss = per.sum() if not self._weighted(device_sample) else (per * device_sample[1]["weight"]).sum()
         loss.backward()
-        torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm=c.max_grad_norm)
-        self.optimizer.step()
+        lr = self._optimizer_step()
         self.last_per_sample = None
         if device_sample is not None:
             d = per.detach()
-            return self._finish_device(device_sample, d, torch.stack([d.sum().double(), tot_v, tot_p, tot_r]), B)
+            totals = torch.stack([d.sum().double(), tot_v, tot_p, tot_r])
+            return self._finish_device(device_sample, d, totals, B, lr)
         if device_totals and c.sample_priorities:
             back = torch.cat([torch.stack([loss.detach().double(), tot_v, tot_p, tot_r]),
                               per.detach().double()]).tolist()
@@ -846,7 +896,7 @@ class MuZeroTrainer:
             if c.sample_priorities:
                 self.last_per_sample = per.detach().cpu().numpy()
         self.last = dict(training_loss=total / B, value_loss=tot_v / B, policy_loss=tot_p / B,
-                         reward_loss=tot_r / B, lr=self.optimizer.param_groups[0]["lr"])
+                         reward_loss=tot_r / B, lr=lr)
         return total / B
 
     def _head_outputs(self, obs0, acts):
@@ -903,11 +953,10 @@ class MuZeroTrainer:
                                   value_transform=c.use_value_transform)
         loss = per.sum() if not self._weighted(device_sample) else (per * device_sample[1]["weight"]).sum()
         loss.backward()
-        torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm=c.max_grad_norm)
-        self.optimizer.step()
+        lr = self._optimizer_step()
         self.last_per_sample = None
         if device_sample is not None:
-            return self._finish_device(device_sample, per.detach(), totals, B)
+            return self._finish_device(device_sample, per.detach(), totals, B, lr)
         if c.sample_priorities:
             back = torch.cat([totals, per.detach().double()]).tolist()
             self.last_per_sample = np.asarray(back[4:], dtype=np.float32)
@@ -915,5 +964,5 @@ class MuZeroTrainer:
             back = totals.tolist()
         total, tot_v, tot_p, tot_r = back[:4]
         self.last = dict(training_loss=total / B, value_loss=tot_v / B, policy_loss=tot_p / B,
-                         reward_loss=tot_r / B, lr=self.optimizer.param_groups[0]["lr"])
+                         reward_loss=tot_r / B, lr=lr)
         return total / B
