@@ -615,6 +615,67 @@ int mzgo_replay_reanalyse_sample(mzgo_replay* replay, mzgo_engine* eng, const in
  * 1..63. */
 int mzgo_replay_window_items_host(const int32_t* length, int cap, const int32_t* items, int B, int unroll_steps,
                                   int32_t* out, int32_t* n);
+/* Search-value targets (opt-in): value targets from the root values the
+ * searches left in the store, without a bootstrap inference.  A game has L
+ * moves, rewards r[0..L] (r[L] the winner entry) and root values nu[0..L-1];
+ * the target of trajectory index i >= 0 with step horizon n = td_steps >= 1 is
+ *   target = 0.0; factor = 1.0                                          (f64)
+ *   for j = i .. i + n - 1:  if j > L: break
+ *                            target += factor * r[j]; factor *= discount  (in this order)
+ *   if      i + n <= L - 1:  target += factor * nu[i + n]
+ *   else if i + n == L:      target += factor * r[L]
+ *   t_val = (float)target
+ * with no contraction, so the result is defined bit for bit (the rule is one
+ * function, search_value_target in csrc/mzgo_replay.hpp, which the kernel and
+ * the host twin both run).  The i + n == L case is deliberate: the final board
+ * is never searched, so nothing is stored for it, and r[L] is the exact
+ * remainder of the return from there; network targets (mzgo_replay_batch)
+ * evaluate the final board at that index instead, so the two kinds of target
+ * differ there even when nu holds the network's values.  td_steps is
+ * independent of unroll_steps.
+ *
+ * mzgo_replay_batch_values / _batch_items_values / _sample_batch_values are
+ * mzgo_replay_batch / _batch_items / _sample_batch with one launch of
+ * k_replay_batch<true>: obs0, acts, t_rew and t_pol as those write them (the
+ * same symmetry gather), and t_val f32 [B][K+1], entry k the target of index
+ * start + k; no boot_obs, val, factor or has_boot, and nothing to finish.
+ * The same promises on staging and synchronisation as their counterparts.
+ * MZGO_EINVAL as for the counterparts (for the five outputs they take), plus
+ * td_steps < 1. */
+int mzgo_replay_batch_values(mzgo_replay* replay, const int32_t* indices_host, const int32_t* starts_host,
+                             const int32_t* symmetries_host, int B, int unroll_steps, int td_steps, double discount,
+                             float* obs0, int64_t* acts, float* t_rew, float* t_pol, float* t_val, void* stream);
+int mzgo_replay_batch_items_values(mzgo_replay* replay, const int32_t* items, int B, int unroll_steps, int td_steps,
+                                   double discount, float* obs0, int64_t* acts, float* t_rew, float* t_pol,
+                                   float* t_val, void* stream);
+int mzgo_replay_sample_batch_values(mzgo_replay* replay, int B, int unroll_steps, int td_steps, double discount,
+                                    uint64_t seed, uint32_t step, int symmetries, double beta, int32_t* items,
+                                    int32_t* index, uint32_t* gen, float* weight, float* obs0, int64_t* acts,
+                                    float* t_rew, float* t_pol, float* t_val, void* stream);
+/* mzgo_replay_reanalyse_sample over every stored row a search-value batch
+ * reads: a sample's window t = start .. min(start + K, L - 1) (its policy
+ * rows) together with its value rows t = start + n .. min(start + K + n, L - 1),
+ * n = td_steps, each row once per sample (for n > K + 1 a gap lies between the
+ * two ranges; a sample with start + n > L - 1 has no value rows).  The same
+ * order (falling t, equal t by batch position), launches, queue and promises;
+ * the list memory the store owns holds 2 B (K + 1) pairs for this call, and
+ * the queue runs on min(2 B (K + 1), CUs, tree slots) workgroups.
+ * MZGO_EINVAL and MZGO_ENOWEIGHTS as mzgo_replay_reanalyse_sample, plus
+ * td_steps < 1. */
+int mzgo_replay_reanalyse_sample_values(mzgo_replay* replay, mzgo_engine* eng, const int32_t* items, int B,
+                                        int unroll_steps, int td_steps, int32_t* n_searched, void* stream);
+/* The target rule's host twin (no device work): reward f64 [L + 1], root_value
+ * f64 [L] (may be NULL when L = 0); t_val f32 [unroll_steps + 1] receives the
+ * targets of indices start .. start + unroll_steps.  MZGO_EINVAL: a null
+ * pointer; L outside 0..2^30; start < 0; unroll_steps outside 1..63;
+ * td_steps < 1. */
+int mzgo_replay_value_targets_host(const double* reward, const double* root_value, int L, int start, int unroll_steps,
+                                   int td_steps, double discount, float* t_val);
+/* The host twin of mzgo_replay_reanalyse_sample_values' item list (no device
+ * work): as mzgo_replay_window_items_host, with out i32 [2 B (K + 1)][2].
+ * MZGO_EINVAL as there, plus td_steps < 1. */
+int mzgo_replay_window_items_values_host(const int32_t* length, int cap, const int32_t* items, int B, int unroll_steps,
+                                         int td_steps, int32_t* out, int32_t* n);
 /* The sampler's host twin (no device work): prio f64 [cap] and length i32
  * [cap] in slot order, ``head`` the slot of logical game 0; host outputs
  * items, index and (unless NULL) weight as above.  MZGO_EINVAL: a null

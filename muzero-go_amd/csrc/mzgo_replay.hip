@@ -60,6 +60,10 @@ __global__ void __launch_bounds__(kThreads) k_replay_ingest(Store R, ReplayEngin
 //              of the sample's output on thread e % 256: every store is
 //              contiguous across the workgroup; the symmetry is a gather
 //              through the cell permutation in LDS
+// SEARCH (search-value targets, mzgo_replay_batch_values): wave 0 writes t_val
+// itself from the stored root values (search_value_target, mzgo_replay.hpp: at
+// most ``td`` multiply-adds), the plane loop covers the start position alone
+// and boot_obs, val, factor and has_boot are not written (null).
 // ---------------------------------------------------------------------------
 struct BatchOut {
   float* obs0;        // [B][6][CELLS]
@@ -70,9 +74,11 @@ struct BatchOut {
   double* val;        // [B][K+1]
   double* factor;     // [B][K+1]
   uint8_t* has_boot;  // [B][K+1]
+  float* t_val;       // [B][K+1]  SEARCH only
 };
 
-__global__ void __launch_bounds__(kThreads) k_replay_batch(Store R, const int* items, int K, double discount,
+template <bool SEARCH>
+__global__ void __launch_bounds__(kThreads) k_replay_batch(Store R, const int* items, int K, int td, double discount,
                                                            BatchOut O) {
   __shared__ int perm[kMaxBoard * kMaxBoard];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -83,7 +89,10 @@ __global__ void __launch_bounds__(kThreads) k_replay_batch(Store R, const int* i
   const size_t pos = (size_t)slot * (R.M + 1), mv = (size_t)slot * R.M;
   for (int c = tid; c < CELLS; c += kThreads) perm[c] = sym_src(N, sym, c);
 
-  if (tid <= K) {                                          // wave 0 (K <= 63)
+  if (SEARCH && tid <= K) {                               // wave 0 (K <= 63)
+    O.t_val[(size_t)b * (K + 1) + tid] =
+        search_value_target(R.reward + pos, R.root_value + mv, L, start + tid, td, discount);
+  } else if (tid <= K) {
     const int index = start + tid;
     double target = 0.0, factor = 1.0;
     for (int k = 0; k < K; ++k) {
@@ -105,7 +114,7 @@ __global__ void __launch_bounds__(kThreads) k_replay_batch(Store R, const int* i
   __syncthreads();
 
   const int plane = 6 * CELLS;
-  for (int e = tid; e < (K + 2) * plane; e += kThreads) {
+  for (int e = tid; e < (SEARCH ? 1 : K + 2) * plane; e += kThreads) {
     const int row = e / plane, rem = e - row * plane;
     const int p = rem / CELLS, c = rem - p * CELLS;
     // row 0: the start position; row k + 1: the bootstrap position of unroll step k
@@ -182,10 +191,19 @@ __global__ void __launch_bounds__(64) k_replay_scatter(Store R, const int* items
 // inputs alone.  The B windows pass through LDS 256 at a time.
 //   cnt [2][M]   scratch: the counts, then each move's next free index
 //   out [B (K + 1)][2], n_out [1]; n_copy: a second word for the count, or null
+// VALUES (search-value targets, td >= 1): a sample's rows are its window and
+// its value rows (value_rows, sample_has), each once; out [2 B (K + 1)][2].
 // ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(kThreads) k_replay_window_items(Store R, const int* items, int B, int K, int* cnt,
-                                                                  int* out, int* n_out, int* n_copy) {
+template <bool VALUES>
+__global__ void __launch_bounds__(kThreads) k_replay_window_items(Store R, const int* items, int B, int K, int td,
+                                                                  int* cnt, int* out, int* n_out, int* n_copy) {
   __shared__ int w_slot[kThreads], w_start[kThreads], w_rows[kThreads];
+  __shared__ int w_vfirst[VALUES ? kThreads : 1], w_vrows[VALUES ? kThreads : 1];
+  // whether sample i of the chunk in LDS lists move t
+  auto has = [&](int i, int t) {
+    if constexpr (VALUES) return sample_has(w_start[i], w_rows[i], w_vfirst[i], w_vrows[i], t);
+    return window_has(w_start[i], w_rows[i], t);
+  };
   const int tid = threadIdx.x, M = R.M;
   int* next = cnt + M;
   for (int t = tid; t < M; t += kThreads) cnt[t] = 0;
@@ -198,17 +216,18 @@ __global__ void __launch_bounds__(kThreads) k_replay_window_items(Store R, const
         w_slot[tid] = slot;
         w_start[tid] = start;
         w_rows[tid] = window_rows(R.length, R.cap, slot, start, K);
+        if constexpr (VALUES) w_vrows[tid] = value_rows(R.length, R.cap, slot, start, K, td, &w_vfirst[tid]);
       }
       __syncthreads();
       for (int t = tid; t < M; t += kThreads) {            // (a game holds at most M moves: t < M)
         if (pass == 0) {
           int c = cnt[t];
-          for (int i = 0; i < nb; ++i) c += window_has(w_start[i], w_rows[i], t);
+          for (int i = 0; i < nb; ++i) c += has(i, t);
           cnt[t] = c;
         } else {
           int at = next[t];
           for (int i = 0; i < nb; ++i)
-            if (window_has(w_start[i], w_rows[i], t)) {
+            if (has(i, t)) {
               out[2 * (size_t)at] = w_slot[i];
               out[2 * (size_t)at + 1] = t;
               ++at;
@@ -649,6 +668,51 @@ int mzgo_replay_export(mzgo_replay* r, int i, int32_t* length_host, int32_t* key
   return MZGO_OK;
 }
 
+// the host samples of mzgo_replay_batch / _batch_values checked against the
+// mirror and uploaded as device items (``who``: the entry point's name)
+static int upload_samples(mzgo_replay* r, const char* who, const int32_t* indices_host, const int32_t* starts_host,
+                          const int32_t* symmetries_host, int B, hipStream_t s) {
+  for (int b = 0; b < B; ++b) {
+    const int i = indices_host[b];
+    if (i < 0 || i >= r->size)
+      return set_error(MZGO_EINVAL, "%s: sample %d: game %d is not in the store (it holds %d)", who, b, i, r->size);
+    const int L = r->len[r->slot_of(i)];
+    if (starts_host[b] < 0 || starts_host[b] >= L)
+      return set_error(MZGO_EINVAL, "%s: sample %d: start %d outside game %d's %d moves", who, b, starts_host[b], i, L);
+    if (symmetries_host && (symmetries_host[b] < 0 || symmetries_host[b] > 7))
+      return set_error(MZGO_EINVAL, "%s: sample %d: symmetry %d (0..7)", who, b, symmetries_host[b]);
+  }
+  if (int rc = r->items_room((size_t)B * 3, s)) return rc;
+  for (int b = 0; b < B; ++b) {
+    r->h_items[3 * b] = r->slot_of(indices_host[b]);
+    r->h_items[3 * b + 1] = starts_host[b];
+    r->h_items[3 * b + 2] = symmetries_host ? symmetries_host[b] : 0;
+  }
+  return r->items_upload((size_t)B * 3, s);
+}
+
+// the checks the three search-value assemblies share, and their launch
+static int values_check(const mzgo_replay* r, const char* who, int B, int unroll_steps, int td_steps, const float* obs0,
+                        const int64_t* acts, const float* t_rew, const float* t_pol, const float* t_val) {
+  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
+  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (1..%d)", who, unroll_steps, kMaxUnroll);
+  if (td_steps < 1) return set_error(MZGO_EINVAL, "%s: td_steps must be >= 1, got %d", who, td_steps);
+  if (!obs0 || !acts || !t_rew || !t_pol || !t_val)
+    return set_error(MZGO_EINVAL, "%s: null %s", who,
+                     !obs0 ? "obs0" : !acts ? "acts" : !t_rew ? "t_rew" : !t_pol ? "t_pol" : "t_val");
+  return MZGO_OK;
+}
+static int values_launch(mzgo_replay* r, const int* items, int B, int unroll_steps, int td_steps, double discount,
+                         float* obs0, int64_t* acts, float* t_rew, float* t_pol, float* t_val, hipStream_t s) {
+  const BatchOut O{obs0, nullptr, acts, t_rew, t_pol, nullptr, nullptr, nullptr, t_val};
+  hipLaunchKernelGGL(k_replay_batch<true>, dim3(B), dim3(kThreads), 0, s, r->R, items, unroll_steps, td_steps,
+                     discount, O);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
 int mzgo_replay_batch(mzgo_replay* r, const int32_t* indices_host, const int32_t* starts_host,
                       const int32_t* symmetries_host, int B, int unroll_steps, double discount, float* obs0,
                       float* boot_obs, int64_t* acts, float* t_rew, float* t_pol, double* val, double* factor,
@@ -662,29 +726,51 @@ int mzgo_replay_batch(mzgo_replay* r, const int32_t* indices_host, const int32_t
                      !indices_host ? "indices" : !starts_host ? "starts" : !obs0 ? "obs0" : !boot_obs ? "boot_obs"
                      : !acts ? "acts" : !t_rew ? "t_rew" : !t_pol ? "t_pol" : !val ? "val" : !factor ? "factor"
                      : "has_boot");
-  for (int b = 0; b < B; ++b) {
-    const int i = indices_host[b];
-    if (i < 0 || i >= r->size)
-      return set_error(MZGO_EINVAL, "mzgo_replay_batch: sample %d: game %d is not in the store (it holds %d)", b, i,
-                       r->size);
-    const int L = r->len[r->slot_of(i)];
-    if (starts_host[b] < 0 || starts_host[b] >= L)
-      return set_error(MZGO_EINVAL, "mzgo_replay_batch: sample %d: start %d outside game %d's %d moves", b,
-                       starts_host[b], i, L);
-    if (symmetries_host && (symmetries_host[b] < 0 || symmetries_host[b] > 7))
-      return set_error(MZGO_EINVAL, "mzgo_replay_batch: sample %d: symmetry %d (0..7)", b, symmetries_host[b]);
-  }
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = r->items_room((size_t)B * 3, s)) return rc;
-  for (int b = 0; b < B; ++b) {
-    r->h_items[3 * b] = r->slot_of(indices_host[b]);
-    r->h_items[3 * b + 1] = starts_host[b];
-    r->h_items[3 * b + 2] = symmetries_host ? symmetries_host[b] : 0;
-  }
-  if (int rc = r->items_upload((size_t)B * 3, s)) return rc;
-  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot};
-  hipLaunchKernelGGL(k_replay_batch, dim3(B), dim3(kThreads), 0, s, r->R, r->d_items, unroll_steps, discount, O);
+  if (int rc = upload_samples(r, "mzgo_replay_batch", indices_host, starts_host, symmetries_host, B, s)) return rc;
+  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot, nullptr};
+  hipLaunchKernelGGL(k_replay_batch<false>, dim3(B), dim3(kThreads), 0, s, r->R, r->d_items, unroll_steps, 0, discount,
+                     O);
   RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+int mzgo_replay_batch_values(mzgo_replay* r, const int32_t* indices_host, const int32_t* starts_host,
+                             const int32_t* symmetries_host, int B, int unroll_steps, int td_steps, double discount,
+                             float* obs0, int64_t* acts, float* t_rew, float* t_pol, float* t_val, void* stream) {
+  const char* who = "mzgo_replay_batch_values";
+  if (int rc = values_check(r, who, B, unroll_steps, td_steps, obs0, acts, t_rew, t_pol, t_val)) return rc;
+  if (!indices_host || !starts_host)
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !indices_host ? "indices" : "starts");
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = upload_samples(r, who, indices_host, starts_host, symmetries_host, B, s)) return rc;
+  return values_launch(r, r->d_items, B, unroll_steps, td_steps, discount, obs0, acts, t_rew, t_pol, t_val, s);
+}
+
+int mzgo_replay_batch_items_values(mzgo_replay* r, const int32_t* items, int B, int unroll_steps, int td_steps,
+                                   double discount, float* obs0, int64_t* acts, float* t_rew, float* t_pol,
+                                   float* t_val, void* stream) {
+  const char* who = "mzgo_replay_batch_items_values";
+  if (int rc = values_check(r, who, B, unroll_steps, td_steps, obs0, acts, t_rew, t_pol, t_val)) return rc;
+  if (!items) return set_error(MZGO_EINVAL, "%s: null items", who);
+  return values_launch(r, items, B, unroll_steps, td_steps, discount, obs0, acts, t_rew, t_pol, t_val,
+                       (hipStream_t)stream);
+}
+
+int mzgo_replay_value_targets_host(const double* reward, const double* root_value, int L, int start, int unroll_steps,
+                                   int td_steps, double discount, float* t_val) {
+  const char* who = "mzgo_replay_value_targets_host";
+  if (!reward || !t_val || (L > 0 && !root_value))
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !reward ? "reward" : !t_val ? "t_val" : "root_value");
+  if (L < 0 || L > (1 << 30)) return set_error(MZGO_EINVAL, "%s: L %d outside 0..2^30", who, L);
+  if (start < 0) return set_error(MZGO_EINVAL, "%s: start must be >= 0, got %d", who, start);
+  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (1..%d)", who, unroll_steps, kMaxUnroll);
+  if (td_steps < 1) return set_error(MZGO_EINVAL, "%s: td_steps must be >= 1, got %d", who, td_steps);
+  for (int k = 0; k <= unroll_steps; ++k) {
+    const long long i = (long long)start + k;              // (every index past L has the target 0)
+    t_val[k] = search_value_target(reward, root_value, L, i > L ? L + 1 : (int)i, td_steps, discount);
+  }
   return MZGO_OK;
 }
 
@@ -758,25 +844,28 @@ int mzgo_replay_reanalyse(mzgo_replay* r, mzgo_engine* eng, const int32_t* games
   return MZGO_OK;
 }
 
-int mzgo_replay_window_items_host(const int32_t* length, int cap, const int32_t* items, int B, int unroll_steps,
-                                  int32_t* out, int32_t* n) {
-  const char* who = "mzgo_replay_window_items_host";
+// the two item-list twins (td_steps 0: the windows alone)
+static int window_items_host(const char* who, const int32_t* length, int cap, const int32_t* items, int B,
+                             int unroll_steps, int td_steps, int32_t* out, int32_t* n) {
   if (!length || !items || !out || !n)
     return set_error(MZGO_EINVAL, "%s: null %s", who, !length ? "length" : !items ? "items" : !out ? "out" : "n");
   if (cap < 1) return set_error(MZGO_EINVAL, "%s: capacity must be >= 1, got %d", who, cap);
   if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
   if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
     return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (1..%d)", who, unroll_steps, kMaxUnroll);
-  std::vector<int> rows((size_t)B);
+  std::vector<int> rows((size_t)B), vfirst((size_t)B, 0), vrows((size_t)B, 0);
   int t_max = -1;
   for (int b = 0; b < B; ++b) {
     rows[b] = window_rows(length, cap, items[3 * b], items[3 * b + 1], unroll_steps);
     if (rows[b] > 0) t_max = std::max(t_max, items[3 * b + 1] + rows[b] - 1);
+    if (td_steps > 0)
+      vrows[b] = value_rows(length, cap, items[3 * b], items[3 * b + 1], unroll_steps, td_steps, &vfirst[b]);
+    if (vrows[b] > 0) t_max = std::max(t_max, vfirst[b] + vrows[b] - 1);
   }
   int at = 0;
   for (int t = t_max; t >= 0; --t)
     for (int b = 0; b < B; ++b)
-      if (window_has(items[3 * b + 1], rows[b], t)) {
+      if (sample_has(items[3 * b + 1], rows[b], vfirst[b], vrows[b], t)) {
         out[2 * at] = items[3 * b];
         out[2 * at + 1] = t;
         ++at;
@@ -785,9 +874,21 @@ int mzgo_replay_window_items_host(const int32_t* length, int cap, const int32_t*
   return MZGO_OK;
 }
 
-int mzgo_replay_reanalyse_sample(mzgo_replay* r, mzgo_engine* eng, const int32_t* items, int B, int unroll_steps,
-                                 int32_t* n_searched, void* stream) {
-  const char* who = "mzgo_replay_reanalyse_sample";
+int mzgo_replay_window_items_host(const int32_t* length, int cap, const int32_t* items, int B, int unroll_steps,
+                                  int32_t* out, int32_t* n) {
+  return window_items_host("mzgo_replay_window_items_host", length, cap, items, B, unroll_steps, 0, out, n);
+}
+
+int mzgo_replay_window_items_values_host(const int32_t* length, int cap, const int32_t* items, int B, int unroll_steps,
+                                         int td_steps, int32_t* out, int32_t* n) {
+  const char* who = "mzgo_replay_window_items_values_host";
+  if (td_steps < 1) return set_error(MZGO_EINVAL, "%s: td_steps must be >= 1, got %d", who, td_steps);
+  return window_items_host(who, length, cap, items, B, unroll_steps, td_steps, out, n);
+}
+
+// mzgo_replay_reanalyse_sample (td_steps 0: the windows alone) and its _values form
+static int reanalyse_sample(const char* who, mzgo_replay* r, mzgo_engine* eng, const int32_t* items, int B,
+                            int unroll_steps, int td_steps, int32_t* n_searched, void* stream) {
   if (!r || !eng || !items)
     return set_error(MZGO_EINVAL, "%s: null %s", who, !r ? "replay" : !eng ? "engine" : "items");
   if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
@@ -799,7 +900,8 @@ int mzgo_replay_reanalyse_sample(mzgo_replay* r, mzgo_engine* eng, const int32_t
   if (E.latent_dim == 0) return set_error(MZGO_EINVAL, "%s: board-only engine (latent_dim 0) has no network", who);
   if (E.tower) return set_error(MZGO_EINVAL, "%s: tower engines (tower = 1) are not supported", who);
   hipStream_t s = (hipStream_t)stream;
-  const size_t most = (size_t)B * (unroll_steps + 1);     // the host's bound on the list
+  // the host's bound on the list: a window's K + 1 rows and, with value rows, K + 1 more
+  const size_t most = (size_t)B * (unroll_steps + 1) * (td_steps > 0 ? 2 : 1);
   if (most > r->win_cap) {
     RHIPCHK(hipStreamSynchronize(s));                      // (a launch may still read the list)
     if (r->win_items) RHIPCHK(hipFree(r->win_items));
@@ -808,12 +910,28 @@ int mzgo_replay_reanalyse_sample(mzgo_replay* r, mzgo_engine* eng, const int32_t
     RHIPCHK(hipMalloc((void**)&r->win_items, most * 2 * sizeof(int)));
     r->win_cap = most;
   }
-  hipLaunchKernelGGL(k_replay_window_items, dim3(1), dim3(kThreads), 0, s, r->R, items, B, unroll_steps, r->win_cnt,
-                     r->win_items, r->win_n, n_searched);
+  if (td_steps > 0)
+    hipLaunchKernelGGL(k_replay_window_items<true>, dim3(1), dim3(kThreads), 0, s, r->R, items, B, unroll_steps,
+                       td_steps, r->win_cnt, r->win_items, r->win_n, n_searched);
+  else
+    hipLaunchKernelGGL(k_replay_window_items<false>, dim3(1), dim3(kThreads), 0, s, r->R, items, B, unroll_steps, 0,
+                       r->win_cnt, r->win_items, r->win_n, n_searched);
   RHIPCHK(hipGetLastError());
   // (an engine without weights is refused below: the builder wrote the store's scratch only)
   const ReanalyseStoreArgs ra{r->win_items, r->win_n, nullptr, r->R};
   return engine_reanalyse_store(eng, ra, (int)std::min<size_t>(most, 1u << 30), s);
+}
+
+int mzgo_replay_reanalyse_sample(mzgo_replay* r, mzgo_engine* eng, const int32_t* items, int B, int unroll_steps,
+                                 int32_t* n_searched, void* stream) {
+  return reanalyse_sample("mzgo_replay_reanalyse_sample", r, eng, items, B, unroll_steps, 0, n_searched, stream);
+}
+
+int mzgo_replay_reanalyse_sample_values(mzgo_replay* r, mzgo_engine* eng, const int32_t* items, int B,
+                                        int unroll_steps, int td_steps, int32_t* n_searched, void* stream) {
+  const char* who = "mzgo_replay_reanalyse_sample_values";
+  if (td_steps < 1) return set_error(MZGO_EINVAL, "%s: td_steps must be >= 1, got %d", who, td_steps);
+  return reanalyse_sample(who, r, eng, items, B, unroll_steps, td_steps, n_searched, stream);
 }
 
 int mzgo_replay_batch_items(mzgo_replay* r, const int32_t* items, int B, int unroll_steps, double discount,
@@ -828,9 +946,9 @@ int mzgo_replay_batch_items(mzgo_replay* r, const int32_t* items, int B, int unr
     return set_error(MZGO_EINVAL, "mzgo_replay_batch_items: null %s",
                      !items ? "items" : !obs0 ? "obs0" : !boot_obs ? "boot_obs" : !acts ? "acts" : !t_rew ? "t_rew"
                      : !t_pol ? "t_pol" : !val ? "val" : !factor ? "factor" : "has_boot");
-  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot};
-  hipLaunchKernelGGL(k_replay_batch, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, r->R, items, unroll_steps,
-                     discount, O);
+  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot, nullptr};
+  hipLaunchKernelGGL(k_replay_batch<false>, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, r->R, items, unroll_steps,
+                     0, discount, O);
   RHIPCHK(hipGetLastError());
   return MZGO_OK;
 }
@@ -881,10 +999,21 @@ int mzgo_replay_sample_batch(mzgo_replay* r, int B, int unroll_steps, double dis
   if (int rc = sample_launch(r, "mzgo_replay_sample_batch", B, seed, step, symmetries, beta, items, index, gen,
                              weight, s))
     return rc;
-  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot};
-  hipLaunchKernelGGL(k_replay_batch, dim3(B), dim3(kThreads), 0, s, r->R, items, unroll_steps, discount, O);
+  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot, nullptr};
+  hipLaunchKernelGGL(k_replay_batch<false>, dim3(B), dim3(kThreads), 0, s, r->R, items, unroll_steps, 0, discount, O);
   RHIPCHK(hipGetLastError());
   return MZGO_OK;
+}
+
+int mzgo_replay_sample_batch_values(mzgo_replay* r, int B, int unroll_steps, int td_steps, double discount,
+                                    uint64_t seed, uint32_t step, int symmetries, double beta, int32_t* items,
+                                    int32_t* index, uint32_t* gen, float* weight, float* obs0, int64_t* acts,
+                                    float* t_rew, float* t_pol, float* t_val, void* stream) {
+  const char* who = "mzgo_replay_sample_batch_values";
+  if (int rc = values_check(r, who, B, unroll_steps, td_steps, obs0, acts, t_rew, t_pol, t_val)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = sample_launch(r, who, B, seed, step, symmetries, beta, items, index, gen, weight, s)) return rc;
+  return values_launch(r, items, B, unroll_steps, td_steps, discount, obs0, acts, t_rew, t_pol, t_val, s);
 }
 
 int mzgo_replay_sample_host(const double* prio, const int32_t* length, int cap, int head, int B, uint64_t seed,

@@ -6,7 +6,8 @@
 // priority ledger and the sampler's order of additions, descent rule and
 // fallback (host and device: the sampler's host twin runs them), the window
 // of a sample and the item list of a batch's windows (host and device
-// likewise) with the in-place reanalysis queue's arguments, and the engine's
+// likewise) with the in-place reanalysis queue's arguments, the search-value
+// target rule and the value rows it reads (host and device), and the engine's
 // side of the store's engine-facing calls (mzgo_capi.hip owns struct
 // mzgo_engine and the thread-local error string).
 #pragma once
@@ -159,6 +160,53 @@ __host__ __device__ __forceinline__ int window_rows(const int* length, int cap, 
 // whether row t belongs to the window of ``rows`` rows from ``start`` (rows > 0: 0 <= start)
 __host__ __device__ __forceinline__ bool window_has(int start, int rows, int t) {
   return rows > 0 && t >= start && t - start < rows;
+}
+
+// ---------------------------------------------------------------------------
+// Search-value targets (mzgo.h: mzgo_replay_batch_values): the n-step return of
+// trajectory index i >= 0 of a game of L moves, bootstrapped from the stored
+// root value of the position n = td_steps >= 1 moves on.  reward [L + 1] (the
+// winner last), root_value [L].  f64, one multiply and one add per step in
+// this order (no contraction: the unit's -ffp-contract=off), so the float is
+// defined bit for bit; k_replay_batch<true> and the host twin run this text.
+//   i + n <= L - 1   a searched position: its root value
+//   i + n == L       the final board was never searched: r[L], all that is
+//                    left of its return (network targets evaluate that board)
+//   i + n >  L       nothing past the rewards
+// ---------------------------------------------------------------------------
+__host__ __device__ __forceinline__ float search_value_target(const double* reward, const double* root_value, int L,
+                                                              int i, int n, double discount) {
+  double target = 0.0, factor = 1.0;
+  for (int k = 0; k < n; ++k) {
+    const long long j = (long long)i + k;
+    if (j > L) break;
+    target += factor * reward[j];
+    factor *= discount;
+  }
+  const long long at = (long long)i + n;
+  if (at <= L - 1) target += factor * root_value[at];
+  else if (at == L) target += factor * reward[L];
+  return (float)target;
+}
+// The value rows of a sample under search-value targets: the stored root values
+// its K + 1 targets read, t = start + n .. min(start + K + n, L - 1), for a
+// triple that has a window (window_rows > 0).  Returns their count (0 = none:
+// start + n > L - 1) and their first in *first.  A sample's rows are its
+// window together with its value rows, each row once: for n <= K + 1 the two
+// ranges overlap or touch, for n > K + 1 a gap lies between them.
+__host__ __device__ __forceinline__ int value_rows(const int* length, int cap, int slot, int start, int K, int n,
+                                                   int* first) {
+  *first = 0;
+  if (window_rows(length, cap, slot, start, K) == 0) return 0;
+  const int L = length[slot];
+  const long long lo = (long long)start + n, hi = lo + K;
+  if (lo > L - 1) return 0;
+  *first = (int)lo;
+  return (int)((hi < L - 1 ? hi : L - 1) - lo) + 1;
+}
+// whether row t is one of a sample's rows (its window, or its value rows past the window)
+__host__ __device__ __forceinline__ bool sample_has(int start, int rows, int vfirst, int vrows, int t) {
+  return window_has(start, rows, t) || window_has(vfirst, vrows, t);
 }
 
 // One mzgo_replay_reanalyse_sample call: the in-place form of the reanalysis

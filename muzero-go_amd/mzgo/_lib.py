@@ -125,6 +125,13 @@ SIGNATURES = {
     "mzgo_replay_batch_items": (_I, [_P, _P, _I, _I, ctypes.c_double] + [_P] * 9),
     "mzgo_replay_reanalyse_sample": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "mzgo_replay_window_items_host": (_I, [_P, _I, _P, _I, _I, _P, _P]),
+    "mzgo_replay_batch_values": (_I, [_P, _P, _P, _P, _I, _I, _I, ctypes.c_double] + [_P] * 6),
+    "mzgo_replay_batch_items_values": (_I, [_P, _P, _I, _I, _I, ctypes.c_double] + [_P] * 6),
+    "mzgo_replay_sample_batch_values": (_I, [_P, _I, _I, _I, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _I,
+                                             ctypes.c_double] + [_P] * 10),
+    "mzgo_replay_reanalyse_sample_values": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "mzgo_replay_value_targets_host": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_double, _P]),
+    "mzgo_replay_window_items_values_host": (_I, [_P, _I, _P, _I, _I, _I, _P, _P]),
     "mzgo_replay_sample_host": (_I, [_P, _P, _I, _I, _I, ctypes.c_uint64, ctypes.c_uint32, _I, ctypes.c_double, _P, _P,
                                      _P]),
     "mzgo_replay_update_priorities": (_I, [_P, _P, _P, _P, _P, _I, ctypes.c_double, _P]),

@@ -10,6 +10,9 @@ and serves both consumers of stored games from there:
 
 * ``batch``     -- one launch (k_replay_batch) writes the trainer's targets for
   B (game, start, symmetry) samples; ``finish_values`` adds the bootstrap;
+  ``batch_values`` -- the same with search-value targets: n-step returns
+  bootstrapped from the stored root values, no bootstrap inference
+  (``TrainConfig.value_target="search"``; ``value_targets_host`` is the rule);
 * ``reanalyse`` -- the stored positions searched again under a ``Reanalyser``'s
   engine, the fresh policies and root values written into the store;
   ``reanalyse_sample`` -- the same for exactly the rows a drawn sample is about
@@ -139,21 +142,49 @@ def sample_host(prio, length, head, batch_size, *, seed, step, symmetries=False,
     return dict(items=items, index=index, weight=weight)
 
 
-def window_items_host(length, items, unroll_steps):
+def window_items_host(length, items, unroll_steps, td_steps=None):
     """The item list of a batch's windows on the host (mzgo_replay_window_items_host:
     the builder kernel's own rule, no GPU).  ``length`` i32 per ring SLOT,
     ``items`` i32 [B,3] (slot, start, symmetry).  Sample b reads the stored
     policy rows t = start .. min(start + K, L - 1) of its slot; a triple whose
     slot is outside the store, whose game is empty or whose start is outside
     0 .. L - 1 contributes nothing.  Returns i32 [n,2] rows (slot, t) by
-    falling t, equal t by batch position."""
+    falling t, equal t by batch position.  With ``td_steps`` (search-value
+    targets, mzgo_replay_window_items_values_host) a sample's rows are its
+    window together with its value rows t = start + td_steps ..
+    min(start + K + td_steps, L - 1), each row once per sample."""
     length = np.ascontiguousarray(np.asarray(length, dtype=np.int32).reshape(-1))
     items = np.ascontiguousarray(np.asarray(items, dtype=np.int32).reshape(-1, 3))
     B, K = len(items), int(unroll_steps)
-    out = np.empty((max(B, 0) * (max(K, 0) + 1), 2), np.int32)
+    out = np.empty((max(B, 0) * (max(K, 0) + 1) * (1 if td_steps is None else 2), 2), np.int32)
     n = ctypes.c_int32()
-    check(lib.mzgo_replay_window_items_host(ptr(length), len(length), ptr(items), B, K, ptr(out), ctypes.byref(n)))
+    if td_steps is None:
+        check(lib.mzgo_replay_window_items_host(ptr(length), len(length), ptr(items), B, K, ptr(out), ctypes.byref(n)))
+    else:
+        check(lib.mzgo_replay_window_items_values_host(ptr(length), len(length), ptr(items), B, K, int(td_steps),
+                                                       ptr(out), ctypes.byref(n)))
     return out[:n.value].copy()
+
+
+def value_targets_host(rewards, root_values, start, unroll_steps, td_steps, discount):
+    """The search-value targets of one sample on the host
+    (mzgo_replay_value_targets_host: the batch kernel's own rule, no GPU).
+    ``rewards`` f64 [L + 1] (the winner last) and ``root_values`` f64 [L] of a
+    game of L moves; returns float32 [K + 1], entry k the target of trajectory
+    index i = ``start`` + k with step horizon n = ``td_steps``: the discounted
+    rewards r[i] .. r[i + n - 1] (stopping after r[L]) plus discount^n times
+    the stored root value of position i + n where one was searched (i + n <=
+    L - 1), or times r[L] at i + n = L -- the final board has no search, r[L]
+    is what is left of its return -- in f64, one multiply and one add per term."""
+    r = np.ascontiguousarray(np.asarray(rewards, dtype=np.float64).reshape(-1))
+    rv = np.ascontiguousarray(np.asarray(root_values, dtype=np.float64).reshape(-1))
+    if len(r) != len(rv) + 1:
+        raise ValueError(f"value_targets_host: a game of L moves has L + 1 rewards and L root values, got {len(r)} "
+                         f"and {len(rv)}")
+    out = np.empty(max(int(unroll_steps), 0) + 1, np.float32)
+    check(lib.mzgo_replay_value_targets_host(ptr(r), ptr(rv) if len(rv) else None, len(rv), int(start),
+                                             int(unroll_steps), int(td_steps), float(discount), ptr(out)))
+    return out
 
 
 class DeviceReplay:
@@ -326,6 +357,33 @@ class DeviceReplay:
                                     ptr(out["val"]), ptr(out["factor"]), ptr(out["has_boot"]), stream_of(dev)))
         return out
 
+    def _values_out(self, B, K):
+        N, A, dev, K1 = self.N, self.A, self.device, max(K, 0) + 1
+        return dict(obs0=torch.empty(B, 6, N, N, device=dev),
+                    acts=torch.empty(B, max(K, 0), dtype=torch.int64, device=dev),
+                    t_rew=torch.empty(B, max(K, 0), device=dev),
+                    t_pol=torch.empty(B, K1, A, device=dev),
+                    t_val=torch.empty(B, K1, device=dev))
+
+    def batch_values(self, indices, starts, unroll_steps, td_steps, discount, symmetries=None):
+        """``batch`` with search-value targets (mzgo_replay_batch_values, one
+        launch, nothing to finish): ``obs0``, ``acts``, ``t_rew`` and ``t_pol``
+        as ``batch`` gives them, and ``t_val`` f32 [B,K+1] -- the n-step returns
+        (n = ``td_steps`` >= 1, independent of K) bootstrapped from the stored
+        root values, ``value_targets_host``'s bits.  No ``boot_obs``, ``val``,
+        ``factor`` or ``has_boot``."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int32).reshape(-1))
+        B, K = len(idx), int(unroll_steps)
+        st = np.ascontiguousarray(np.asarray(starts, dtype=np.int32).reshape(-1))
+        sy = None if symmetries is None else np.ascontiguousarray(np.asarray(symmetries, dtype=np.int32).reshape(-1))
+        if len(st) != B or (sy is not None and len(sy) != B):
+            raise ValueError("batch_values: indices, starts and symmetries must have one entry per sample")
+        out = self._values_out(B, K)
+        check(lib.mzgo_replay_batch_values(self._h, ptr(idx), ptr(st), ptr(sy), B, K, int(td_steps), float(discount),
+                                           ptr(out["obs0"]), ptr(out["acts"]), ptr(out["t_rew"]), ptr(out["t_pol"]),
+                                           ptr(out["t_val"]), stream_of(self.device)))
+        return out
+
     # ---- the device ledger and sampler ----
     # Independent of ``ledger`` above: the host ledger (``priorities``,
     # ``sample_indices``, ``update_priorities``) is main.py's np.random path and
@@ -393,6 +451,35 @@ class DeviceReplay:
                                           ptr(out["boot_obs"]), ptr(out["acts"]), ptr(out["t_rew"]), ptr(out["t_pol"]),
                                           ptr(out["val"]), ptr(out["factor"]), ptr(out["has_boot"]),
                                           stream_of(self.device)))
+        return out
+
+    def sample_batch_values(self, batch_size, unroll_steps, td_steps, discount, *, seed, step, symmetries=False,
+                            beta=0.0):
+        """``sample`` and ``batch_values`` in one call without the host
+        (mzgo_replay_sample_batch_values): ``sample_batch``'s draw, with
+        ``batch_values``' five tensors for the sampled triples."""
+        B, K = int(batch_size), int(unroll_steps)
+        out = self._values_out(B, K)
+        out.update(self._sample_out(B))
+        check(lib.mzgo_replay_sample_batch_values(self._h, B, K, int(td_steps), float(discount),
+                                                  int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF,
+                                                  int(bool(symmetries)), float(beta), ptr(out["items"]),
+                                                  ptr(out["index"]), ptr(out["gen"]), ptr(out["weight"]),
+                                                  ptr(out["obs0"]), ptr(out["acts"]), ptr(out["t_rew"]),
+                                                  ptr(out["t_pol"]), ptr(out["t_val"]), stream_of(self.device)))
+        return out
+
+    def batch_values_from(self, sample, unroll_steps, td_steps, discount):
+        """``batch_values``' dict for a drawn ``sample`` (what ``sample``
+        returned, or its ``items`` tensor): the assembly half of
+        ``sample_batch_values`` (mzgo_replay_batch_items_values), to run after
+        ``reanalyse_sample(..., td_steps=td_steps)``.  No synchronisation."""
+        items = self._items_of(sample)
+        B, K = items.shape[0], int(unroll_steps)
+        out = self._values_out(B, K)
+        check(lib.mzgo_replay_batch_items_values(self._h, ptr(items), B, K, int(td_steps), float(discount),
+                                                 ptr(out["obs0"]), ptr(out["acts"]), ptr(out["t_rew"]),
+                                                 ptr(out["t_pol"]), ptr(out["t_val"]), stream_of(self.device)))
         return out
 
     def _items_of(self, sample):
@@ -476,7 +563,7 @@ class DeviceReplay:
         check(lib.mzgo_replay_reanalyse(self._h, reanalyser.engine.handle, ptr(g), 0 if g is None else len(g),
                                         stream_of(self.device)))
 
-    def reanalyse_sample(self, reanalyser, sample, unroll_steps):
+    def reanalyse_sample(self, reanalyser, sample, unroll_steps, td_steps=None):
         """MuZero Reanalyse for a drawn ``sample`` (what ``sample`` returned, or
         its ``items`` tensor), without the host: the stored policy rows the
         batch is about to read -- sample b's rows start .. min(start + K, L - 1)
@@ -484,18 +571,27 @@ class DeviceReplay:
         ``reanalyse`` keys them, latest moves first, by one persistent queue
         launch that reads each position from the store and writes the fresh
         policy row and root value into it (mzgo_replay_reanalyse_sample).
-        Rows outside the windows stay as they are.  Returns the number of
+        Rows outside the windows stay as they are.  With ``td_steps``
+        (search-value targets, mzgo_replay_reanalyse_sample_values) the rows
+        searched are those ``batch_values_from`` reads: the windows together
+        with each sample's value rows start + td_steps .. min(start + K +
+        td_steps, L - 1), a row once per sample.  Returns the number of
         positions searched as a CUDA int32 tensor of one element; nothing is
         copied back and nothing synchronises."""
         if reanalyser.N != self.N:
             raise ValueError(f"the reanalyser plays {reanalyser.N}x{reanalyser.N}, the store holds {self.N}x{self.N}")
         items = self._items_of(sample)
         n = torch.empty(1, dtype=torch.int32, device=self.device)
-        check(lib.mzgo_replay_reanalyse_sample(self._h, reanalyser.engine.handle, ptr(items), items.shape[0],
-                                               int(unroll_steps), ptr(n), stream_of(self.device)))
+        if td_steps is None:
+            check(lib.mzgo_replay_reanalyse_sample(self._h, reanalyser.engine.handle, ptr(items), items.shape[0],
+                                                   int(unroll_steps), ptr(n), stream_of(self.device)))
+        else:
+            check(lib.mzgo_replay_reanalyse_sample_values(self._h, reanalyser.engine.handle, ptr(items),
+                                                          items.shape[0], int(unroll_steps), int(td_steps), ptr(n),
+                                                          stream_of(self.device)))
         return n
 
-    def window_items_host(self, items, unroll_steps):
+    def window_items_host(self, items, unroll_steps, td_steps=None):
         """``window_items_host`` on this store's lengths (the host mirror's,
         in slot order): numpy i32 [n,2] rows (slot, t).  ``items``: [B,3]
         (slot, start, symmetry), a tensor or an array."""
@@ -508,4 +604,4 @@ class DeviceReplay:
             items = items["items"]
         if isinstance(items, torch.Tensor):
             items = items.cpu().numpy()
-        return window_items_host(length, items, unroll_steps)
+        return window_items_host(length, items, unroll_steps, td_steps)

@@ -83,6 +83,19 @@ on the device, every game of a batch at once) and trains on it:
   turn one such entry into NaN in every parameter and, at the next pack, in
   every engine.  ``p.grad`` keeps the unclipped gradient.
 
+  ``TrainConfig.value_target="search"`` (default ``"network"``; batched mode)
+  takes every value target from the root values the searches left with the
+  game -- ``trajectory["root_values"]`` on the host, ``Store::root_value`` in a
+  ``DeviceReplay`` -- instead of a network evaluation: the n-step return of
+  index i is the discounted rewards r[i] .. r[i + n - 1] plus discount^n times
+  the root value of position i + n, with n = ``td_steps`` (0 = ``unroll_steps``)
+  independent of the unroll length.  Where i + n is the final board, which no
+  search saw, the bootstrap is the winner entry r[L] (network targets evaluate
+  that board).  On a ``DeviceReplay`` the batch assembly writes ``t_val``
+  itself (``batch_values``, csrc/mzgo_replay.hip k_replay_batch<true>): no
+  bootstrap observations, no ``initial_inference``, no ``finish_values``; with
+  ``reanalyse_sample`` the searched rows include those the value targets read.
+
 ``initial_inference_torch`` / ``recurrent_inference_torch`` restate
 main.py:72-144 with torch ops on the module's own parameters (reference
 mode, and the CPU).  Replay buffers restate main.py:158-244.
@@ -126,6 +139,8 @@ class TrainConfig:
     reanalyse_sample: bool = False    # device_sampling: search the sampled windows' positions before the targets
     reanalyse_every: int = 1          # reanalyse_sample: on the steps with sample_step % reanalyse_every == 0
     device_optimizer: bool = False    # batched mode: clip + Adam + StepLR as one HIP call (mzgo.DeviceAdam)
+    value_target: str = "network"     # "network": main.py's bootstrap; "search": the stored root values (batched mode)
+    td_steps: int = 0                 # value_target="search": the n-step horizon; 0 = unroll_steps
 
 
 def reward_value_transform(x, epsilon=0.001):
@@ -459,7 +474,13 @@ class MuZeroTrainer:
     parameters, ``train(replay_buffer, batch_size)`` as main.py:381-501.
 
     ``start_index(trajectory_length)`` draws a trajectory's start (main.py:395
-    ``random.randint(0, T - 1)``; tests pass a fixed sequence)."""
+    ``random.randint(0, T - 1)``; tests pass a fixed sequence).
+
+    For inspection and tests, a ``device_sampling`` step leaves two device
+    tensors behind without synchronising: ``last_searched_device`` (i32 [1],
+    the positions ``reanalyse_sample`` searched on the last searched step) and
+    ``last_t_val_device`` (f32 [B, K+1], the value targets the last step
+    trained on, under either ``value_target``; held until the next step)."""
 
     def __init__(self, net: MuZeroNet, config: TrainConfig = None, mode="reference", start_index=None,
                  hip_forward=None, sample_seed=0, reanalyser=None):
@@ -525,6 +546,19 @@ class MuZeroTrainer:
             if next(net.parameters()).device.type != "cuda":
                 raise ValueError("device_optimizer needs the net on the GPU (net.to('cuda')): mzgo.DeviceAdam has no "
                                  "eager fall-back")
+        if c.value_target not in ("network", "search"):
+            raise ValueError(f"value_target must be 'network' or 'search', not {c.value_target!r}")
+        if int(c.td_steps) < 0:
+            raise ValueError(f"td_steps must be >= 0 (0 = unroll_steps), got {c.td_steps}")
+        if c.value_target == "search":
+            if mode != "batched":
+                raise ValueError("value_target='search' needs mode='batched': mode='reference' is main.py's own "
+                                 "step, whose value targets bootstrap from the network")
+        elif c.td_steps != 0:
+            raise ValueError("td_steps belongs to value_target='search' (TrainConfig.value_target): network targets "
+                             "bootstrap unroll_steps moves on, as main.py does")
+        # value_target="search": the n of the n-step return (None: network targets)
+        self.td_steps = (int(c.td_steps) or int(c.unroll_steps)) if c.value_target == "search" else None
         self.reanalyser = reanalyser
         self.mode = mode
         self.sample_seed = int(sample_seed)   # device_sampling: the sampler's seed; its step is sample_step
@@ -532,6 +566,7 @@ class MuZeroTrainer:
         self._pending = None                  # device_sampling: the last step's totals, still on the device
         self.last_per_sample_device = None    # device_sampling + sample_priorities: the per-sample losses (CUDA)
         self.last_searched_device = None      # reanalyse_sample: the positions the last searched step searched (CUDA i32 [1])
+        self.last_t_val_device = None         # device_sampling: the value targets the last step trained on (CUDA f32 [B, K+1])
         self.action_size = net.board_size ** 2 + 1
         if c.device_optimizer:
             from .optim import DeviceAdam
@@ -568,6 +603,26 @@ class MuZeroTrainer:
             factor *= c.discount
         boot = index + c.unroll_steps if index + c.unroll_steps < T else None
         return target, factor, boot
+
+    def _search_value(self, trajectory, index):
+        """The search-value target of ``index`` (value_target="search"): the
+        rewards of ``td_steps`` moves, then the stored root value of the
+        position reached -- or, where that is the final board, which no search
+        saw, the winner entry r[L] -- in float64, mzgo_replay.hpp's
+        search_value_target operation by operation."""
+        rewards, nu = trajectory["rewards"], trajectory["root_values"]
+        L, n = len(trajectory["actions"]), self.td_steps
+        target, factor = 0.0, 1.0
+        for j in range(index, index + n):
+            if j > L:
+                break
+            target += factor * float(rewards[j])
+            factor *= self.config.discount
+        if index + n <= L - 1:
+            target += factor * float(nu[index + n])
+        elif index + n == L:
+            target += factor * float(rewards[L])
+        return target
 
     def compute_target_value(self, trajectory, index, unroll_steps=None):
         """main.py:503-522 (bootstrap value from the current weights)."""
@@ -721,22 +776,35 @@ class MuZeroTrainer:
         current weights, in the store, before the targets are assembled.  The
         refresh goes through the host (one blocking copy per tensor) without
         ``device_weights`` and is a device copy with it; the searches and the
-        assembly never synchronise."""
+        assembly never synchronise.
+
+        With ``value_target="search"`` the assembly writes ``t_val`` itself from
+        the stored root values (``sample_batch_values``; with
+        ``reanalyse_sample``: ``reanalyse_sample(td_steps=...)``, which also
+        searches the rows the value targets read, then ``batch_values_from``):
+        no bootstrap rows, no ``initial_inference``, no ``finish_values``, and
+        so no weight reload on the step's own account."""
         from .replay import finish_values
-        c, N = self.config, self.net.board_size
+        c, N, td = self.config, self.net.board_size, self.td_steps
+        draw = dict(seed=self.sample_seed, step=self.sample_step, symmetries=c.symmetries, beta=c.importance_beta)
         if c.reanalyse_sample and self.sample_step % c.reanalyse_every == 0:
-            s = replay.sample(batch_size, seed=self.sample_seed, step=self.sample_step, symmetries=c.symmetries,
-                              beta=c.importance_beta)
+            s = replay.sample(batch_size, **draw)
             self.reanalyser.refresh()
-            self.last_searched_device = replay.reanalyse_sample(self.reanalyser, s, c.unroll_steps)
-            s.update(replay.batch_from(s, c.unroll_steps, c.discount))
+            self.last_searched_device = replay.reanalyse_sample(self.reanalyser, s, c.unroll_steps, td_steps=td)
+            s.update(replay.batch_from(s, c.unroll_steps, c.discount) if td is None
+                     else replay.batch_values_from(s, c.unroll_steps, td, c.discount))
+        elif td is None:
+            s = replay.sample_batch(batch_size, c.unroll_steps, c.discount, **draw)
         else:
-            s = replay.sample_batch(batch_size, c.unroll_steps, c.discount, seed=self.sample_seed,
-                                    step=self.sample_step, symmetries=c.symmetries, beta=c.importance_beta)
+            s = replay.sample_batch_values(batch_size, c.unroll_steps, td, c.discount, **draw)
         self.sample_step += 1
-        with torch.no_grad():
-            _, v, _ = self.net.initial_inference(s["boot_obs"].view(-1, 6, N, N))
-        t_val = finish_values(s["val"], s["factor"], s["has_boot"], v)
+        if td is None:
+            with torch.no_grad():
+                _, v, _ = self.net.initial_inference(s["boot_obs"].view(-1, 6, N, N))
+            t_val = finish_values(s["val"], s["factor"], s["has_boot"], v)
+        else:                               # value_target="search": the assembly wrote the targets
+            t_val = s["t_val"]
+        self.last_t_val_device = t_val
         avg = self._unroll_step(s["obs0"], s["acts"], t_val, s["t_rew"], s["t_pol"], device_totals=True,
                                 device_sample=(replay, s))
         self._scheduler_step()
@@ -778,6 +846,9 @@ class MuZeroTrainer:
         finishing launch.  Nothing comes back to the host."""
         from .replay import finish_values
         c, N = self.config, self.net.board_size
+        if self.td_steps is not None:       # value_target="search": one launch, no inference, nothing to finish
+            bt = replay.batch_values(indices, starts, c.unroll_steps, self.td_steps, c.discount, symmetries)
+            return bt["obs0"], bt["acts"], bt["t_val"], bt["t_rew"], bt["t_pol"]
         bt = replay.batch(indices, starts, c.unroll_steps, c.discount, symmetries)
         with torch.no_grad():
             _, v, _ = self.net.initial_inference(bt["boot_obs"].view(-1, 6, N, N))
@@ -812,14 +883,22 @@ class MuZeroTrainer:
         t_pol = np.zeros((B, K + 1, A))
         acts = np.full((B, K), A - 1, dtype=np.int64)
         boot_obs, boot_at = [], []
+        search = self.td_steps is not None
         for b, (tr, s) in enumerate(zip(batch, starts)):
             T = len(tr["actions"])
+            if search and (tr.get("root_values") is None or len(tr["root_values"]) != T):
+                raise ValueError(f"value_target='search' reads trajectory['root_values'] (one per move, as Reanalyser "
+                                 f"and DeviceReplay.export give them); trajectory {b} has "
+                                 f"{'none' if tr.get('root_values') is None else len(tr['root_values'])} for {T} moves")
             for k in range(K + 1):
-                val, factor, boot = self._discounted(tr, s + k)
-                t_val[b, k] = val
-                if boot is not None:
-                    boot_obs.append(np.asarray(tr["observations"][boot]))
-                    boot_at.append((b, k, factor))
+                if search:
+                    t_val[b, k] = self._search_value(tr, s + k)
+                else:
+                    val, factor, boot = self._discounted(tr, s + k)
+                    t_val[b, k] = val
+                    if boot is not None:
+                        boot_obs.append(np.asarray(tr["observations"][boot]))
+                        boot_at.append((b, k, factor))
                 t_pol[b, k] = self._policy_target(tr, s + k)
             for k in range(K):
                 j = s + k

@@ -1,0 +1,171 @@
+// replay_twins_check.cpp -- the replay store's two search-value host twins,
+// mzgo_replay_value_targets_host and mzgo_replay_window_items_values_host
+// (csrc/mzgo_replay.hip), called from a stand-alone host program so that the C
+// wrappers themselves -- their vectors, the index clamp, the writes into the
+// caller's buffers -- can run under AddressSanitizer and UBSan on a machine
+// without a GPU.  The program links the replay unit alone: what that unit takes
+// from mzgo_capi.hip is stubbed below (the twins call none of it but
+// set_error), and no HIP call is made.  Every buffer has exactly the size the
+// header promises, so a write or read past it is a report; results are compared
+// with the rule restated here.  Exit status 0 and "ok" = clean.
+//
+// Build and run (host code sanitized, device code as the library's):
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off \
+//     -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
+//     -x hip tools/replay_twins_check.cpp muzero-go_amd/csrc/mzgo_replay.hip -o tools/replay_twins_check
+//   tools/replay_twins_check
+#include <algorithm>
+#include <climits>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../include/mzgo.h"
+#include "../muzero-go_amd/csrc/mzgo_replay.hpp"
+
+// ---- mzgo_capi.hip's side of the replay unit, stubbed ----
+static std::string g_err;
+int mzgo::set_error(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+static void no_engine() {
+  fprintf(stderr, "replay_twins_check: an engine call was reached\n");
+  abort();
+}
+void mzgo::replay_engine_view(const mzgo_engine*, ReplayEngineView*) { no_engine(); }
+bool mzgo::engine_noise_hooked(const mzgo_engine*) { no_engine(); return false; }
+int mzgo::engine_play_games(mzgo_engine*, const GamesArgs&, hipStream_t) { no_engine(); return 0; }
+int mzgo::engine_reanalyse_store(mzgo_engine*, const ReanalyseStoreArgs&, int, hipStream_t) { no_engine(); return 0; }
+extern "C" int mzgo_reanalyse(mzgo_engine*, const int8_t*, const uint8_t*, const uint8_t*, const int32_t*, const double*,
+                              int, int32_t*, double*, double*, void*) {
+  no_engine();
+  return 0;
+}
+
+#define CHECK(c)                                                            \
+  do {                                                                      \
+    if (!(c)) {                                                             \
+      fprintf(stderr, "%s:%d: %s (%s)\n", __FILE__, __LINE__, #c, g_err.c_str()); \
+      return 1;                                                             \
+    }                                                                       \
+  } while (0)
+
+// the target rule, read off mzgo.h's formula
+static float restated(const std::vector<double>& r, const std::vector<double>& nu, long long i, long long n, double d) {
+  const long long L = (long long)nu.size();
+  double target = 0.0, factor = 1.0;
+  for (long long j = i; j < i + n; ++j) {
+    if (j > L) break;
+    target += factor * r[j];
+    factor *= d;
+  }
+  if (i + n <= L - 1) target += factor * nu[i + n];
+  else if (i + n == L) target += factor * r[L];
+  return (float)target;
+}
+
+int main() {
+  srand(1);
+  auto unit = [] { return rand() / (double)RAND_MAX - 0.5; };
+  long targets = 0, pairs = 0;
+
+  // ---- mzgo_replay_value_targets_host ----
+  for (int L : {0, 1, 2, 7, 15, 54}) {
+    std::vector<double> r(L + 1), nu(L);
+    for (auto& x : r) x = rand() % 5 ? unit() : 0.0;
+    for (auto& x : nu) x = rand() % 5 ? unit() : 0.0;
+    for (int K : {1, 3, 10, 63})
+      for (int n : {1, 3, K, K + 3, L, L + 5, INT_MAX})
+        for (int start : {0, 1, L / 2, L - 1, L, L + 1, L + 70, INT_MAX - 1, INT_MAX}) {
+          if (n < 1 || start < 0) continue;
+          std::vector<float> out(K + 1, -7.f);              // exactly K + 1 floats
+          const double d = rand() % 2 ? 0.99 : 1.0;
+          CHECK(mzgo_replay_value_targets_host(r.data(), L ? nu.data() : nullptr, L, start, K, n, d, out.data()) ==
+                MZGO_OK);
+          for (int k = 0; k <= K; ++k) {
+            const float want = restated(r, nu, (long long)start + k, n, d);
+            CHECK(std::memcmp(&out[k], &want, sizeof want) == 0);
+            ++targets;
+          }
+        }
+  }
+  {
+    double r[2] = {1.0, 2.0}, nu[1] = {0.5};
+    float out[64];
+    CHECK(mzgo_replay_value_targets_host(nullptr, nu, 1, 0, 3, 1, 0.99, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_value_targets_host(r, nullptr, 1, 0, 3, 1, 0.99, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_value_targets_host(r, nu, 1, 0, 3, 1, 0.99, nullptr) == MZGO_EINVAL);
+    CHECK(mzgo_replay_value_targets_host(r, nu, -1, 0, 3, 1, 0.99, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_value_targets_host(r, nu, INT_MAX, 0, 3, 1, 0.99, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_value_targets_host(r, nu, 1, -1, 3, 1, 0.99, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_value_targets_host(r, nu, 1, INT_MIN, 3, 1, 0.99, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_value_targets_host(r, nu, 1, 0, 0, 1, 0.99, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_value_targets_host(r, nu, 1, 0, 64, 1, 0.99, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_value_targets_host(r, nu, 1, 0, 3, 0, 0.99, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_value_targets_host(r, nu, 1, 0, 3, INT_MIN, 0.99, out) == MZGO_EINVAL);
+  }
+
+  // ---- mzgo_replay_window_items_values_host (and, through the same builder, mzgo_replay_window_items_host) ----
+  const int extremes[] = {INT_MIN, -1, 0, INT_MAX, INT_MAX - 1};
+  for (int rep = 0; rep < 300; ++rep) {
+    const int cap = 1 + rand() % 40, B = 1 + rand() % 300, K = 1 + rand() % 63;
+    const int tds[] = {1, 2, K, K + 1, K + 2, 40, INT_MAX};
+    const int td = tds[rand() % 7];
+    std::vector<int32_t> length(cap), items(3 * (size_t)B);
+    for (auto& x : length) x = rand() % 60;
+    for (int b = 0; b < B; ++b) {
+      items[3 * b] = rand() % 8 ? rand() % (cap + 2) - 1 : extremes[rand() % 5];
+      items[3 * b + 1] = rand() % 8 ? rand() % 62 - 1 : extremes[rand() % 5];
+      items[3 * b + 2] = rand() % 8;
+    }
+    for (int values = 0; values < 2; ++values) {
+      // exactly the pairs the header promises: 2 B (K + 1) with value rows, B (K + 1) without
+      std::vector<int32_t> out((size_t)B * (K + 1) * (values ? 2 : 1) * 2, -1);
+      int32_t n = -1;
+      CHECK((values ? mzgo_replay_window_items_values_host(length.data(), cap, items.data(), B, K, td, out.data(), &n)
+                    : mzgo_replay_window_items_host(length.data(), cap, items.data(), B, K, out.data(), &n)) == MZGO_OK);
+      // the rule restated: per sample its window and its value rows, each once; falling t, ties by batch position
+      std::vector<std::pair<std::pair<int, int>, int>> want;   // ((-t, b), slot)
+      for (int b = 0; b < B; ++b) {
+        const long long slot = items[3 * b], start = items[3 * b + 1];
+        if (slot < 0 || slot >= cap) continue;
+        const long long L = length[slot];
+        if (L <= 0 || start < 0 || start >= L) continue;
+        std::set<long long> rows;
+        for (long long t = start; t <= std::min(start + K, L - 1); ++t) rows.insert(t);
+        if (values)
+          for (long long t = start + td; t <= std::min(start + K + td, L - 1); ++t) rows.insert(t);
+        for (long long t : rows) want.push_back({{(int)-t, b}, (int)slot});
+      }
+      std::sort(want.begin(), want.end());
+      CHECK(n == (int32_t)want.size() && (size_t)n * 2 <= out.size());
+      for (int i = 0; i < n; ++i) CHECK(out[2 * i] == want[i].second && out[2 * i + 1] == -want[i].first.first);
+      pairs += n;
+    }
+  }
+  {
+    int32_t length[1] = {5}, items[3] = {0, 0, 0}, out[64], n = 0;
+    CHECK(mzgo_replay_window_items_values_host(nullptr, 1, items, 1, 3, 2, out, &n) == MZGO_EINVAL);
+    CHECK(mzgo_replay_window_items_values_host(length, 1, nullptr, 1, 3, 2, out, &n) == MZGO_EINVAL);
+    CHECK(mzgo_replay_window_items_values_host(length, 1, items, 1, 3, 2, nullptr, &n) == MZGO_EINVAL);
+    CHECK(mzgo_replay_window_items_values_host(length, 1, items, 1, 3, 2, out, nullptr) == MZGO_EINVAL);
+    CHECK(mzgo_replay_window_items_values_host(length, 0, items, 1, 3, 2, out, &n) == MZGO_EINVAL);
+    CHECK(mzgo_replay_window_items_values_host(length, 1, items, 0, 3, 2, out, &n) == MZGO_EINVAL);
+    CHECK(mzgo_replay_window_items_values_host(length, 1, items, 1, 0, 2, out, &n) == MZGO_EINVAL);
+    CHECK(mzgo_replay_window_items_values_host(length, 1, items, 1, 64, 2, out, &n) == MZGO_EINVAL);
+    CHECK(mzgo_replay_window_items_values_host(length, 1, items, 1, 3, 0, out, &n) == MZGO_EINVAL);
+    CHECK(mzgo_replay_window_items_values_host(length, 1, items, 1, 3, INT_MIN, out, &n) == MZGO_EINVAL);
+  }
+  printf("ok: %ld targets, %ld pairs\n", targets, pairs);
+  return 0;
+}
