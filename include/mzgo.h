@@ -835,6 +835,67 @@ int mzgo_unroll_backward(const char* const* keys, const float* const* params, co
                          const int* ndims, float* const* grads, int n_params, const void* saved, int64_t saved_bytes,
                          const float* g_logits, const float* g_value, const float* g_reward, int B, int K, int C, int N,
                          int emb_rows, void* work, int64_t work_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
+ * bf16 mixed precision for the dynamics conv (csrc/mzgo_conv_bf16.hip).
+ *
+ * With R(t) = float32 -> bfloat16 round-to-nearest-even, returned as float32
+ * (torch's t.bfloat16().float(): NaN stays NaN, overflow goes to inf), the
+ * mode changes the dynamics conv's three matrix products only:
+ *   forward          y  = relu(conv3x3(R(x + emb[a]), R(W)) + b)
+ *   input gradient   gx = conv3x3^T(R(gp), R(W)),  gp = g [y > 0]
+ *   weight gradient  gw = corr(R(gp), R(x + emb[a]))
+ * on v_mfma_f32_16x16x32_bf16: exact products, float32 accumulation in a
+ * fixed order (no atomics: repeats give the same bits).  The add x + emb[a],
+ * the bias, the ReLU, every stored tensor, the bias gradient (the float32 sum
+ * of the unrounded gp) and the weights themselves stay float32; rounding is
+ * straight-through.  Cin and Cout must be multiples of 32 (the MFMA's K) and
+ * 2 <= N <= 19: anything else is MZGO_EINVAL, naming the value, before any
+ * launch.
+ *
+ * mzgo_bf16_round_host: out[i] = R(in[i]) on host arrays, compiled from the
+ * function the kernels round with.
+ *
+ * mzgo_conv3x3_relu_forward_bf16 / mzgo_conv3x3_backward_bf16_workspace /
+ * mzgo_conv3x3_backward_bf16: one layer, with the arguments of
+ * mzgo_conv3x3_relu_forward / _backward_workspace / _backward.  ``weight`` is
+ * the float32 tensor [Cout][Cin][3][3]: the forward rounds it while staging,
+ * the backward packs R(weight) into its workspace (16-byte aligned), which is
+ * mzgo_conv3x3_backward_workspace(B, Cin, Cout) rounded up to 256, plus
+ * 36 Cin Cout bytes for the two packed layouts ([tap][co][ci] and
+ * [tap][ci][co], bf16).  grad_x may be NULL.
+ *
+ * mzgo_unroll_workspace_p / _forward_p / _backward_p: the three unroll calls
+ * with ``precision``.  MZGO_PREC_F32 is mzgo_unroll_workspace / _forward /
+ * _backward exactly (those are calls of these).  MZGO_PREC_BF16 runs the K
+ * dynamics convs, the K chain steps and the weight pass in the mode above:
+ * the forward packs R(dynamics.conv.weight) once into ``saved``, which grows
+ * by 36 C C bytes (rounded up to 256), and the backward reads it there, so the
+ * weights must not change between the two calls; ``work`` keeps its size and
+ * the weight pass its chunks.  C must be a multiple of 32.  At K == 0 the mode
+ * changes nothing, and at K >= 1 logits[0] and value[0] are the float32
+ * mode's bits.  The backward must be given the forward's precision. */
+enum { MZGO_PREC_F32 = 0, MZGO_PREC_BF16 = 1 };
+int mzgo_bf16_round_host(const float* in, int64_t n, float* out);
+int mzgo_conv3x3_relu_forward_bf16(const float* x, const int64_t* action, const float* emb, const float* weight,
+                                   const float* bias, int B, int Cin, int Cout, int N, float* out, void* stream);
+int mzgo_conv3x3_backward_bf16_workspace(int B, int Cin, int Cout, int64_t* bytes_host);
+int mzgo_conv3x3_backward_bf16(const float* grad_out, const float* out, const float* x, const int64_t* action,
+                               const float* emb, const float* weight, int B, int Cin, int Cout, int N, float* grad_x,
+                               float* grad_weight, float* grad_bias, void* workspace, int64_t workspace_bytes,
+                               void* stream);
+int mzgo_unroll_workspace_p(int B, int K, int C, int N, int emb_rows, int precision, int64_t* saved_bytes,
+                            int64_t* work_bytes);
+int mzgo_unroll_forward_p(const char* const* keys, const float* const* params, const int64_t* const* shapes,
+                          const int* ndims, int n_params, const float* obs0, const int64_t* acts, int B, int K, int C,
+                          int N, int emb_rows, void* saved, int64_t saved_bytes, float* logits, float* value,
+                          float* reward, int precision, void* stream);
+int mzgo_unroll_backward_p(const char* const* keys, const float* const* params, const int64_t* const* shapes,
+                           const int* ndims, float* const* grads, int n_params, const void* saved,
+                           int64_t saved_bytes, const float* g_logits, const float* g_value, const float* g_reward,
+                           int B, int K, int C, int N, int emb_rows, void* work, int64_t work_bytes, int precision,
+                           void* stream);
+
 /* The heads' host twin: the same scalar functions (csrc/mzgo_unroll.hpp) run
  * serially over HOST arrays -- forward and backward of the heads of S = K + 1
  * steps' latents [S][B][C][N][N] (every channel and cell sum in index order).

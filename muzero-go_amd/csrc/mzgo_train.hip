@@ -262,4 +262,16 @@ hipError_t conv_backward(const float* g, const float* out, const float* x, const
   return conv_backward_chunk(g, out, x, action, emb, w, B, Cin, Cout, N, kBwdChunk, gx, gw, gb, workspace, s);
 }
 
+// k_conv_bwd_reduce and k_conv_bwd_bias on their own, for the bf16 weight pass (mzgo_conv_bf16.hip), whose
+// partials have the same layout and whose bias gradient is this float32 sum
+hipError_t conv_bwd_reduce(const float* part, float* gw, int chunks, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_conv_bwd_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, gw, chunks, n);
+  return hipGetLastError();
+}
+
+hipError_t conv_bwd_bias(const float* g, const float* out, float* gb, int B, int Cout, int N, hipStream_t s) {
+  hipLaunchKernelGGL(k_conv_bwd_bias, dim3(Cout), dim3(256), 0, s, g, out, gb, B, Cout, N);
+  return hipGetLastError();
+}
+
 }  // namespace mzgo

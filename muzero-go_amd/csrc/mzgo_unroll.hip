@@ -24,7 +24,11 @@
 //             the representation's three layers on conv_backward from the
 //             saved activations: K + 17 launches.
 //
-// fp32 throughout.  Plain vector loads and stores only; no atomics;
+// fp32 throughout, unless the _p entry points are given MZGO_PREC_BF16: then
+// the dynamics conv's three matrix products -- the K forward convs, the K
+// chain steps and the weight pass -- run on mzgo_conv_bf16.hip's bf16 MFMA
+// kernels from weights packed once per forward call into `saved`; everything
+// else, stored tensors included, is the same float32.  Plain vector loads and stores only; no atomics;
 // workgroups never communicate; every sum has a fixed order, so the same
 // inputs give the same bits.  Nothing here allocates or synchronises.
 // Compiled with -ffp-contract=off like every unit.
@@ -36,6 +40,7 @@
 #include <cstring>
 
 #include "../../include/mzgo.h"
+#include "mzgo_conv_bf16.hpp"
 #include "mzgo_unroll.hpp"
 #include "mzgo_weights.hpp"
 
@@ -52,6 +57,8 @@ hipError_t conv_backward(const float* g, const float* out, const float* x, const
 hipError_t conv_backward_chunk(const float* g, const float* out, const float* x, const int64_t* action,
                                const float* emb, const float* w, int B, int Cin, int Cout, int N, int cb, float* gx,
                                float* gw, float* gb, void* workspace, hipStream_t s);
+hipError_t conv_bwd_reduce(const float* part, float* gw, int chunks, size_t n, hipStream_t s);
+hipError_t conv_bwd_bias(const float* g, const float* out, float* gb, int B, int Cout, int N, hipStream_t s);
 }  // namespace mzgo
 
 using namespace mzgo;
@@ -129,6 +136,14 @@ int check_dims(const char* fn, int B, int K, int C, int N, int emb_rows) {
   return MZGO_OK;
 }
 
+int check_precision(const char* fn, int precision, int C) {
+  if (precision != MZGO_PREC_F32 && precision != MZGO_PREC_BF16)
+    return set_error(MZGO_EINVAL, "%s: unknown precision %d (MZGO_PREC_F32 = 0, MZGO_PREC_BF16 = 1)", fn, precision);
+  if (precision == MZGO_PREC_BF16 && C % 32)
+    return set_error(MZGO_EINVAL, "%s: C must be a multiple of 32 in bf16 mode, got %d", fn, C);
+  return MZGO_OK;
+}
+
 // ---------------------------------------------------------------------------
 // the two caller-owned buffers: offsets in floats, every part a multiple of 64
 // ---------------------------------------------------------------------------
@@ -137,14 +152,14 @@ struct Layout {
   int CT;                                               // 16-cell tiles of a board
   int dyn_cb;                                           // boards per chunk of the dynamics' weight pass
   // saved
-  size_t s_obs, s_x1, s_x2, s_lat, s_vmean, s_rmean, s_acts, saved_floats;
+  size_t s_obs, s_x1, s_x2, s_lat, s_vmean, s_rmean, s_acts, s_wpk, saved_floats;
   // work
   size_t w_G, w_g2, w_g1, w_bsum, w_hp, w_conv, work_floats;
 };
 
 size_t pad64(size_t n) { return (n + 63) / 64 * 64; }
 
-Layout layout(int B, int K, int C, int N) {
+Layout layout(int B, int K, int C, int N, int precision) {
   Layout L{};
   const size_t CELLS = (size_t)N * N, S = (size_t)K + 1;
   L.LS = (size_t)B * C * CELLS;
@@ -158,6 +173,8 @@ Layout layout(int B, int K, int C, int N) {
   L.s_vmean = take(S * B);
   L.s_rmean = take(S * B);
   L.s_acts = take((size_t)2 * K * B);                    // int64 [K][B]
+  L.s_wpk = o;                                           // bf16 mode: the dynamics conv's two packed layouts
+  if (precision == MZGO_PREC_BF16) take(conv_bf16_packed_bytes(C, C) / sizeof(float));
   L.saved_floats = o;
   o = 0;
   L.w_G = take(S * L.LS);
@@ -455,10 +472,16 @@ HeadG head_grads(float* const* G) {
 extern "C" {
 
 int mzgo_unroll_workspace(int B, int K, int C, int N, int emb_rows, int64_t* saved_bytes, int64_t* work_bytes) {
+  return mzgo_unroll_workspace_p(B, K, C, N, emb_rows, MZGO_PREC_F32, saved_bytes, work_bytes);
+}
+
+int mzgo_unroll_workspace_p(int B, int K, int C, int N, int emb_rows, int precision, int64_t* saved_bytes,
+                            int64_t* work_bytes) {
   if (int rc = check_dims("mzgo_unroll_workspace", B, K, C, N, emb_rows)) return rc;
+  if (int rc = check_precision("mzgo_unroll_workspace", precision, C)) return rc;
   if (!saved_bytes || !work_bytes)
     return set_error(MZGO_EINVAL, "mzgo_unroll_workspace: null %s", !saved_bytes ? "saved_bytes" : "work_bytes");
-  const Layout L = layout(B, K, C, N);
+  const Layout L = layout(B, K, C, N, precision);
   *saved_bytes = (int64_t)(L.saved_floats * sizeof(float));
   *work_bytes = (int64_t)(L.work_floats * sizeof(float));
   return MZGO_OK;
@@ -468,8 +491,17 @@ int mzgo_unroll_forward(const char* const* keys, const float* const* params, con
                         const int* ndims, int n_params, const float* obs0, const int64_t* acts, int B, int K, int C,
                         int N, int emb_rows, void* saved, int64_t saved_bytes, float* logits, float* value,
                         float* reward, void* stream) {
+  return mzgo_unroll_forward_p(keys, params, shapes, ndims, n_params, obs0, acts, B, K, C, N, emb_rows, saved,
+                               saved_bytes, logits, value, reward, MZGO_PREC_F32, stream);
+}
+
+int mzgo_unroll_forward_p(const char* const* keys, const float* const* params, const int64_t* const* shapes,
+                          const int* ndims, int n_params, const float* obs0, const int64_t* acts, int B, int K, int C,
+                          int N, int emb_rows, void* saved, int64_t saved_bytes, float* logits, float* value,
+                          float* reward, int precision, void* stream) {
   const char* fn = "mzgo_unroll_forward";
   if (int rc = check_dims(fn, B, K, C, N, emb_rows)) return rc;
+  if (int rc = check_precision(fn, precision, C)) return rc;
   const char* null = !obs0 ? "obs0" : !saved ? "saved" : !logits ? "logits" : !value ? "value" : nullptr;
   if (!null && K > 0) null = !acts ? "acts" : !reward ? "reward" : nullptr;
   if (null) return set_error(MZGO_EINVAL, "%s: null %s", fn, null);
@@ -477,7 +509,7 @@ int mzgo_unroll_forward(const char* const* keys, const float* const* params, con
   if (int rc = resolve(fn, keys, params, shapes, ndims, nullptr, n_params, C, emb_rows, kAllSet, kAllSet, 0, P,
                        nullptr))
     return rc;
-  const Layout L = layout(B, K, C, N);
+  const Layout L = layout(B, K, C, N, precision);
   if (saved_bytes < (int64_t)(L.saved_floats * sizeof(float)))
     return set_error(MZGO_EINVAL, "%s: saved too small: %lld < %lld bytes", fn, (long long)saved_bytes,
                      (long long)(L.saved_floats * sizeof(float)));
@@ -493,9 +525,18 @@ int mzgo_unroll_forward(const char* const* keys, const float* const* params, con
   UHIPCHK(conv_forward(obs, nullptr, nullptr, P[WK_CONV1_W], P[WK_CONV1_B], B, 6, kRepC, N, x1, s));
   UHIPCHK(conv_forward(x1, nullptr, nullptr, P[WK_CONV2_W], P[WK_CONV2_B], B, kRepC, kRepC, N, x2, s));
   UHIPCHK(conv_forward(x2, nullptr, nullptr, P[WK_CONV3_W], P[WK_CONV3_B], B, kRepC, C, N, lat, s));
-  for (int k = 1; k <= K; ++k)
-    UHIPCHK(conv_forward(lat + (size_t)(k - 1) * L.LS, acts_t + (size_t)(k - 1) * B, P[WK_EMB], P[WK_DYN_W],
-                         P[WK_DYN_B], B, C, C, N, lat + (size_t)k * L.LS, s));
+  if (precision == MZGO_PREC_BF16 && K > 0) {
+    // R(W) once, in the forward's and the input gradient's layouts: the backward call reads them from `saved`
+    void* wpk = sv + L.s_wpk;
+    UHIPCHK(conv_bf16_pack(P[WK_DYN_W], C, C, wpk, s));
+    for (int k = 1; k <= K; ++k)
+      UHIPCHK(conv_bf16_forward(lat + (size_t)(k - 1) * L.LS, acts_t + (size_t)(k - 1) * B, P[WK_EMB], wpk, nullptr,
+                                P[WK_DYN_B], B, C, C, N, lat + (size_t)k * L.LS, s));
+  } else {
+    for (int k = 1; k <= K; ++k)
+      UHIPCHK(conv_forward(lat + (size_t)(k - 1) * L.LS, acts_t + (size_t)(k - 1) * B, P[WK_EMB], P[WK_DYN_W],
+                           P[WK_DYN_B], B, C, C, N, lat + (size_t)k * L.LS, s));
+  }
   hipLaunchKernelGGL(k_unroll_heads, dim3((unsigned)((K + 1) * B)), dim3(kHeadThreads), 0, s, head_weights(P), lat, B, C,
                      CELLS, logits, value, reward, sv + L.s_vmean, sv + L.s_rmean);
   UHIPCHK(hipGetLastError());
@@ -506,8 +547,18 @@ int mzgo_unroll_backward(const char* const* keys, const float* const* params, co
                          const int* ndims, float* const* grads, int n_params, const void* saved, int64_t saved_bytes,
                          const float* g_logits, const float* g_value, const float* g_reward, int B, int K, int C, int N,
                          int emb_rows, void* work, int64_t work_bytes, void* stream) {
+  return mzgo_unroll_backward_p(keys, params, shapes, ndims, grads, n_params, saved, saved_bytes, g_logits, g_value,
+                                g_reward, B, K, C, N, emb_rows, work, work_bytes, MZGO_PREC_F32, stream);
+}
+
+int mzgo_unroll_backward_p(const char* const* keys, const float* const* params, const int64_t* const* shapes,
+                           const int* ndims, float* const* grads, int n_params, const void* saved,
+                           int64_t saved_bytes, const float* g_logits, const float* g_value, const float* g_reward,
+                           int B, int K, int C, int N, int emb_rows, void* work, int64_t work_bytes, int precision,
+                           void* stream) {
   const char* fn = "mzgo_unroll_backward";
   if (int rc = check_dims(fn, B, K, C, N, emb_rows)) return rc;
+  if (int rc = check_precision(fn, precision, C)) return rc;
   const char* null = !saved ? "saved" : !g_logits ? "g_logits" : !g_value ? "g_value" : !work ? "work"
                      : !grads ? "grads" : nullptr;
   if (!null && K > 0 && !g_reward) null = "g_reward";
@@ -517,7 +568,7 @@ int mzgo_unroll_backward(const char* const* keys, const float* const* params, co
   if (int rc = resolve(fn, keys, params, shapes, ndims, grads, n_params, C, emb_rows, kAllSet, kAllSet,
                        K > 0 ? kAllSet : kAllSet & ~kDynSet, P, Gd))
     return rc;
-  const Layout L = layout(B, K, C, N);
+  const Layout L = layout(B, K, C, N, precision);
   if (saved_bytes < (int64_t)(L.saved_floats * sizeof(float)))
     return set_error(MZGO_EINVAL, "%s: saved too small: %lld < %lld bytes", fn, (long long)saved_bytes,
                      (long long)(L.saved_floats * sizeof(float)));
@@ -543,7 +594,24 @@ int mzgo_unroll_backward(const char* const* keys, const float* const* params, co
   hipLaunchKernelGGL(k_unroll_heads_reduce, dim3((unsigned)(3 * C + 48 + HS_COUNT)), dim3(64), 0, s, hp, rows, C,
                      head_grads(Gd));
   UHIPCHK(hipGetLastError());
-  if (K > 0) {
+  if (K > 0 && precision == MZGO_PREC_BF16) {
+    // (b) - (d) with the conv's products on bf16 MFMA: the chain from the packed weights the forward left in
+    // `saved`, the weight pass's partials into the same region and chunks, then the float32 reduce, bias
+    // gradient and embedding gradient as below
+    const void* wpk = sv + L.s_wpk;
+    for (int st = K; st >= 1; --st)
+      UHIPCHK(conv_bf16_input_grad(G + (size_t)st * L.LS, lat + (size_t)st * L.LS, wpk, B, C, C, N,
+                                   G + (size_t)(st - 1) * L.LS, 1, bsum + (size_t)(st - 1) * B * C * L.CT, s));
+    const int chunks = (K * B + L.dyn_cb - 1) / L.dyn_cb;
+    UHIPCHK(conv_bf16_weight_partials(G + L.LS, lat + L.LS, lat, acts_t, P[WK_EMB], K * B, C, C, N, L.dyn_cb,
+                                      static_cast<float*>(cw), s));
+    UHIPCHK(conv_bwd_reduce(static_cast<const float*>(cw), Gd[WK_DYN_W], chunks, (size_t)C * C * 9, s));
+    UHIPCHK(conv_bwd_bias(G + L.LS, lat + L.LS, Gd[WK_DYN_B], K * B, C, N, s));
+    const size_t n_emb = (size_t)emb_rows * C;
+    hipLaunchKernelGGL(k_unroll_emb_grad, dim3((unsigned)((n_emb + 255) / 256)), dim3(256), 0, s, bsum, acts_t, K * B, C,
+                       L.CT, emb_rows, Gd[WK_EMB]);
+    UHIPCHK(hipGetLastError());
+  } else if (K > 0) {
     // (b) the chain: step s's input gradient into step s - 1's latent gradient
     for (int st = K; st >= 1; --st) {
       hipLaunchKernelGGL(k_unroll_chain, dim3((unsigned)L.CT, (unsigned)(C / 16), (unsigned)B), dim3(64), 0, s,

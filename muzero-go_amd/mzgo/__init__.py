@@ -23,7 +23,9 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
   per-sample sums and the heads' gradients from one kernel (``TrainConfig.fused_loss``)
 * ``unroll`` -- the trainer's whole K-step unroll (representation, dynamics chain, the heads of
   every latent) as one autograd node: one HIP forward call, one backward call
-  (``TrainConfig.fused_unroll``)
+  (``TrainConfig.fused_unroll``); ``precision="bf16"`` (``TrainConfig.unroll_precision``) runs the
+  dynamics conv's three matrix products on bf16 MFMA with float32 accumulation and float32 master
+  weights, and ``bf16_round_host`` is the kernels' rounding on host arrays
 * ``DeviceAdam`` -- the optimizer tail (gradient-norm clip, Adam / AdamW, StepLR) of any float32
   module in one stream-ordered HIP call that refuses and counts a non-finite gradient
   (``TrainConfig.device_optimizer``); ``adam_step_host`` is its host twin on numpy arrays
@@ -41,11 +43,11 @@ from .replay import DeviceReplay, queue_key_gids, value_targets_host, window_ite
 from .resnet import ResMuZeroNet
 from .search import MCTS, MainMCTS, MuZeroAgent
 from .selfplay import GameHistory, SelfPlay, history_from_device, save_batches
-from .unroll import unroll, unroll_heads_host
+from .unroll import bf16_round_host, unroll, unroll_heads_host
 from .weights import deterministic_res_state_dict, deterministic_state_dict
 
 __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "MuZeroAgent", "SelfPlay",
            "GameHistory", "history_from_device", "save_batches", "deterministic_state_dict", "SelfPlayEvaluator",
            "ResMuZeroNet", "deterministic_res_state_dict", "MzgoError", "Reanalyser",
            "positions_from_planes", "record_ids", "DeviceReplay", "queue_key_gids", "unroll_loss",
-           "unroll_loss_host", "unroll", "unroll_heads_host", "window_items_host", "value_targets_host", "DeviceAdam", "adam_step_host", "optim_chunk"]
+           "unroll_loss_host", "unroll", "unroll_heads_host", "bf16_round_host", "window_items_host", "value_targets_host", "DeviceAdam", "adam_step_host", "optim_chunk"]

@@ -145,6 +145,14 @@ SIGNATURES = {
     "mzgo_unroll_backward": (_I, [_P] * 5 + [_I] + [_P, ctypes.c_int64] + [_P] * 3 + [_I] * 5
                              + [_P, ctypes.c_int64, _P]),
     "mzgo_unroll_heads_host": (_I, [_P] * 5 + [_I] + [_P] + [_I] * 4 + [_P] * 7),
+    "mzgo_bf16_round_host": (_I, [_P, ctypes.c_int64, _P]),
+    "mzgo_conv3x3_relu_forward_bf16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "mzgo_conv3x3_backward_bf16_workspace": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
+    "mzgo_conv3x3_backward_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    "mzgo_unroll_workspace_p": (_I, [_I] * 6 + [ctypes.POINTER(ctypes.c_int64)] * 2),
+    "mzgo_unroll_forward_p": (_I, [_P] * 4 + [_I] + [_P] * 2 + [_I] * 5 + [_P, ctypes.c_int64] + [_P] * 3 + [_I, _P]),
+    "mzgo_unroll_backward_p": (_I, [_P] * 5 + [_I] + [_P, ctypes.c_int64] + [_P] * 3 + [_I] * 5
+                               + [_P, ctypes.c_int64, _I, _P]),
     "mzgo_optim_chunk": (_I, []),
     "mzgo_optim_create": (_I, [_I, _P, _I, ctypes.POINTER(_P)]),
     "mzgo_optim_destroy": (None, [_P]),

@@ -66,6 +66,14 @@ on the device, every game of a batch at once) and trains on it:
   step.  The loss, the importance weights, the priorities and the device tail
   are unchanged: ``fused_loss`` reads the stacked outputs as they come, the
   torch loss ops read their slices.
+  ``TrainConfig.unroll_precision="bf16"`` (default ``"fp32"``; ``fused_unroll``
+  in batched mode, ``latent_dim`` a multiple of 32) is mixed precision for the
+  dynamics conv, where nine tenths of the unroll's arithmetic are: its forward,
+  its input gradient and its weight gradient run on bf16 MFMA
+  (csrc/mzgo_conv_bf16.hip) with both operands rounded to bfloat16, nearest
+  even, and float32 accumulation.  The master weights, the stored latents, all
+  22 gradients, the representation, the heads and the optimizer stay float32,
+  and the step stays deterministic.
   ``TrainConfig.reanalyse_sample`` (default off; ``device_sampling`` and a
   ``Reanalyser`` on the trainer's net) is MuZero Reanalyse inside the step:
   between the draw and the target assembly one queue launch searches exactly
@@ -141,6 +149,7 @@ class TrainConfig:
     device_optimizer: bool = False    # batched mode: clip + Adam + StepLR as one HIP call (mzgo.DeviceAdam)
     value_target: str = "network"     # "network": main.py's bootstrap; "search": the stored root values (batched mode)
     td_steps: int = 0                 # value_target="search": the n-step horizon; 0 = unroll_steps
+    unroll_precision: str = "fp32"    # fused_unroll: "bf16" runs the dynamics conv's products on bf16 MFMA
 
 
 def reward_value_transform(x, epsilon=0.001):
@@ -507,6 +516,18 @@ class MuZeroTrainer:
                              "(TrainConfig.device_sampling=True)")
         if c.importance_beta < 0 or not c.priority_alpha > 0:
             raise ValueError("importance_beta must be >= 0 and priority_alpha > 0")
+        if c.unroll_precision not in ("fp32", "bf16"):
+            raise ValueError(f"unroll_precision must be 'fp32' or 'bf16', not {c.unroll_precision!r}")
+        if c.unroll_precision == "bf16":
+            if mode != "batched":
+                raise ValueError("unroll_precision='bf16' needs mode='batched' and fused_unroll=True: mode='reference' "
+                                 "is main.py's per-trajectory float32 step")
+            if not c.fused_unroll:
+                raise ValueError("unroll_precision='bf16' needs fused_unroll=True: the bf16 kernels are mzgo.unroll's "
+                                 "(the per-layer paths are float32 only)")
+            if isinstance(net, MuZeroNet) and net.latent_dim % 32:
+                raise ValueError(f"unroll_precision='bf16' needs latent_dim to be a multiple of 32, got "
+                                 f"{net.latent_dim}")
         if c.fused_unroll:
             if not isinstance(net, MuZeroNet):
                 raise ValueError(f"fused_unroll runs the reference network (MuZeroNet) only, not {type(net).__name__}: "
@@ -988,7 +1009,7 @@ class MuZeroTrainer:
         K = acts.shape[1]
         if self.config.fused_unroll:
             from .unroll import unroll
-            logits, value, reward = unroll(net, obs0, acts)
+            logits, value, reward = unroll(net, obs0, acts, self.config.unroll_precision)
             for k in range(K + 1):
                 yield (reward[k - 1] if k else None), value[k], logits[k]
             return
@@ -1018,7 +1039,7 @@ class MuZeroTrainer:
         self.optimizer.zero_grad()
         if c.fused_unroll:
             from .unroll import unroll
-            lgs, vals, rews = unroll(net, obs0, acts)          # stacked as they come
+            lgs, vals, rews = unroll(net, obs0, acts, c.unroll_precision)   # stacked as they come
         else:
             lgs, vals, rews = [], [], []
             for reward, value, logits in self._head_outputs(obs0, acts):

@@ -24,15 +24,24 @@ HEAD_KEYS = ("dynamics.reward_conv.weight", "dynamics.reward_conv.bias", "dynami
              "prediction.value_fc.weight", "prediction.value_fc.bias", "prediction.policy_conv.weight",
              "prediction.policy_conv.bias")
 
-_sizes = {}      # (B, K, C, N, emb_rows) -> (saved_bytes, work_bytes)
+PRECISIONS = {"fp32": 0, "bf16": 1}      # mzgo.h: MZGO_PREC_F32, MZGO_PREC_BF16
+
+_sizes = {}      # (B, K, C, N, emb_rows, precision) -> (saved_bytes, work_bytes)
 
 
-def workspace_bytes(B, K, C, N, emb_rows):
-    """``mzgo_unroll_workspace``: (saved_bytes, work_bytes) of a call's two device buffers."""
-    key = (B, K, C, N, emb_rows)
+def _precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
+    return PRECISIONS[precision]
+
+
+def workspace_bytes(B, K, C, N, emb_rows, precision="fp32"):
+    """``mzgo_unroll_workspace_p``: (saved_bytes, work_bytes) of a call's two device buffers."""
+    key = (B, K, C, N, emb_rows, precision)
     if key not in _sizes:
         saved, work = ctypes.c_int64(), ctypes.c_int64()
-        check(lib.mzgo_unroll_workspace(B, K, C, N, emb_rows, ctypes.byref(saved), ctypes.byref(work)))
+        check(lib.mzgo_unroll_workspace_p(B, K, C, N, emb_rows, _precision(precision), ctypes.byref(saved),
+                                          ctypes.byref(work)))
         _sizes[key] = (saved.value, work.value)
     return _sizes[key]
 
@@ -68,22 +77,23 @@ def _net_table(net):
 
 class _Unroll(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, obs0, acts, table, names, dims, *params):
+    def forward(ctx, obs0, acts, table, names, dims, precision, *params):
         B, K, C, N, emb_rows = dims
         dev = obs0.device
         A = N * N + 1
-        saved_bytes, _ = workspace_bytes(*dims)
+        saved_bytes, _ = workspace_bytes(*dims, precision)
         saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
         logits = torch.empty(K + 1, B, A, device=dev)
         value = torch.empty(K + 1, B, device=dev)
         reward = torch.empty(K, B, device=dev) if K > 0 else None
         data = [p.detach() for p in params]
         with torch.cuda.device(dev):
-            check(lib.mzgo_unroll_forward(table.keys, table.pointers(data), table.shapes, table.ndims, table.n,
-                                          ptr(obs0), ptr(acts) if K > 0 else None, B, K, C, N, emb_rows, ptr(saved),
-                                          saved_bytes, ptr(logits), ptr(value), ptr(reward), stream_of(dev)))
+            check(lib.mzgo_unroll_forward_p(table.keys, table.pointers(data), table.shapes, table.ndims, table.n,
+                                            ptr(obs0), ptr(acts) if K > 0 else None, B, K, C, N, emb_rows,
+                                            ptr(saved), saved_bytes, ptr(logits), ptr(value), ptr(reward),
+                                            PRECISIONS[precision], stream_of(dev)))
         ctx.save_for_backward(saved, *params)
-        ctx.table, ctx.names, ctx.dims = table, names, dims
+        ctx.table, ctx.names, ctx.dims, ctx.precision = table, names, dims, precision
         if K == 0:
             return logits, value
         return logits, value, reward
@@ -92,11 +102,11 @@ class _Unroll(torch.autograd.Function):
     @once_differentiable                 # the HIP backward builds no graph: create_graph=True is an error, not silence
     def backward(ctx, g_logits, g_value, g_reward=None):
         saved, *params = ctx.saved_tensors
-        table, names, dims = ctx.table, ctx.names, ctx.dims
+        table, names, dims, precision = ctx.table, ctx.names, ctx.dims, ctx.precision
         B, K, C, N, emb_rows = dims
         dev = saved.device
         A = N * N + 1
-        saved_bytes, work_bytes = workspace_bytes(*dims)
+        saved_bytes, work_bytes = workspace_bytes(*dims, precision)
 
         def grad(g, *shape):
             if g is None:
@@ -110,14 +120,23 @@ class _Unroll(torch.autograd.Function):
         grads = [None if K == 0 and k.startswith("dynamics.") else torch.empty_like(p) for k, p in zip(names, params)]
         data = [p.detach() for p in params]
         with torch.cuda.device(dev):
-            check(lib.mzgo_unroll_backward(table.keys, table.pointers(data), table.shapes, table.ndims,
-                                           table.pointers(grads), table.n, ptr(saved), saved_bytes, ptr(g_logits),
-                                           ptr(g_value), ptr(g_reward), B, K, C, N, emb_rows, ptr(work), work_bytes,
-                                           stream_of(dev)))
-        return (None, None, None, None, None, *grads)
+            check(lib.mzgo_unroll_backward_p(table.keys, table.pointers(data), table.shapes, table.ndims,
+                                             table.pointers(grads), table.n, ptr(saved), saved_bytes, ptr(g_logits),
+                                             ptr(g_value), ptr(g_reward), B, K, C, N, emb_rows, ptr(work), work_bytes,
+                                             PRECISIONS[precision], stream_of(dev)))
+        return (None, None, None, None, None, None, *grads)
 
 
-def unroll(net, obs0, acts):
+def bf16_round_host(x):
+    """``mzgo_bf16_round_host``: float32 -> bfloat16 round-to-nearest-even, returned as float32
+    (``t.bfloat16().float()``), by the function the bf16 kernels round with.  A numpy array in, one out."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(x)
+    check(lib.mzgo_bf16_round_host(ptr(x), x.size, ptr(out)))
+    return out
+
+
+def unroll(net, obs0, acts, precision="fp32"):
     """The K-step unroll of ``net`` (a ``MuZeroNet`` on the GPU) from the
     observations ``obs0`` f32 [B, 6, N, N] under the actions ``acts`` i64
     [B, K] (``device_targets``' layout; None or [B, 0] for K = 0), values in
@@ -129,13 +148,24 @@ def unroll(net, obs0, acts):
     ``mzgo_unroll_forward`` call, the backward one ``mzgo_unroll_backward``
     call; a net whose embedding is larger than the board (``board_size=``)
     gets a full-size embedding gradient.  Each call owns its buffers, so calls
-    may overlap freely.  Device tensors only: there is no eager fall-back."""
+    may overlap freely.  Device tensors only: there is no eager fall-back.
+
+    ``precision="bf16"`` runs the dynamics conv's three matrix products --
+    forward, input gradient and weight gradient -- on bf16 MFMA with their
+    operands rounded to bfloat16 (nearest even) and float32 accumulation
+    (``mzgo_unroll_forward_p`` with ``MZGO_PREC_BF16``, mzgo.h); the weights,
+    the latents, every gradient and everything else stay float32.  It needs
+    ``latent_dim`` to be a multiple of 32.  Any other string is a ValueError."""
     from .resnet import ResMuZeroNet
+    _precision(precision)
     if isinstance(net, ResMuZeroNet):
         raise TypeError("mzgo.unroll runs the reference network (MuZeroNet) only: ResMuZeroNet's residual tower has "
                         "no fused unroll kernels")
     if not isinstance(net, MuZeroNet):
         raise TypeError(f"mzgo.unroll needs a MuZeroNet, got {type(net).__name__}")
+    if precision == "bf16" and net.latent_dim % 32:
+        raise ValueError(f"mzgo.unroll: precision='bf16' needs latent_dim to be a multiple of 32, got "
+                         f"{net.latent_dim}")
     params = list(net.parameters())
     dev = params[0].device
     if dev.type != "cuda":
@@ -162,7 +192,7 @@ def unroll(net, obs0, acts):
             raise ValueError(f"mzgo.unroll: parameter '{k}' must be contiguous float32")
     table, names = _net_table(net)
     obs0 = obs0.detach().to(torch.float32).contiguous()
-    out = _Unroll.apply(obs0, acts, table, names, (B, K, C, N, net.max_action_size), *params)
+    out = _Unroll.apply(obs0, acts, table, names, (B, K, C, N, net.max_action_size), precision, *params)
     return (out[0], out[1], out[2] if K > 0 else None)
 
 
