@@ -39,24 +39,14 @@
 
 #include "../../include/mzgo.h"
 #include "mzgo_conv_bf16.hpp"
+#include "mzgo_train.hpp"
 
 namespace mzgo {
 
-// mzgo_capi.hip
-int set_error(int code, const char* fmt, ...);
-// mzgo_train.hip
-extern const int kConvMaxBatch;
-size_t conv_bwd_workspace_bytes(int B, int Cin, int Cout);
-hipError_t conv_bwd_reduce(const float* part, float* gw, int chunks, size_t n, hipStream_t s);
-hipError_t conv_bwd_bias(const float* g, const float* out, float* gb, int B, int Cout, int N, hipStream_t s);
-
 namespace {
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-
-constexpr int kChunk = 8;                 // boards per gw partial of the layer entry point (mzgo_train.hip's kBwdChunk)
 
 __device__ __forceinline__ bf16x8_t frag_ld(const uint16_t* p) { return *reinterpret_cast<const bf16x8_t*>(p); }
 
@@ -343,12 +333,6 @@ hipError_t conv_bf16_weight_partials(const float* g, const float* out, const flo
 
 using namespace mzgo;
 
-#define BHIPCHK(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return set_error(MZGO_EHIP, "%s: %s", #expr, hipGetErrorString(e_));     \
-  } while (0)
-
 extern "C" {
 
 int mzgo_bf16_round_host(const float* in, int64_t n, float* out) {
@@ -363,7 +347,7 @@ int mzgo_conv3x3_relu_forward_bf16(const float* x, const int64_t* action, const 
   const char* fn = "mzgo_conv3x3_relu_forward_bf16";
   if (int rc = check_layer(fn, B, Cin, Cout, N)) return rc;
   if (!x || !weight || !bias || !out || (emb && !action)) return set_error(MZGO_EINVAL, "%s: null argument", fn);
-  BHIPCHK(conv_bf16_forward(x, action, emb, nullptr, weight, bias, B, Cin, Cout, N, out, (hipStream_t)stream));
+  MZGO_HIPCHK(conv_bf16_forward(x, action, emb, nullptr, weight, bias, B, Cin, Cout, N, out, (hipStream_t)stream));
   return MZGO_OK;
 }
 
@@ -393,14 +377,14 @@ int mzgo_conv3x3_backward_bf16(const float* grad_out, const float* out, const fl
   hipStream_t s = (hipStream_t)stream;
   float* part = static_cast<float*>(workspace);
   void* packed = static_cast<char*>(workspace) + parts;
-  const int chunks = (B + kChunk - 1) / kChunk;
+  const int chunks = (B + kBwdChunk - 1) / kBwdChunk;
   if (grad_x) {
-    BHIPCHK(conv_bf16_pack(weight, Cin, Cout, packed, s));
-    BHIPCHK(conv_bf16_input_grad(grad_out, out, packed, B, Cin, Cout, N, grad_x, 0, nullptr, s));
+    MZGO_HIPCHK(conv_bf16_pack(weight, Cin, Cout, packed, s));
+    MZGO_HIPCHK(conv_bf16_input_grad(grad_out, out, packed, B, Cin, Cout, N, grad_x, 0, nullptr, s));
   }
-  BHIPCHK(conv_bf16_weight_partials(grad_out, out, x, action, emb, B, Cin, Cout, N, kChunk, part, s));
-  BHIPCHK(conv_bwd_reduce(part, grad_weight, chunks, (size_t)Cout * Cin * 9, s));
-  BHIPCHK(conv_bwd_bias(grad_out, out, grad_bias, B, Cout, N, s));
+  MZGO_HIPCHK(conv_bf16_weight_partials(grad_out, out, x, action, emb, B, Cin, Cout, N, kBwdChunk, part, s));
+  MZGO_HIPCHK(conv_bwd_reduce(part, grad_weight, chunks, (size_t)Cout * Cin * 9, s));
+  MZGO_HIPCHK(conv_bwd_bias(grad_out, out, grad_bias, B, Cout, N, s));
   return MZGO_OK;
 }
 

@@ -28,28 +28,15 @@
 //
 // Operand fragments (16x16x4 f32): lane l holds A[l & 15][k = l >> 4] and
 // B[k = l >> 4][l & 15]; the result C[(l >> 4) * 4 + r][l & 15] in register r.
-#include <hip/hip_runtime.h>
-
-#include <cstddef>
-#include <cstdint>
+//
+// The layer entry points (mzgo.h: mzgo_conv3x3_relu_forward,
+// mzgo_conv3x3_backward, mzgo_dyn_conv_backward and their workspace sizes) are
+// at the end of this file.
+#include "mzgo_train.hpp"
 
 namespace mzgo {
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-constexpr int kBwdChunk = 8;   // boards per gw partial (a chunk's K = 8 x cells); a caller may ask for more
 constexpr int kMaxN = 19;
-// k_conv_fwd, k_conv_bwd_input (and mzgo_unroll.hip's k_unroll_chain) put the batch in gridDim.z: HIP's
-// portable limit of that dimension.  The entry points refuse a larger batch before any launch.
-extern const int kConvMaxBatch = 65535;
-
-// gp at (b, co, cell (y, x)) or 0 off the board
-__device__ __forceinline__ float masked_grad(const float* __restrict__ g, const float* __restrict__ out,
-                                             size_t plane, int N, int y, int x) {
-  if (y < 0 || y >= N || x < 0 || x >= N) return 0.f;
-  const size_t i = plane + (size_t)y * N + x;
-  return out[i] > 0.f ? g[i] : 0.f;
-}
 
 // y = relu(conv3x3(x (+ emb[action]) ) + bias); grid (ceil(CELLS/16), ceil(Cout/16), B), one wave
 __global__ void __launch_bounds__(64) k_conv_fwd(const float* __restrict__ x, const int64_t* __restrict__ action,
@@ -92,10 +79,17 @@ __global__ void __launch_bounds__(64) k_conv_fwd(const float* __restrict__ x, co
   }
 }
 
-// gx; grid (ceil(CELLS/16), ceil(Cin/16), B), one wave per block
+// gx; grid (ceil(CELLS/16), ceil(Cin/16), B), one wave per block.  CHAIN (a step of the unroll's chain): the
+// result is ADDED into dst (the previous latent's gradient, which already holds its heads' part), and the
+// tile's sum over its 16 cells goes to bsum[b][ci][tile] for the embedding; Cin and Cout are multiples of 16
+// there (the launcher refuses others), so the channel masks are compiled out: with them the ten steps of the
+// chain at 6x6, C = 128, B = 128 measured 0.10 ms slower (profiles/unroll_timing_refactor_masked.json), and
+// with the tap's board mask tested per K step instead of once per tap still 0.04 ms.  The loop is one load
+// chain per MFMA (out, g and w, then the product), so every test in it is on the critical path.
+template <bool CHAIN>
 __global__ void __launch_bounds__(64) k_conv_bwd_input(const float* __restrict__ g, const float* __restrict__ out,
-                                                       const float* __restrict__ w, float* __restrict__ gx, int Cin,
-                                                       int Cout, int N) {
+                                                       const float* __restrict__ w, float* __restrict__ dst,
+                                                       float* __restrict__ bsum, int Cin, int Cout, int N) {
   const int lane = threadIdx.x;
   const int CELLS = N * N;
   const int b = blockIdx.z, ci0 = blockIdx.y * 16, p0 = blockIdx.x * 16;
@@ -104,27 +98,40 @@ __global__ void __launch_bounds__(64) k_conv_bwd_input(const float* __restrict__
   const int py = p / N, px = p - py * N;
   const bool prow = p < CELLS;
   const int ci = ci0 + i;                         // this lane's B column
-  const bool ccol = ci < Cin;
+  const bool ccol = CHAIN || ci < Cin;
   const size_t gplane = (size_t)b * Cout * CELLS;
   f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
   for (int tap = 0; tap < 9; ++tap) {
     const int ky = tap / 3, kx = tap - ky * 3;
     const int qy = py - ky + 1, qx = px - kx + 1;
+    const bool on = prow && qy >= 0 && qy < N && qx >= 0 && qx < N;
+    const size_t q = on ? (size_t)qy * N + qx : 0;
     for (int co0 = 0; co0 < Cout; co0 += 4) {
       const int co = co0 + k;
-      const bool okc = co < Cout;
-      const float a = prow && okc ? masked_grad(g, out, gplane + (size_t)co * CELLS, N, qy, qx) : 0.f;
+      const bool okc = CHAIN || co < Cout;
+      float a = 0.f;                              // gp at the tap's cell, 0 off the board
+      if (on && okc) {
+        const size_t idx = gplane + (size_t)co * CELLS + q;
+        a = out[idx] > 0.f ? g[idx] : 0.f;
+      }
       const float bw = ccol && okc ? w[((size_t)co * Cin + ci) * 9 + tap] : 0.f;
       acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bw, acc, 0, 0, 0);
     }
   }
-  const int col = ci0 + (lane & 15);
-  if (col < Cin) {
+  float t = 0.f;                                  // rows past the board are exact zeros
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int pr = p0 + (lane >> 4) * 4 + r;
-      if (pr < CELLS) gx[((size_t)b * Cin + col) * CELLS + pr] = acc[r];
+  for (int r = 0; r < 4; ++r) {
+    const int pr = p0 + (lane >> 4) * 4 + r;
+    if (ccol && pr < CELLS) {
+      const size_t idx = ((size_t)b * Cin + ci) * CELLS + pr;
+      dst[idx] = CHAIN ? dst[idx] + acc[r] : acc[r];
     }
+    t += acc[r];
+  }
+  if (CHAIN) {
+    t += __shfl_xor(t, 16, 64);
+    t += __shfl_xor(t, 32, 64);
+    if (bsum && lane < 16 && ccol) bsum[((size_t)b * Cin + ci) * gridDim.x + blockIdx.x] = t;
   }
 }
 
@@ -219,15 +226,6 @@ __global__ void __launch_bounds__(256) k_conv_bwd_bias(const float* __restrict__
   if (tid == 0) gb[co] = red[0];
 }
 
-size_t conv_bwd_workspace_bytes_chunk(int B, int Cin, int Cout, int cb) {
-  const size_t chunks = (size_t)(B + cb - 1) / cb;
-  return chunks * (size_t)Cout * Cin * 9 * sizeof(float);
-}
-
-size_t conv_bwd_workspace_bytes(int B, int Cin, int Cout) {
-  return conv_bwd_workspace_bytes_chunk(B, Cin, Cout, kBwdChunk);
-}
-
 hipError_t conv_forward(const float* x, const int64_t* action, const float* emb, const float* w, const float* bias,
                         int B, int Cin, int Cout, int N, float* y, hipStream_t s) {
   const int CELLS = N * N;
@@ -236,34 +234,26 @@ hipError_t conv_forward(const float* x, const int64_t* action, const float* emb,
   return hipGetLastError();
 }
 
-// conv_backward with `cb` boards per gw partial (the workspace holds
-// conv_bwd_workspace_bytes_chunk(B, Cin, Cout, cb)): the partials' order is
-// fixed by (B, cb) alone
-hipError_t conv_backward_chunk(const float* g, const float* out, const float* x, const int64_t* action,
-                               const float* emb, const float* w, int B, int Cin, int Cout, int N, int cb, float* gx,
-                               float* gw, float* gb, void* workspace, hipStream_t s) {
-  const int CELLS = N * N;
-  const int chunks = (B + cb - 1) / cb;
-  if (gx)
-    hipLaunchKernelGGL(k_conv_bwd_input, dim3((CELLS + 15) / 16, (Cin + 15) / 16, B), dim3(64), 0, s, g, out, w, gx,
-                       Cin, Cout, N);
-  hipLaunchKernelGGL(k_conv_bwd_weight, dim3(((Cout + 15) / 16) * ((Cin + 15) / 16), chunks), dim3(576), 0, s, g,
-                     out, x, action, emb, static_cast<float*>(workspace), B, Cin, Cout, N, cb);
-  const size_t n = (size_t)Cout * Cin * 9;
-  hipLaunchKernelGGL(k_conv_bwd_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                     static_cast<const float*>(workspace), gw, chunks, n);
-  hipLaunchKernelGGL(k_conv_bwd_bias, dim3(Cout), dim3(256), 0, s, g, out, gb, B, Cout, N);
+hipError_t conv_input_grad(const float* g, const float* out, const float* w, int B, int Cin, int Cout, int N,
+                           float* dst, int accumulate, float* bsum, hipStream_t s) {
+  const dim3 grid((N * N + 15) / 16, (Cin + 15) / 16, B);
+  if (accumulate && (Cin % 16 || Cout % 16)) return hipErrorInvalidValue;   // (its instantiation has no channel masks)
+  if (accumulate)
+    hipLaunchKernelGGL(k_conv_bwd_input<true>, grid, dim3(64), 0, s, g, out, w, dst, bsum, Cin, Cout, N);
+  else
+    hipLaunchKernelGGL(k_conv_bwd_input<false>, grid, dim3(64), 0, s, g, out, w, dst, (float*)nullptr, Cin, Cout, N);
   return hipGetLastError();
 }
 
-hipError_t conv_backward(const float* g, const float* out, const float* x, const int64_t* action, const float* emb,
-                         const float* w, int B, int Cin, int Cout, int N, float* gx, float* gw, float* gb,
-                         void* workspace, hipStream_t s) {
-  return conv_backward_chunk(g, out, x, action, emb, w, B, Cin, Cout, N, kBwdChunk, gx, gw, gb, workspace, s);
+hipError_t conv_weight_partials(const float* g, const float* out, const float* x, const int64_t* action,
+                                const float* emb, int B, int Cin, int Cout, int N, int cb, float* part,
+                                hipStream_t s) {
+  const int chunks = (B + cb - 1) / cb;
+  hipLaunchKernelGGL(k_conv_bwd_weight, dim3(((Cout + 15) / 16) * ((Cin + 15) / 16), chunks), dim3(576), 0, s, g,
+                     out, x, action, emb, part, B, Cin, Cout, N, cb);
+  return hipGetLastError();
 }
 
-// k_conv_bwd_reduce and k_conv_bwd_bias on their own, for the bf16 weight pass (mzgo_conv_bf16.hip), whose
-// partials have the same layout and whose bias gradient is this float32 sum
 hipError_t conv_bwd_reduce(const float* part, float* gw, int chunks, size_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_conv_bwd_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, gw, chunks, n);
   return hipGetLastError();
@@ -274,4 +264,81 @@ hipError_t conv_bwd_bias(const float* g, const float* out, float* gb, int B, int
   return hipGetLastError();
 }
 
+hipError_t conv_backward(const float* g, const float* out, const float* x, const int64_t* action, const float* emb,
+                         const float* w, int B, int Cin, int Cout, int N, float* gx, float* gw, float* gb,
+                         void* workspace, hipStream_t s) {
+  float* part = static_cast<float*>(workspace);
+  hipError_t e = gx ? conv_input_grad(g, out, w, B, Cin, Cout, N, gx, 0, nullptr, s) : hipSuccess;
+  if (e == hipSuccess) e = conv_weight_partials(g, out, x, action, emb, B, Cin, Cout, N, kBwdChunk, part, s);
+  if (e == hipSuccess) e = conv_bwd_reduce(part, gw, (B + kBwdChunk - 1) / kBwdChunk, (size_t)Cout * Cin * 9, s);
+  if (e == hipSuccess) e = conv_bwd_bias(g, out, gb, B, Cout, N, s);
+  return e;
+}
+
 }  // namespace mzgo
+
+using namespace mzgo;
+
+extern "C" {
+
+int mzgo_dyn_conv_backward_workspace(int B, int C, int64_t* bytes_host) {
+  if (B < 1 || C < 16 || C % 16 || !bytes_host) return set_error(MZGO_EINVAL, "bad argument (B=%d, C=%d)", B, C);
+  *bytes_host = (int64_t)conv_bwd_workspace_bytes(B, C, C);
+  return MZGO_OK;
+}
+
+int mzgo_dyn_conv_backward(const float* grad_out, const float* out, const float* latent, const int64_t* action,
+                           const float* emb, const float* weight, int B, int C, int N, float* grad_latent,
+                           float* grad_weight, float* grad_bias, void* workspace, int64_t workspace_bytes,
+                           void* stream) {
+  if (!grad_out || !out || !latent || !action || !emb || !weight || !grad_latent || !grad_weight || !grad_bias ||
+      !workspace || B < 1 || C < 16 || C % 16 || N < 2 || N > 19)
+    return set_error(MZGO_EINVAL, "bad argument (B=%d, C=%d, N=%d)", B, C, N);
+  if (B > kConvMaxBatch)
+    return set_error(MZGO_EINVAL, "mzgo_dyn_conv_backward: B = %d exceeds the launch grid's z limit of %d", B,
+                     kConvMaxBatch);
+  if (workspace_bytes < (int64_t)conv_bwd_workspace_bytes(B, C, C))
+    return set_error(MZGO_EINVAL, "workspace too small: %lld < %lld bytes", (long long)workspace_bytes,
+                     (long long)conv_bwd_workspace_bytes(B, C, C));
+  MZGO_HIPCHK(conv_backward(grad_out, out, latent, action, emb, weight, B, C, C, N, grad_latent, grad_weight,
+                            grad_bias, workspace, (hipStream_t)stream));
+  return MZGO_OK;
+}
+
+int mzgo_conv3x3_relu_forward(const float* x, const int64_t* action, const float* emb, const float* weight,
+                              const float* bias, int B, int Cin, int Cout, int N, float* out, void* stream) {
+  if (!x || !weight || !bias || !out || (emb && !action) || B < 1 || Cin < 1 || Cout < 1 || N < 2 || N > 19)
+    return set_error(MZGO_EINVAL, "bad argument (B=%d, Cin=%d, Cout=%d, N=%d)", B, Cin, Cout, N);
+  if (B > kConvMaxBatch)
+    return set_error(MZGO_EINVAL, "mzgo_conv3x3_relu_forward: B = %d exceeds the launch grid's z limit of %d", B,
+                     kConvMaxBatch);
+  MZGO_HIPCHK(conv_forward(x, action, emb, weight, bias, B, Cin, Cout, N, out, (hipStream_t)stream));
+  return MZGO_OK;
+}
+
+int mzgo_conv3x3_backward_workspace(int B, int Cin, int Cout, int64_t* bytes_host) {
+  if (B < 1 || Cin < 1 || Cout < 1 || !bytes_host)
+    return set_error(MZGO_EINVAL, "bad argument (B=%d, Cin=%d, Cout=%d)", B, Cin, Cout);
+  *bytes_host = (int64_t)conv_bwd_workspace_bytes(B, Cin, Cout);
+  return MZGO_OK;
+}
+
+int mzgo_conv3x3_backward(const float* grad_out, const float* out, const float* x, const int64_t* action,
+                          const float* emb, const float* weight, int B, int Cin, int Cout, int N, float* grad_x,
+                          float* grad_weight, float* grad_bias, void* workspace, int64_t workspace_bytes,
+                          void* stream) {
+  if (!grad_out || !out || !x || (emb && !action) || !weight || !grad_weight || !grad_bias || !workspace || B < 1 ||
+      Cin < 1 || Cout < 1 || N < 2 || N > 19)
+    return set_error(MZGO_EINVAL, "bad argument (B=%d, Cin=%d, Cout=%d, N=%d)", B, Cin, Cout, N);
+  if (B > kConvMaxBatch)
+    return set_error(MZGO_EINVAL, "mzgo_conv3x3_backward: B = %d exceeds the launch grid's z limit of %d", B,
+                     kConvMaxBatch);
+  if (workspace_bytes < (int64_t)conv_bwd_workspace_bytes(B, Cin, Cout))
+    return set_error(MZGO_EINVAL, "workspace too small: %lld < %lld bytes", (long long)workspace_bytes,
+                     (long long)conv_bwd_workspace_bytes(B, Cin, Cout));
+  MZGO_HIPCHK(conv_backward(grad_out, out, x, action, emb, weight, B, Cin, Cout, N, grad_x, grad_weight, grad_bias,
+                            workspace, (hipStream_t)stream));
+  return MZGO_OK;
+}
+
+}  // extern "C"

@@ -17,21 +17,24 @@
 //   backward  ONE k_unroll_heads_bwd launch (every latent's gradient from the
 //             heads, and a row of partial sums per latent for the thirteen
 //             head tensors), k_unroll_heads_reduce (the rows summed in a fixed
-//             order), K k_unroll_chain launches (the dynamics conv's input
-//             gradient of step s added into step s - 1's, with its board sums),
-//             the dynamics conv's weight and bias gradients in ONE pass of
-//             conv_backward_chunk over the K B boards, k_unroll_emb_grad, and
-//             the representation's three layers on conv_backward from the
-//             saved activations: K + 17 launches.
+//             order), K conv_input_grad launches in its accumulating form
+//             (the dynamics conv's input gradient of step s added into step
+//             s - 1's, with its board sums), the dynamics conv's weight and
+//             bias gradients in ONE pass over the K B boards
+//             (conv_weight_partials, conv_bwd_reduce, conv_bwd_bias),
+//             k_unroll_emb_grad, and the representation's three layers on
+//             conv_backward from the saved activations: K + 17 launches.
 //
 // fp32 throughout, unless the _p entry points are given MZGO_PREC_BF16: then
 // the dynamics conv's three matrix products -- the K forward convs, the K
-// chain steps and the weight pass -- run on mzgo_conv_bf16.hip's bf16 MFMA
-// kernels from weights packed once per forward call into `saved`; everything
-// else, stored tensors included, is the same float32.  Plain vector loads and stores only; no atomics;
-// workgroups never communicate; every sum has a fixed order, so the same
-// inputs give the same bits.  Nothing here allocates or synchronises.
-// Compiled with -ffp-contract=off like every unit.
+// chain steps and the weight pass's partials, the three dyn_* helpers below --
+// run on mzgo_conv_bf16.hip's bf16 MFMA kernels from weights packed once per
+// forward call into `saved` (one more launch); everything else, stored tensors
+// included, is the same float32 and the same sequence of launches.  Plain
+// vector loads and stores only; no atomics; workgroups never communicate;
+// every sum has a fixed order, so the same inputs give the same bits.  Nothing
+// here allocates or synchronises.  Compiled with -ffp-contract=off like every
+// unit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,37 +44,13 @@
 
 #include "../../include/mzgo.h"
 #include "mzgo_conv_bf16.hpp"
+#include "mzgo_train.hpp"
 #include "mzgo_unroll.hpp"
 #include "mzgo_weights.hpp"
 
-namespace mzgo {
-// mzgo_train.hip
-extern const int kConvMaxBatch;
-size_t conv_bwd_workspace_bytes(int B, int Cin, int Cout);
-size_t conv_bwd_workspace_bytes_chunk(int B, int Cin, int Cout, int cb);
-hipError_t conv_forward(const float* x, const int64_t* action, const float* emb, const float* w, const float* bias,
-                        int B, int Cin, int Cout, int N, float* y, hipStream_t s);
-hipError_t conv_backward(const float* g, const float* out, const float* x, const int64_t* action, const float* emb,
-                         const float* w, int B, int Cin, int Cout, int N, float* gx, float* gw, float* gb,
-                         void* workspace, hipStream_t s);
-hipError_t conv_backward_chunk(const float* g, const float* out, const float* x, const int64_t* action,
-                               const float* emb, const float* w, int B, int Cin, int Cout, int N, int cb, float* gx,
-                               float* gw, float* gb, void* workspace, hipStream_t s);
-hipError_t conv_bwd_reduce(const float* part, float* gw, int chunks, size_t n, hipStream_t s);
-hipError_t conv_bwd_bias(const float* g, const float* out, float* gb, int B, int Cout, int N, hipStream_t s);
-}  // namespace mzgo
-
 using namespace mzgo;
 
-#define UHIPCHK(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return set_error(MZGO_EHIP, "%s: %s", #expr, hipGetErrorString(e_));     \
-  } while (0)
-
 namespace {
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kHeadThreads = 256;
 constexpr int kMaxCells = 19 * 19;
@@ -389,55 +368,6 @@ __global__ void __launch_bounds__(64) k_unroll_heads_reduce(const float* __restr
   if (dst) *dst = s;
 }
 
-// k_conv_bwd_input (mzgo_train.hip) for one step of the chain: the dynamics
-// conv's input gradient from gp = g * [out > 0] is ADDED into gprev (the
-// previous latent's gradient, which already holds its heads' part), and the
-// tile's sum over its 16 cells goes to bsum[b][ci][tile] for the embedding.
-// grid (ceil(CELLS/16), C/16, B), one wave per block.
-__global__ void __launch_bounds__(64) k_unroll_chain(const float* __restrict__ g, const float* __restrict__ out,
-                                                     const float* __restrict__ w, float* __restrict__ gprev,
-                                                     float* __restrict__ bsum, int C, int N) {
-  const int lane = threadIdx.x;
-  const int CELLS = N * N;
-  const int b = blockIdx.z, ci0 = blockIdx.y * 16, p0 = blockIdx.x * 16;
-  const int i = lane & 15, k = lane >> 4;
-  const int p = p0 + i;                           // this lane's A row (cell)
-  const int py = p / N, px = p - py * N;
-  const bool prow = p < CELLS;
-  const int ci = ci0 + i;                         // this lane's B column (C is a multiple of 16)
-  const size_t gplane = (size_t)b * C * CELLS;
-  f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-  for (int tap = 0; tap < 9; ++tap) {
-    const int ky = tap / 3, kx = tap - ky * 3;
-    const int qy = py - ky + 1, qx = px - kx + 1;
-    const bool on = prow && qy >= 0 && qy < N && qx >= 0 && qx < N;
-    const size_t q = on ? (size_t)qy * N + qx : 0;
-    for (int co0 = 0; co0 < C; co0 += 4) {
-      const int co = co0 + k;
-      float a = 0.f;
-      if (on) {
-        const size_t idx = gplane + (size_t)co * CELLS + q;
-        a = out[idx] > 0.f ? g[idx] : 0.f;
-      }
-      const float bw = w[((size_t)co * C + ci) * 9 + tap];
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bw, acc, 0, 0, 0);
-    }
-  }
-  float t = 0.f;                                  // rows past the board are exact zeros
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int pr = p0 + (lane >> 4) * 4 + r;
-    if (pr < CELLS) {
-      const size_t idx = ((size_t)b * C + ci) * CELLS + pr;
-      gprev[idx] = gprev[idx] + acc[r];
-    }
-    t += acc[r];
-  }
-  t += __shfl_xor(t, 16, 64);
-  t += __shfl_xor(t, 32, 64);
-  if (lane < 16) bsum[((size_t)b * C + ci) * gridDim.x + blockIdx.x] = t;
-}
-
 // gemb[row][c] = the board sums of the (step, sample) pairs whose action is
 // `row`, in (step, sample) order; every other row 0.  A thread per entry.
 __global__ void __launch_bounds__(256) k_unroll_emb_grad(const float* __restrict__ bsum,
@@ -465,6 +395,39 @@ HeadW head_weights(const float* const* P) {
 HeadG head_grads(float* const* G) {
   return HeadG{G[WK_POLICY_W], G[WK_POLICY_B], G[WK_VALUE_W], G[WK_VALUE_B], G[WK_VFC_W], G[WK_VFC_B],
                G[WK_PASS_LOGIT], G[WK_REWARD_W], G[WK_REWARD_B], G[WK_FC1_W], G[WK_FC1_B], G[WK_FC2_W], G[WK_FC2_B]};
+}
+
+// The dynamics conv's weights in the call's precision, and its three matrix products on them: mzgo_train.hip's
+// float32 launchers from `w`, or mzgo_conv_bf16.hip's from `packed` (conv_bf16_pack's two layouts, in `saved`)
+struct DynConv {
+  int precision;
+  const float* w;
+  const void* packed;
+};
+
+// latent [B][C][N][N] (+ emb[action]) -> y
+hipError_t dyn_forward(const DynConv& d, const float* x, const int64_t* action, const float* emb, const float* bias,
+                       int B, int C, int N, float* y, hipStream_t s) {
+  if (d.precision == MZGO_PREC_BF16)
+    return conv_bf16_forward(x, action, emb, d.packed, nullptr, bias, B, C, C, N, y, s);
+  return conv_forward(x, action, emb, d.w, bias, B, C, C, N, y, s);
+}
+
+// a step of the chain: the input gradient from g [out > 0] ADDED into dst, its 16-cell tile sums to bsum
+hipError_t dyn_input_grad(const DynConv& d, const float* g, const float* out, int B, int C, int N, float* dst,
+                          float* bsum, hipStream_t s) {
+  if (d.precision == MZGO_PREC_BF16)
+    return conv_bf16_input_grad(g, out, d.packed, B, C, C, N, dst, 1, bsum, s);
+  return conv_input_grad(g, out, d.w, B, C, C, N, dst, 1, bsum, s);
+}
+
+// the weight gradient's partials over chunks of `cb` of the `boards` boards
+hipError_t dyn_weight_partials(const DynConv& d, const float* g, const float* out, const float* x,
+                               const int64_t* action, const float* emb, int boards, int C, int N, int cb, float* part,
+                               hipStream_t s) {
+  if (d.precision == MZGO_PREC_BF16)
+    return conv_bf16_weight_partials(g, out, x, action, emb, boards, C, C, N, cb, part, s);
+  return conv_weight_partials(g, out, x, action, emb, boards, C, C, N, cb, part, s);
 }
 
 }  // namespace
@@ -521,25 +484,19 @@ int mzgo_unroll_forward_p(const char* const* keys, const float* const* params, c
   const size_t n_obs = (size_t)B * 6 * CELLS, n_stage = std::max(n_obs, (size_t)K * B);
   hipLaunchKernelGGL(k_unroll_stage, dim3((unsigned)((n_stage + 255) / 256)), dim3(256), 0, s, obs0, n_obs, obs, acts, B,
                      K, acts_t);
-  UHIPCHK(hipGetLastError());
-  UHIPCHK(conv_forward(obs, nullptr, nullptr, P[WK_CONV1_W], P[WK_CONV1_B], B, 6, kRepC, N, x1, s));
-  UHIPCHK(conv_forward(x1, nullptr, nullptr, P[WK_CONV2_W], P[WK_CONV2_B], B, kRepC, kRepC, N, x2, s));
-  UHIPCHK(conv_forward(x2, nullptr, nullptr, P[WK_CONV3_W], P[WK_CONV3_B], B, kRepC, C, N, lat, s));
-  if (precision == MZGO_PREC_BF16 && K > 0) {
-    // R(W) once, in the forward's and the input gradient's layouts: the backward call reads them from `saved`
-    void* wpk = sv + L.s_wpk;
-    UHIPCHK(conv_bf16_pack(P[WK_DYN_W], C, C, wpk, s));
-    for (int k = 1; k <= K; ++k)
-      UHIPCHK(conv_bf16_forward(lat + (size_t)(k - 1) * L.LS, acts_t + (size_t)(k - 1) * B, P[WK_EMB], wpk, nullptr,
-                                P[WK_DYN_B], B, C, C, N, lat + (size_t)k * L.LS, s));
-  } else {
-    for (int k = 1; k <= K; ++k)
-      UHIPCHK(conv_forward(lat + (size_t)(k - 1) * L.LS, acts_t + (size_t)(k - 1) * B, P[WK_EMB], P[WK_DYN_W],
-                           P[WK_DYN_B], B, C, C, N, lat + (size_t)k * L.LS, s));
-  }
+  MZGO_HIPCHK(hipGetLastError());
+  MZGO_HIPCHK(conv_forward(obs, nullptr, nullptr, P[WK_CONV1_W], P[WK_CONV1_B], B, 6, kRepC, N, x1, s));
+  MZGO_HIPCHK(conv_forward(x1, nullptr, nullptr, P[WK_CONV2_W], P[WK_CONV2_B], B, kRepC, kRepC, N, x2, s));
+  MZGO_HIPCHK(conv_forward(x2, nullptr, nullptr, P[WK_CONV3_W], P[WK_CONV3_B], B, kRepC, C, N, lat, s));
+  // bf16: R(W) once, in the forward's and the input gradient's layouts; the backward call reads them from `saved`
+  if (precision == MZGO_PREC_BF16 && K > 0) MZGO_HIPCHK(conv_bf16_pack(P[WK_DYN_W], C, C, sv + L.s_wpk, s));
+  const DynConv dyn{precision, P[WK_DYN_W], sv + L.s_wpk};
+  for (int k = 1; k <= K; ++k)
+    MZGO_HIPCHK(dyn_forward(dyn, lat + (size_t)(k - 1) * L.LS, acts_t + (size_t)(k - 1) * B, P[WK_EMB], P[WK_DYN_B], B,
+                            C, N, lat + (size_t)k * L.LS, s));
   hipLaunchKernelGGL(k_unroll_heads, dim3((unsigned)((K + 1) * B)), dim3(kHeadThreads), 0, s, head_weights(P), lat, B, C,
                      CELLS, logits, value, reward, sv + L.s_vmean, sv + L.s_rmean);
-  UHIPCHK(hipGetLastError());
+  MZGO_HIPCHK(hipGetLastError());
   return MZGO_OK;
 }
 
@@ -581,7 +538,7 @@ int mzgo_unroll_backward_p(const char* const* keys, const float* const* params, 
   const int64_t* acts_t = reinterpret_cast<const int64_t*>(sv + L.s_acts);
   float* wk = static_cast<float*>(work);
   float *G = wk + L.w_G, *g2 = wk + L.w_g2, *g1 = wk + L.w_g1, *bsum = wk + L.w_bsum, *hp = wk + L.w_hp;
-  void* cw = wk + L.w_conv;
+  float* cw = wk + L.w_conv;                          // the conv weight partials
   const int CELLS = N * N, rows = (K + 1) * B;
   if (K == 0)                                           // (the reward head has no gradient: skipped by the reduce)
     for (int k = 0; k < WK_COUNT; ++k)
@@ -590,51 +547,36 @@ int mzgo_unroll_backward_p(const char* const* keys, const float* const* params, 
   // (a) the heads
   hipLaunchKernelGGL(k_unroll_heads_bwd, dim3((unsigned)rows), dim3(kHeadThreads), 0, s, head_weights(P), lat, g_logits,
                      g_value, g_reward, sv + L.s_vmean, sv + L.s_rmean, B, C, CELLS, G, hp);
-  UHIPCHK(hipGetLastError());
+  MZGO_HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_unroll_heads_reduce, dim3((unsigned)(3 * C + 48 + HS_COUNT)), dim3(64), 0, s, hp, rows, C,
                      head_grads(Gd));
-  UHIPCHK(hipGetLastError());
-  if (K > 0 && precision == MZGO_PREC_BF16) {
-    // (b) - (d) with the conv's products on bf16 MFMA: the chain from the packed weights the forward left in
-    // `saved`, the weight pass's partials into the same region and chunks, then the float32 reduce, bias
-    // gradient and embedding gradient as below
-    const void* wpk = sv + L.s_wpk;
+  MZGO_HIPCHK(hipGetLastError());
+  if (K > 0) {
+    // (b) the chain: step s's input gradient into step s - 1's latent gradient (bf16: from the packed weights the
+    // forward left in `saved`)
+    const DynConv dyn{precision, P[WK_DYN_W], sv + L.s_wpk};
     for (int st = K; st >= 1; --st)
-      UHIPCHK(conv_bf16_input_grad(G + (size_t)st * L.LS, lat + (size_t)st * L.LS, wpk, B, C, C, N,
-                                   G + (size_t)(st - 1) * L.LS, 1, bsum + (size_t)(st - 1) * B * C * L.CT, s));
+      MZGO_HIPCHK(dyn_input_grad(dyn, G + (size_t)st * L.LS, lat + (size_t)st * L.LS, B, C, N,
+                                 G + (size_t)(st - 1) * L.LS, bsum + (size_t)(st - 1) * B * C * L.CT, s));
+    // (c) the dynamics conv's weight and bias: steps 0..K-1 are the inputs, 1..K the outputs of K B boards; the
+    // reduce and the bias gradient are float32 in both precisions
     const int chunks = (K * B + L.dyn_cb - 1) / L.dyn_cb;
-    UHIPCHK(conv_bf16_weight_partials(G + L.LS, lat + L.LS, lat, acts_t, P[WK_EMB], K * B, C, C, N, L.dyn_cb,
-                                      static_cast<float*>(cw), s));
-    UHIPCHK(conv_bwd_reduce(static_cast<const float*>(cw), Gd[WK_DYN_W], chunks, (size_t)C * C * 9, s));
-    UHIPCHK(conv_bwd_bias(G + L.LS, lat + L.LS, Gd[WK_DYN_B], K * B, C, N, s));
-    const size_t n_emb = (size_t)emb_rows * C;
-    hipLaunchKernelGGL(k_unroll_emb_grad, dim3((unsigned)((n_emb + 255) / 256)), dim3(256), 0, s, bsum, acts_t, K * B, C,
-                       L.CT, emb_rows, Gd[WK_EMB]);
-    UHIPCHK(hipGetLastError());
-  } else if (K > 0) {
-    // (b) the chain: step s's input gradient into step s - 1's latent gradient
-    for (int st = K; st >= 1; --st) {
-      hipLaunchKernelGGL(k_unroll_chain, dim3((unsigned)L.CT, (unsigned)(C / 16), (unsigned)B), dim3(64), 0, s,
-                         G + (size_t)st * L.LS, lat + (size_t)st * L.LS, P[WK_DYN_W], G + (size_t)(st - 1) * L.LS,
-                         bsum + (size_t)(st - 1) * B * C * L.CT, C, N);
-      UHIPCHK(hipGetLastError());
-    }
-    // (c) the dynamics conv's weight and bias: steps 0..K-1 are the inputs, 1..K the outputs of K B boards
-    UHIPCHK(conv_backward_chunk(G + L.LS, lat + L.LS, lat, acts_t, P[WK_EMB], P[WK_DYN_W], K * B, C, C, N, L.dyn_cb,
-                                nullptr, Gd[WK_DYN_W], Gd[WK_DYN_B], cw, s));
+    MZGO_HIPCHK(dyn_weight_partials(dyn, G + L.LS, lat + L.LS, lat, acts_t, P[WK_EMB], K * B, C, N, L.dyn_cb, cw, s));
+    MZGO_HIPCHK(conv_bwd_reduce(cw, Gd[WK_DYN_W], chunks, (size_t)C * C * 9, s));
+    MZGO_HIPCHK(conv_bwd_bias(G + L.LS, lat + L.LS, Gd[WK_DYN_B], K * B, C, N, s));
     // (d) the embedding
     const size_t n_emb = (size_t)emb_rows * C;
     hipLaunchKernelGGL(k_unroll_emb_grad, dim3((unsigned)((n_emb + 255) / 256)), dim3(256), 0, s, bsum, acts_t, K * B, C,
                        L.CT, emb_rows, Gd[WK_EMB]);
-    UHIPCHK(hipGetLastError());
+    MZGO_HIPCHK(hipGetLastError());
   }
   // (e) the representation, from the saved activations
-  UHIPCHK(conv_backward(G, lat, x2, nullptr, nullptr, P[WK_CONV3_W], B, kRepC, C, N, g2, Gd[WK_CONV3_W],
-                        Gd[WK_CONV3_B], cw, s));
-  UHIPCHK(conv_backward(g2, x2, x1, nullptr, nullptr, P[WK_CONV2_W], B, kRepC, kRepC, N, g1, Gd[WK_CONV2_W],
-                        Gd[WK_CONV2_B], cw, s));
-  UHIPCHK(conv_backward(g1, x1, obs, nullptr, nullptr, P[WK_CONV1_W], B, 6, kRepC, N, nullptr, Gd[WK_CONV1_W],
-                        Gd[WK_CONV1_B], cw, s));
+  MZGO_HIPCHK(conv_backward(G, lat, x2, nullptr, nullptr, P[WK_CONV3_W], B, kRepC, C, N, g2, Gd[WK_CONV3_W],
+                            Gd[WK_CONV3_B], cw, s));
+  MZGO_HIPCHK(conv_backward(g2, x2, x1, nullptr, nullptr, P[WK_CONV2_W], B, kRepC, kRepC, N, g1, Gd[WK_CONV2_W],
+                            Gd[WK_CONV2_B], cw, s));
+  MZGO_HIPCHK(conv_backward(g1, x1, obs, nullptr, nullptr, P[WK_CONV1_W], B, 6, kRepC, N, nullptr, Gd[WK_CONV1_W],
+                            Gd[WK_CONV1_B], cw, s));
   return MZGO_OK;
 }
 

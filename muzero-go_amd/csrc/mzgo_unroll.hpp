@@ -73,7 +73,4 @@ __host__ __device__ __forceinline__ float heads_latent_grad(float w_pol, float g
   return w_pol * g_logit + (w_val * dvmean + w_rew * drmean) / cells;
 }
 
-// mzgo_capi.hip: set mzgo_last_error()'s text and return ``code``
-int set_error(int code, const char* fmt, ...);
-
 }  // namespace mzgo

@@ -244,7 +244,7 @@ def test_backward_refusals():
 
 
 def test_batch_above_the_grid_limit_is_refused_before_any_launch():
-    """k_conv_fwd, k_conv_bwd_input and k_unroll_chain launch a grid with z =
+    """k_conv_fwd and k_conv_bwd_input (the unroll's chain too) launch a grid with z =
     B: 65536 boards are MZGO_EINVAL from the unroll and from the three layer
     entry points, 65535 pass that check (and fail a later one here)."""
     from mzgo import _lib
