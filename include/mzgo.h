@@ -704,6 +704,98 @@ int mzgo_replay_set_priorities(mzgo_replay* replay, const double* values_host, i
 /* The number of priority updates refused so far (synchronises). */
 int mzgo_replay_skipped_updates(mzgo_replay* replay, int64_t* count_host, void* stream);
 
+/* Position-level prioritized replay (opt-in on top of the ledger above; MuZero,
+ * App. G): a sampling weight per stored POSITION, pprio f64 [capacity][max_moves]
+ * (already raised to alpha; rows t >= the game's length are never read), and a
+ * sampler that draws (game, start) with probability w[game][start] / total.
+ * Nothing is allocated until mzgo_replay_enable_positions; until then every
+ * device call below returns MZGO_EINVAL and mzgo_last_error() names it.
+ *
+ * The weight of a position whose value error is err is
+ *   pow(max(err, floor), alpha)   -- exactly max(err, floor) at alpha == 1
+ * with floor > 0 (0 selects FLT_MIN, the floor of mzgo_replay_update_priorities;
+ * a caller may raise it so that no position starves).  A new game (stored by
+ * mzgo_replay_add_games, _play_games or _add: one more small launch on their
+ * stream, k_replay_new_positions, next to the one that sets weight 1.0 and
+ * gen + 1; the games held at the time of the enabling call get the same) has
+ *   init_mode 0 (td):      err_t = |nu[t] - (double)target(t)|, target the
+ *                          search-value target of index t with n = td_steps
+ *                          under ``discount`` (above; the same function)
+ *   init_mode 1 (uniform): weight 1.0 for every position.
+ * MZGO_EINVAL: null replay; max_moves > 4096 (two levels of 64 inside a game);
+ * capacity > 64^3; td_steps < 1; discount not finite; alpha not finite or <= 0;
+ * floor negative or not finite; init_mode; a second call with other parameters
+ * (one with the same is a no-op). */
+int mzgo_replay_enable_positions(mzgo_replay* replay, int td_steps, double discount, double alpha, double floor,
+                                 int init_mode, void* stream);
+/* mzgo_replay_sample over positions.  A game's weight is not stored; it is the
+ * sum of its positions' weights in the sampler's one order of additions: rows
+ * 0..L-1 in chunks of 64, a chunk's sum element 63 of the six-step scan, the
+ * game's weight element 63 of the scan over its <= 64 chunk sums, entries past
+ * the end 0.  k_replay_possample_build (a workgroup per 64 slots) writes the
+ * leaves (that weight, 0 for a game without moves), the sums of 64 leaves and
+ * the count of stored positions n_pos; k_replay_possample_draw (one wave)
+ * descends the same three levels with the same u, rules and fallback, then
+ * carries the remainder of the same target through two more levels of the same
+ * rule -- the picked game's chunk sums (formed again, the same additions, so
+ * the same bits), then the picked chunk's 64 positions: start is the picked
+ * position (tag 6 is not drawn).  The picked game's leaf is zeroed and its
+ * ancestors summed again, so the B games are distinct; symmetry, index and gen
+ * as mzgo_replay_sample; weight f32 [B] = (n_pos w / total)^(-beta) over the
+ * batch's largest, w the picked position's weight, total the sum before any
+ * removal.  The items feed mzgo_replay_batch_items, _batch_items_values and
+ * mzgo_replay_reanalyse_sample(_values) unchanged.  MZGO_EINVAL as
+ * mzgo_replay_sample.  The _batch and _batch_values forms mirror
+ * mzgo_replay_sample_batch and mzgo_replay_sample_batch_values launch for
+ * launch (build, draw, the unchanged k_replay_batch). */
+int mzgo_replay_sample_positions(mzgo_replay* replay, int B, uint64_t seed, uint32_t step, int symmetries,
+                                 double beta, int32_t* items, int32_t* index, uint32_t* gen, float* weight,
+                                 void* stream);
+int mzgo_replay_sample_positions_batch(mzgo_replay* replay, int B, int unroll_steps, double discount, uint64_t seed,
+                                       uint32_t step, int symmetries, double beta, int32_t* items, int32_t* index,
+                                       uint32_t* gen, float* weight, float* obs0, float* boot_obs, int64_t* acts,
+                                       float* t_rew, float* t_pol, double* val, double* factor, uint8_t* has_boot,
+                                       void* stream);
+int mzgo_replay_sample_positions_batch_values(mzgo_replay* replay, int B, int unroll_steps, int td_steps,
+                                              double discount, uint64_t seed, uint32_t step, int symmetries,
+                                              double beta, int32_t* items, int32_t* index, uint32_t* gen,
+                                              float* weight, float* obs0, int64_t* acts, float* t_rew, float* t_pol,
+                                              float* t_val, void* stream);
+/* New weights for a sampled batch's windows (k_replay_update_position_priorities,
+ * a thread per (sample b, unroll step k); device pointers; no synchronisation):
+ * position t = items[b][1] + k of slot items[b][0] gets the weight of err =
+ * |(double)value[b][k] - (double)t_val[b][k]|, value and t_val f32 [B][K + 1]:
+ * the RAW value head outputs and the RAW value targets (a value transform
+ * shapes the loss, not the priority).  Left alone: a slot whose generation no
+ * longer equals gen[b], rows t >= the game's length, and an err that is NaN or
+ * infinite, which is counted (mzgo_replay_skipped_updates).  MZGO_EINVAL: null
+ * pointers; B < 1; unroll_steps outside 1..63. */
+int mzgo_replay_update_position_priorities(mzgo_replay* replay, const int32_t* items, const uint32_t* gen,
+                                           const float* value, const float* t_val, int B, int unroll_steps,
+                                           void* stream);
+/* The position weights of the games held, in logical order (oldest first),
+ * copied to a device buffer f64 [size][max_moves] (rows t >= a game's length
+ * are unspecified; no synchronisation). */
+int mzgo_replay_position_priorities(mzgo_replay* replay, double* pprio, void* stream);
+/* Set them from a host buffer f64 [n = size][max_moves] in logical order (a test
+ * hook; synchronises).  MZGO_EINVAL: n != size; an entry t < length that is
+ * negative or not finite; a game with moves whose entries are all 0 (single
+ * zeros are allowed). */
+int mzgo_replay_set_position_priorities(mzgo_replay* replay, const double* values_host, int n, void* stream);
+/* The position sampler's host twin (no device work): pprio f64 [cap][M] and
+ * length i32 [cap] in slot order; outputs as mzgo_replay_sample_host.
+ * MZGO_EINVAL as there, plus M outside 1..4096, an entry t < length that is
+ * negative or not finite, and a game with moves whose weight is not finite
+ * and > 0. */
+int mzgo_replay_sample_positions_host(const double* pprio, const int32_t* length, int cap, int M, int head, int B,
+                                      uint64_t seed, uint32_t step, int symmetries, double beta, int32_t* items,
+                                      int32_t* index, float* weight);
+/* The td rule's host twin (no device work): reward f64 [L + 1], root_value f64
+ * [L]; pprio f64 [L] receives the new-game weights.  floor 0 = FLT_MIN.
+ * MZGO_EINVAL: a null pointer; L outside 0..4096; td_steps < 1; alpha; floor. */
+int mzgo_replay_position_priorities_host(const double* reward, const double* root_value, int L, int td_steps,
+                                         double discount, double alpha, double floor, double* pprio);
+
 /* --------------------------------------------------------------------------
  * The trainer's unroll loss in one launch (main.py:431-482: the value, policy
  * and reward losses of a trajectory's K + 1 unroll steps, which the reference

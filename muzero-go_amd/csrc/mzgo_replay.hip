@@ -13,6 +13,10 @@
 // from the sampler's device items, priorities written back by a launch -- and,
 // between the draw and the assembly, the sampled windows' positions searched
 // again in place (k_replay_window_items, then the engine's in-place queue).
+// Opt-in on top of that ledger, a weight per stored position (PosLedger) and a
+// sampler that carries one draw's target through two more levels inside the
+// picked game (k_replay_possample_build, k_replay_possample_draw), with the
+// positions' weights written back from the step's value errors.
 //
 // Kernels here use plain vector loads and stores only (and one vector atomic,
 // the count of refused priority updates); workgroups never communicate.  Compiled with -ffp-contract=off like every unit: the value
@@ -377,6 +381,167 @@ __global__ void __launch_bounds__(kThreads) k_replay_update_priorities(Ledger L,
   L.prio[slot] = priority_of(p, alpha);
 }
 
+// ---------------------------------------------------------------------------
+// The position ledger (PosLedger, mzgo_replay.hpp).  New games: a thread per
+// (game, position), after the launch (or copies) that wrote the games and next
+// to k_replay_new_games: the |root value - n-step target| of the position,
+// floored and raised to alpha (POS_INIT_TD), or 1.0 (POS_INIT_UNIFORM).
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) k_replay_new_positions(Store R, PosLedger P, int first, int n) {
+  const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (e >= (long long)n * P.M) return;
+  const int i = (int)(e / P.M), t = (int)(e - (long long)i * P.M);
+  const int slot = (first + i) % P.cap;
+  const int L = R.length[slot];
+  if (t >= L) return;
+  P.pprio[(size_t)slot * P.M + t] =
+      P.init_mode == POS_INIT_UNIFORM
+          ? 1.0
+          : position_td_priority(R.reward + (size_t)slot * (R.M + 1), R.root_value + (size_t)slot * R.M, L, t,
+                                 P.td_steps, P.discount, P.floor, P.alpha);
+}
+
+// a game's weight from its position weights row[0..len), on one wave: the chunk
+// sums land a lane each (lane c: chunk c; the rest 0) in *chunks, the weight is
+// returned on every lane (len <= 64 * 64)
+__device__ __forceinline__ double wave_game_weight(const double* row, int len, int lane, double* chunks) {
+  double xc = 0.0;
+  for (int c = 0; c * 64 < len; ++c) {
+    const int t = c * 64 + lane;
+    const double s = __shfl(wave_scan64(t < len ? row[t] : 0.0, lane), 63);
+    if (lane == c) xc = s;
+  }
+  *chunks = xc;
+  return __shfl(wave_scan64(xc, lane), 63);
+}
+
+// a workgroup per group of 64 slots, a wave per 16 of them: the working leaves
+// (the games' weights), the group's sum and the group's count of positions
+__global__ void __launch_bounds__(kThreads) k_replay_possample_build(PosLedger P, const int* length) {
+  __shared__ double s_w[64];
+  __shared__ int s_len[64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = blockIdx.x;
+  for (int k = wave; k < 64; k += kThreads / 64) {
+    const int slot = g * 64 + k;                           // (uniform over the wave)
+    const int len = slot < P.cap ? min(max(length[slot], 0), P.M) : 0;
+    double chunks;
+    const double w = len > 0 ? wave_game_weight(P.pprio + (size_t)slot * P.M, len, lane, &chunks) : 0.0;
+    if (lane == 0) {
+      s_w[k] = w;
+      s_len[k] = len;
+    }
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const int i = g * 64 + lane;
+  const double x = s_w[lane];
+  if (i < P.cap) P.leaf[i] = x;
+  const double p = wave_scan64(x, lane);
+  int np = s_len[lane];
+  for (int d = 32; d > 0; d >>= 1) np += __shfl_xor(np, d);
+  if (lane == 63) {
+    P.l1[g] = p;
+    P.npos1[g] = np;
+  }
+}
+
+// k_replay_sample_draw over the games' weights, then the remainder of the same
+// target through the picked game's chunk sums and the picked chunk's positions:
+// one u picks (game, position).  One workgroup of one wave.
+__global__ void __launch_bounds__(64) k_replay_possample_draw(PosLedger P, const uint32_t* gen, const int* length,
+                                                              int head, int B, uint64_t key, int symmetries,
+                                                              double beta, SampleOut O) {
+  __shared__ double s1[64 * 64];
+  const int lane = threadIdx.x;
+  const int n1 = P.n1, n2 = (n1 + 63) / 64;
+  int n_pos = 0;
+  for (int i = lane; i < n2 * 64; i += 64) {
+    s1[i] = i < n1 ? P.l1[i] : 0.0;
+    n_pos += i < n1 ? P.npos1[i] : 0;
+  }
+  for (int d = 32; d > 0; d >>= 1) n_pos += __shfl_xor(n_pos, d);
+  if (lane == 0) *P.n_pos = n_pos;
+  __syncthreads();
+  double x2 = 0.0;                                         // lane i: level-2 entry i
+  for (int g = 0; g < n2; ++g) {
+    const double s = __shfl(wave_scan64(s1[g * 64 + lane], lane), 63);
+    if (lane == g) x2 = s;
+  }
+  double total0 = 0.0;
+  for (int t = 0; t < B; ++t) {
+    const double p2 = wave_scan64(x2, lane);
+    const double total = __shfl(p2, 63);
+    if (t == 0) total0 = total;
+    double target = sample_u(key, t) * total;
+    const int j2 = wave_pick(x2, p2, &target);
+    const double x1 = s1[j2 * 64 + lane];
+    const int j1 = wave_pick(x1, wave_scan64(x1, lane), &target);
+    const int g1 = j2 * 64 + j1, i0 = g1 * 64 + lane;
+    double x0 = i0 < P.cap ? P.leaf[i0] : 0.0;
+    const int j0 = wave_pick(x0, wave_scan64(x0, lane), &target);
+    const int slot = min(g1 * 64 + j0, P.cap - 1);
+    // remove the leaf; its two ancestors are summed again, never subtracted from
+    if (lane == j0) {
+      x0 = 0.0;
+      P.leaf[slot] = 0.0;
+    }
+    const double sum0 = __shfl(wave_scan64(x0, lane), 63);
+    const double sum1 = __shfl(wave_scan64(lane == j1 ? sum0 : x1, lane), 63);
+    if (lane == j1) s1[g1] = sum0;
+    if (lane == j2) x2 = sum1;
+    // inside the game: its chunk sums (the build's additions again), then the chunk's positions
+    const int len = min(max(length[slot], 0), P.M);
+    const double* row = P.pprio + (size_t)slot * P.M;
+    double xc;
+    (void)wave_game_weight(row, len, lane, &xc);
+    const int jc = wave_pick(xc, wave_scan64(xc, lane), &target);
+    const int tt = jc * 64 + lane;
+    const double xt = tt < len ? row[tt] : 0.0;
+    const int jt = wave_pick(xt, wave_scan64(xt, lane), &target);
+    const double w = __shfl(xt, jt);
+    if (lane == 0) {
+      O.items[3 * t] = slot;
+      O.items[3 * t + 1] = max(min(jc * 64 + jt, len - 1), 0);
+      O.items[3 * t + 2] = sample_symmetry(key, t, symmetries);
+      O.index[t] = (slot - head + P.cap) % P.cap;
+      O.gen[t] = gen[slot];
+      P.pick_w[t] = w;
+    }
+    __syncthreads();                                       // (the leaf and s1 before the next draw reads them)
+  }
+  if (!O.weight) return;
+  // importance weights over positions, from the weights before any removal, over the batch's largest
+  double vmax = 0.0;
+  for (int b = lane; b < B; b += 64) vmax = fmax(vmax, pow((double)n_pos * P.pick_w[b] / total0, -beta));
+  for (int d = 32; d > 0; d >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, d));
+  for (int b = lane; b < B; b += 64) O.weight[b] = (float)(pow((double)n_pos * P.pick_w[b] / total0, -beta) / vmax);
+}
+
+// a thread per (sample b, unroll step k): position start_b + k of the sampled
+// game gets the weight of |value - t_val| (f32 [B][K + 1] both, raw head outputs
+// and raw targets), unless the slot has taken another game since the draw or
+// the row lies past the game's end.  Samples are distinct games: no two
+// threads write one word.
+__global__ void __launch_bounds__(kThreads) k_replay_update_position_priorities(PosLedger P, const uint32_t* slot_gen,
+                                                                                unsigned* skipped, const int* length,
+                                                                                const int* items, const uint32_t* gen,
+                                                                                const float* value, const float* t_val,
+                                                                                int B, int K1) {
+  const int e = blockIdx.x * kThreads + threadIdx.x;
+  if (e >= B * K1) return;
+  const int b = e / K1, k = e - b * K1;
+  const int slot = items[3 * b], start = items[3 * b + 1];
+  if (slot < 0 || slot >= P.cap || start < 0 || slot_gen[slot] != gen[b]) return;
+  const int t = start + k;
+  if (t >= length[slot] || t >= P.M) return;
+  const double err = fabs((double)value[e] - (double)t_val[e]);
+  if (!(err <= 1.79769313486231570815e308)) {              // NaN or inf: the position keeps its weight
+    atomicAdd(skipped, 1u);
+    return;
+  }
+  P.pprio[(size_t)slot * P.M + t] = position_priority_of(err, P.floor, P.alpha);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -404,6 +569,8 @@ struct mzgo_replay {
   size_t win_cap = 0;                     // pairs win_items holds
   Ledger L{};                             // device priorities, generations and the sampler's scratch
   int n_valid = 0;                        // slots whose mirrored length is > 0 (the sampler's population)
+  PosLedger P{};                          // the position ledger (mzgo_replay_enable_positions)
+  bool positions = false;                 // whether P is allocated and kept
 
   int slot_of(int i) const { return (head + i) % R.cap; }
   void set_len(int slot, int length) {
@@ -414,6 +581,14 @@ struct mzgo_replay {
   int new_games(int first, int n, hipStream_t s) {
     if (n < 1) return MZGO_OK;
     hipLaunchKernelGGL(k_replay_new_games, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, L, first, n);
+    RHIPCHK(hipGetLastError());
+    return positions ? new_positions(first, n, s) : MZGO_OK;
+  }
+  // the position weights of the n games from ring slot ``first`` (n <= cap), from the lengths on the device
+  int new_positions(int first, int n, hipStream_t s) {
+    const long long threads = (long long)n * P.M;
+    hipLaunchKernelGGL(k_replay_new_positions, dim3((unsigned)((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       s, R, P, first, n);
     RHIPCHK(hipGetLastError());
     return MZGO_OK;
   }
@@ -953,9 +1128,22 @@ int mzgo_replay_batch_items(mzgo_replay* r, const int32_t* items, int B, int unr
   return MZGO_OK;
 }
 
-// the sampler's checks and its two launches (``who``: the entry point's name)
-static int sample_launch(mzgo_replay* r, const char* who, int B, uint64_t seed, uint32_t step, int symmetries,
-                         double beta, int32_t* items, int32_t* index, uint32_t* gen, float* weight, hipStream_t s) {
+// every device call of the position ledger on a store that has none
+static int positions_check(const mzgo_replay* r, const char* who) {
+  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
+  if (!r->positions)
+    return set_error(MZGO_EINVAL, "%s: the store keeps no position weights (call mzgo_replay_enable_positions first)",
+                     who);
+  return MZGO_OK;
+}
+
+// the sampler's checks and its two launches (``who``: the entry point's name);
+// ``positions``: the position sampler's two (mzgo_replay_sample_positions)
+static int sample_launch(mzgo_replay* r, const char* who, bool positions, int B, uint64_t seed, uint32_t step,
+                         int symmetries, double beta, int32_t* items, int32_t* index, uint32_t* gen, float* weight,
+                         hipStream_t s) {
+  if (positions)
+    if (int rc = positions_check(r, who)) return rc;
   if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
   if (r->R.cap > kSampleMaxCap)
     return set_error(MZGO_EINVAL, "%s: capacity %d exceeds the sampler's 64^3 = %d slots", who, r->R.cap,
@@ -965,21 +1153,60 @@ static int sample_launch(mzgo_replay* r, const char* who, int B, uint64_t seed, 
   if (!(beta >= 0.0) || std::isinf(beta)) return set_error(MZGO_EINVAL, "%s: beta must be finite and >= 0", who);
   if (!items || !index || !gen)
     return set_error(MZGO_EINVAL, "%s: null %s", who, !items ? "items" : !index ? "index" : "gen");
+  const SampleOut O{items, index, gen, weight};
+  const uint64_t key = stream_key(seed, kSamplerDomain, step);
+  if (positions) {
+    const PosLedger& P = r->P;
+    hipLaunchKernelGGL(k_replay_possample_build, dim3(P.n1), dim3(kThreads), 0, s, P, r->R.length);
+    RHIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_replay_possample_draw, dim3(1), dim3(64), 0, s, P, r->L.gen, r->R.length, r->head, B, key,
+                       symmetries != 0, beta, O);
+    RHIPCHK(hipGetLastError());
+    return MZGO_OK;
+  }
   const Ledger& L = r->L;
   hipLaunchKernelGGL(k_replay_sample_build, dim3((L.n1 + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads), 0, s,
                      L, r->R.length);
   RHIPCHK(hipGetLastError());
-  const SampleOut O{items, index, gen, weight};
-  hipLaunchKernelGGL(k_replay_sample_draw, dim3(1), dim3(64), 0, s, L, r->R.length, r->head, B,
-                     stream_key(seed, kSamplerDomain, step), symmetries != 0, beta, r->n_valid, O);
+  hipLaunchKernelGGL(k_replay_sample_draw, dim3(1), dim3(64), 0, s, L, r->R.length, r->head, B, key, symmetries != 0,
+                     beta, r->n_valid, O);
   RHIPCHK(hipGetLastError());
   return MZGO_OK;
+}
+
+// the three sample calls, for the game sampler and (``positions``) the position sampler
+static int sample_batch(mzgo_replay* r, const char* who, bool positions, int B, int unroll_steps, double discount,
+                        uint64_t seed, uint32_t step, int symmetries, double beta, int32_t* items, int32_t* index,
+                        uint32_t* gen, float* weight, float* obs0, float* boot_obs, int64_t* acts, float* t_rew,
+                        float* t_pol, double* val, double* factor, uint8_t* has_boot, hipStream_t s) {
+  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
+  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (1..%d)", who, unroll_steps, kMaxUnroll);
+  if (!obs0 || !boot_obs || !acts || !t_rew || !t_pol || !val || !factor || !has_boot)
+    return set_error(MZGO_EINVAL, "%s: null %s", who,
+                     !obs0 ? "obs0" : !boot_obs ? "boot_obs" : !acts ? "acts" : !t_rew ? "t_rew" : !t_pol ? "t_pol"
+                     : !val ? "val" : !factor ? "factor" : "has_boot");
+  if (int rc = sample_launch(r, who, positions, B, seed, step, symmetries, beta, items, index, gen, weight, s))
+    return rc;
+  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot, nullptr};
+  hipLaunchKernelGGL(k_replay_batch<false>, dim3(B), dim3(kThreads), 0, s, r->R, items, unroll_steps, 0, discount, O);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+static int sample_batch_values(mzgo_replay* r, const char* who, bool positions, int B, int unroll_steps, int td_steps,
+                               double discount, uint64_t seed, uint32_t step, int symmetries, double beta,
+                               int32_t* items, int32_t* index, uint32_t* gen, float* weight, float* obs0,
+                               int64_t* acts, float* t_rew, float* t_pol, float* t_val, hipStream_t s) {
+  if (int rc = values_check(r, who, B, unroll_steps, td_steps, obs0, acts, t_rew, t_pol, t_val)) return rc;
+  if (int rc = sample_launch(r, who, positions, B, seed, step, symmetries, beta, items, index, gen, weight, s))
+    return rc;
+  return values_launch(r, items, B, unroll_steps, td_steps, discount, obs0, acts, t_rew, t_pol, t_val, s);
 }
 
 int mzgo_replay_sample(mzgo_replay* r, int B, uint64_t seed, uint32_t step, int symmetries, double beta,
                        int32_t* items, int32_t* index, uint32_t* gen, float* weight, void* stream) {
   if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_sample: null replay");
-  return sample_launch(r, "mzgo_replay_sample", B, seed, step, symmetries, beta, items, index, gen, weight,
+  return sample_launch(r, "mzgo_replay_sample", false, B, seed, step, symmetries, beta, items, index, gen, weight,
                        (hipStream_t)stream);
 }
 
@@ -987,33 +1214,44 @@ int mzgo_replay_sample_batch(mzgo_replay* r, int B, int unroll_steps, double dis
                              int symmetries, double beta, int32_t* items, int32_t* index, uint32_t* gen,
                              float* weight, float* obs0, float* boot_obs, int64_t* acts, float* t_rew, float* t_pol,
                              double* val, double* factor, uint8_t* has_boot, void* stream) {
-  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_sample_batch: null replay");
-  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
-    return set_error(MZGO_EINVAL, "mzgo_replay_sample_batch: unroll_steps %d out of range (1..%d)", unroll_steps,
-                     kMaxUnroll);
-  if (!obs0 || !boot_obs || !acts || !t_rew || !t_pol || !val || !factor || !has_boot)
-    return set_error(MZGO_EINVAL, "mzgo_replay_sample_batch: null %s",
-                     !obs0 ? "obs0" : !boot_obs ? "boot_obs" : !acts ? "acts" : !t_rew ? "t_rew" : !t_pol ? "t_pol"
-                     : !val ? "val" : !factor ? "factor" : "has_boot");
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = sample_launch(r, "mzgo_replay_sample_batch", B, seed, step, symmetries, beta, items, index, gen,
-                             weight, s))
-    return rc;
-  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot, nullptr};
-  hipLaunchKernelGGL(k_replay_batch<false>, dim3(B), dim3(kThreads), 0, s, r->R, items, unroll_steps, 0, discount, O);
-  RHIPCHK(hipGetLastError());
-  return MZGO_OK;
+  return sample_batch(r, "mzgo_replay_sample_batch", false, B, unroll_steps, discount, seed, step, symmetries, beta,
+                      items, index, gen, weight, obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot,
+                      (hipStream_t)stream);
 }
 
 int mzgo_replay_sample_batch_values(mzgo_replay* r, int B, int unroll_steps, int td_steps, double discount,
                                     uint64_t seed, uint32_t step, int symmetries, double beta, int32_t* items,
                                     int32_t* index, uint32_t* gen, float* weight, float* obs0, int64_t* acts,
                                     float* t_rew, float* t_pol, float* t_val, void* stream) {
-  const char* who = "mzgo_replay_sample_batch_values";
-  if (int rc = values_check(r, who, B, unroll_steps, td_steps, obs0, acts, t_rew, t_pol, t_val)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = sample_launch(r, who, B, seed, step, symmetries, beta, items, index, gen, weight, s)) return rc;
-  return values_launch(r, items, B, unroll_steps, td_steps, discount, obs0, acts, t_rew, t_pol, t_val, s);
+  return sample_batch_values(r, "mzgo_replay_sample_batch_values", false, B, unroll_steps, td_steps, discount, seed,
+                             step, symmetries, beta, items, index, gen, weight, obs0, acts, t_rew, t_pol, t_val,
+                             (hipStream_t)stream);
+}
+
+int mzgo_replay_sample_positions(mzgo_replay* r, int B, uint64_t seed, uint32_t step, int symmetries, double beta,
+                                 int32_t* items, int32_t* index, uint32_t* gen, float* weight, void* stream) {
+  return sample_launch(r, "mzgo_replay_sample_positions", true, B, seed, step, symmetries, beta, items, index, gen,
+                       weight, (hipStream_t)stream);
+}
+
+int mzgo_replay_sample_positions_batch(mzgo_replay* r, int B, int unroll_steps, double discount, uint64_t seed,
+                                       uint32_t step, int symmetries, double beta, int32_t* items, int32_t* index,
+                                       uint32_t* gen, float* weight, float* obs0, float* boot_obs, int64_t* acts,
+                                       float* t_rew, float* t_pol, double* val, double* factor, uint8_t* has_boot,
+                                       void* stream) {
+  return sample_batch(r, "mzgo_replay_sample_positions_batch", true, B, unroll_steps, discount, seed, step, symmetries,
+                      beta, items, index, gen, weight, obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot,
+                      (hipStream_t)stream);
+}
+
+int mzgo_replay_sample_positions_batch_values(mzgo_replay* r, int B, int unroll_steps, int td_steps, double discount,
+                                              uint64_t seed, uint32_t step, int symmetries, double beta,
+                                              int32_t* items, int32_t* index, uint32_t* gen, float* weight,
+                                              float* obs0, int64_t* acts, float* t_rew, float* t_pol, float* t_val,
+                                              void* stream) {
+  return sample_batch_values(r, "mzgo_replay_sample_positions_batch_values", true, B, unroll_steps, td_steps, discount,
+                             seed, step, symmetries, beta, items, index, gen, weight, obs0, acts, t_rew, t_pol, t_val,
+                             (hipStream_t)stream);
 }
 
 int mzgo_replay_sample_host(const double* prio, const int32_t* length, int cap, int head, int B, uint64_t seed,
@@ -1144,6 +1382,210 @@ int mzgo_replay_skipped_updates(mzgo_replay* r, int64_t* count_host, void* strea
   RHIPCHK(hipMemcpyAsync(&c, r->L.skipped, sizeof(c), hipMemcpyDeviceToHost, (hipStream_t)stream));
   RHIPCHK(hipStreamSynchronize((hipStream_t)stream));
   *count_host = c;
+  return MZGO_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The position ledger's entry points
+// ---------------------------------------------------------------------------
+int mzgo_replay_enable_positions(mzgo_replay* r, int td_steps, double discount, double alpha, double floor,
+                                 int init_mode, void* stream) {
+  const char* who = "mzgo_replay_enable_positions";
+  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
+  if (r->R.M > kPositionMaxMoves)
+    return set_error(MZGO_EINVAL, "%s: max_moves %d exceeds the two levels of 64 inside a game (%d)", who, r->R.M,
+                     kPositionMaxMoves);
+  if (r->R.cap > kSampleMaxCap)
+    return set_error(MZGO_EINVAL, "%s: capacity %d exceeds the sampler's 64^3 = %d slots", who, r->R.cap,
+                     kSampleMaxCap);
+  if (td_steps < 1) return set_error(MZGO_EINVAL, "%s: td_steps must be >= 1, got %d", who, td_steps);
+  if (!std::isfinite(discount)) return set_error(MZGO_EINVAL, "%s: discount must be finite", who);
+  if (!(alpha > 0.0) || std::isinf(alpha)) return set_error(MZGO_EINVAL, "%s: alpha must be finite and > 0", who);
+  if (!(floor >= 0.0) || std::isinf(floor))
+    return set_error(MZGO_EINVAL, "%s: floor must be finite and >= 0 (0 = float32's smallest normal)", who);
+  if (init_mode != POS_INIT_TD && init_mode != POS_INIT_UNIFORM)
+    return set_error(MZGO_EINVAL, "%s: init_mode %d (0 = td, 1 = uniform)", who, init_mode);
+  if (floor == 0.0) floor = kPriorityFloor;
+  PosLedger& P = r->P;
+  if (r->positions) {
+    if (P.td_steps != td_steps || P.discount != discount || P.alpha != alpha || P.floor != floor ||
+        P.init_mode != init_mode)
+      return set_error(MZGO_EINVAL, "%s: already enabled with other parameters (td_steps %d, discount %g, alpha %g, "
+                       "floor %g, init_mode %d)", who, P.td_steps, P.discount, P.alpha, P.floor, P.init_mode);
+    return MZGO_OK;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const size_t cap = r->R.cap, M = r->R.M;
+  PosLedger Q{};
+  Q.cap = r->R.cap; Q.n1 = (r->R.cap + 63) / 64; Q.M = r->R.M;
+  Q.td_steps = td_steps; Q.init_mode = init_mode; Q.discount = discount; Q.alpha = alpha; Q.floor = floor;
+  int rc = MZGO_OK;
+  auto chk = [&](int x) { if (rc == MZGO_OK) rc = x; };
+  chk(r->alloc(&Q.pprio, cap * M));
+  chk(r->alloc(&Q.leaf, cap));
+  chk(r->alloc(&Q.l1, (size_t)Q.n1));
+  chk(r->alloc(&Q.npos1, (size_t)Q.n1));
+  chk(r->alloc(&Q.pick_w, cap));
+  chk(r->alloc(&Q.n_pos, 1));
+  if (rc != MZGO_OK) return rc;                             // (what was allocated is freed with the store)
+  RHIPCHK(hipMemsetAsync(Q.pprio, 0, cap * M * sizeof(double), s));
+  RHIPCHK(hipMemsetAsync(Q.n_pos, 0, sizeof(int), s));
+  P = Q;
+  r->positions = true;
+  // the games the store already holds: the new-game rule, from the ring's head
+  if (r->size > 0) return r->new_positions(r->head, r->size, s);
+  return MZGO_OK;
+}
+
+int mzgo_replay_update_position_priorities(mzgo_replay* r, const int32_t* items, const uint32_t* gen,
+                                           const float* value, const float* t_val, int B, int unroll_steps,
+                                           void* stream) {
+  const char* who = "mzgo_replay_update_position_priorities";
+  if (int rc = positions_check(r, who)) return rc;
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
+  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (1..%d)", who, unroll_steps, kMaxUnroll);
+  if (B > (1 << 24)) return set_error(MZGO_EINVAL, "%s: B %d exceeds 2^24", who, B);
+  if (!items || !gen || !value || !t_val)
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !items ? "items" : !gen ? "gen" : !value ? "value" : "t_val");
+  const int K1 = unroll_steps + 1;
+  hipLaunchKernelGGL(k_replay_update_position_priorities, dim3((B * K1 + kThreads - 1) / kThreads), dim3(kThreads), 0,
+                     (hipStream_t)stream, r->P, r->L.gen, r->L.skipped, r->R.length, items, gen, value, t_val, B, K1);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+int mzgo_replay_position_priorities(mzgo_replay* r, double* pprio, void* stream) {
+  const char* who = "mzgo_replay_position_priorities";
+  if (int rc = positions_check(r, who)) return rc;
+  if (!pprio) return set_error(MZGO_EINVAL, "%s: null pprio", who);
+  return copy_logical(r, pprio, r->P.pprio, (size_t)r->P.M * sizeof(double), false, hipMemcpyDeviceToDevice,
+                      (hipStream_t)stream);
+}
+
+int mzgo_replay_set_position_priorities(mzgo_replay* r, const double* values_host, int n, void* stream) {
+  const char* who = "mzgo_replay_set_position_priorities";
+  if (int rc = positions_check(r, who)) return rc;
+  if (!values_host) return set_error(MZGO_EINVAL, "%s: null values", who);
+  if (n != r->size) return set_error(MZGO_EINVAL, "%s: %d rows for the %d games held", who, n, r->size);
+  const size_t M = r->P.M;
+  for (int i = 0; i < n; ++i) {
+    const int L = r->len[r->slot_of(i)];
+    bool positive = false;
+    for (int t = 0; t < L; ++t) {
+      const double v = values_host[(size_t)i * M + t];
+      if (!(v >= 0.0) || std::isinf(v))
+        return set_error(MZGO_EINVAL, "%s: game %d, position %d: %g (finite values >= 0 only)", who, i, t, v);
+      positive = positive || v > 0.0;
+    }
+    if (L > 0 && !positive)
+      return set_error(MZGO_EINVAL, "%s: game %d has no position with a weight > 0", who, i);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = copy_logical(r, const_cast<double*>(values_host), r->P.pprio, M * sizeof(double), true,
+                            hipMemcpyHostToDevice, s))
+    return rc;
+  RHIPCHK(hipStreamSynchronize(s));                         // (the host buffer is the caller's)
+  return MZGO_OK;
+}
+
+int mzgo_replay_position_priorities_host(const double* reward, const double* root_value, int L, int td_steps,
+                                         double discount, double alpha, double floor, double* pprio) {
+  const char* who = "mzgo_replay_position_priorities_host";
+  if (L < 0 || L > kPositionMaxMoves) return set_error(MZGO_EINVAL, "%s: L %d outside 0..%d", who, L, kPositionMaxMoves);
+  if (!reward || (L > 0 && (!root_value || !pprio)))
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !reward ? "reward" : !root_value ? "root_value" : "pprio");
+  if (td_steps < 1) return set_error(MZGO_EINVAL, "%s: td_steps must be >= 1, got %d", who, td_steps);
+  if (!(alpha > 0.0) || std::isinf(alpha)) return set_error(MZGO_EINVAL, "%s: alpha must be finite and > 0", who);
+  if (!(floor >= 0.0) || std::isinf(floor)) return set_error(MZGO_EINVAL, "%s: floor must be finite and >= 0", who);
+  if (floor == 0.0) floor = kPriorityFloor;
+  for (int t = 0; t < L; ++t)
+    pprio[t] = position_td_priority(reward, root_value, L, t, td_steps, discount, floor, alpha);
+  return MZGO_OK;
+}
+
+int mzgo_replay_sample_positions_host(const double* pprio, const int32_t* length, int cap, int M, int head, int B,
+                                      uint64_t seed, uint32_t step, int symmetries, double beta, int32_t* items,
+                                      int32_t* index, float* weight) {
+  const char* who = "mzgo_replay_sample_positions_host";
+  if (cap < 1 || cap > kSampleMaxCap)
+    return set_error(MZGO_EINVAL, "%s: capacity %d outside 1..64^3 = %d", who, cap, kSampleMaxCap);
+  if (M < 1 || M > kPositionMaxMoves)
+    return set_error(MZGO_EINVAL, "%s: max_moves %d outside 1..%d", who, M, kPositionMaxMoves);
+  if (!pprio || !length || !items || !index)
+    return set_error(MZGO_EINVAL, "%s: null %s", who,
+                     !pprio ? "pprio" : !length ? "length" : !items ? "items" : "index");
+  if (head < 0 || head >= cap) return set_error(MZGO_EINVAL, "%s: head %d outside 0..%d", who, head, cap - 1);
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
+  if (!(beta >= 0.0) || std::isinf(beta)) return set_error(MZGO_EINVAL, "%s: beta must be finite and >= 0", who);
+  auto len_of = [&](int i) { return std::min(std::max(length[i], 0), M); };
+  // k_replay_possample_build and the draw kernel's prologue
+  int n_valid = 0;
+  long long n_pos = 0;
+  std::vector<double> leaf((size_t)cap);
+  double csum[64], p[64];
+  for (int i = 0; i < cap; ++i) {
+    const int L = len_of(i);
+    const double* row = pprio + (size_t)i * M;
+    for (int t = 0; t < L; ++t)
+      if (!(row[t] >= 0.0) || std::isinf(row[t]))
+        return set_error(MZGO_EINVAL, "%s: slot %d, position %d: weight %g (finite and >= 0)", who, i, t, row[t]);
+    leaf[i] = L > 0 ? game_weight_host(row, L, csum) : 0.0;
+    if (L > 0 && !(leaf[i] > 0.0 && !std::isinf(leaf[i])))
+      return set_error(MZGO_EINVAL, "%s: slot %d: the game's weight is %g (finite and > 0)", who, i, leaf[i]);
+    n_valid += L > 0;
+    n_pos += L;
+  }
+  if (B > n_valid) return set_error(MZGO_EINVAL, "%s: B %d exceeds the %d stored games that have moves", who, B, n_valid);
+  const int n1 = (cap + 63) / 64, n2 = (n1 + 63) / 64;
+  std::vector<double> l1((size_t)n2 * 64, 0.0);
+  double x2[64] = {0.0};
+  for (int g = 0; g < n1; ++g) {
+    scan64_host(leaf.data() + (size_t)g * 64, std::min(64, cap - g * 64), p);
+    l1[g] = p[63];
+  }
+  for (int g = 0; g < n2; ++g) {
+    scan64_host(l1.data() + (size_t)g * 64, 64, p);
+    x2[g] = p[63];
+  }
+  const uint64_t key = stream_key(seed, kSamplerDomain, step);
+  std::vector<double> pick_w((size_t)B);
+  double total0 = 0.0;
+  for (int t = 0; t < B; ++t) {
+    scan64_host(x2, 64, p);
+    const double total = p[63];
+    if (t == 0) total0 = total;
+    double target = sample_u(key, t) * total;
+    const int j2 = pick64_host(x2, 64, &target);
+    const int j1 = pick64_host(l1.data() + (size_t)j2 * 64, 64, &target);
+    const int g1 = j2 * 64 + j1;
+    const int n0 = std::max(0, std::min(64, cap - g1 * 64));
+    const int j0 = pick64_host(leaf.data() + (size_t)g1 * 64, n0, &target);
+    const int slot = std::min(g1 * 64 + j0, cap - 1);
+    leaf[slot] = 0.0;
+    scan64_host(leaf.data() + (size_t)g1 * 64, n0, p);
+    l1[g1] = p[63];
+    scan64_host(l1.data() + (size_t)j2 * 64, 64, p);
+    x2[j2] = p[63];
+    // inside the game: its chunk sums, then the chunk's positions
+    const int L = len_of(slot);
+    const double* row = pprio + (size_t)slot * M;
+    (void)game_weight_host(row, L, csum);
+    const int jc = pick64_host(csum, 64, &target);
+    const int nt = std::max(0, std::min(64, L - jc * 64));
+    const int jt = pick64_host(nt > 0 ? row + (size_t)jc * 64 : row, nt, &target);
+    const int start = std::max(std::min(jc * 64 + jt, L - 1), 0);
+    pick_w[t] = jt < nt ? row[(size_t)jc * 64 + jt] : 0.0;
+    items[3 * t] = slot;
+    items[3 * t + 1] = start;
+    items[3 * t + 2] = sample_symmetry(key, t, symmetries != 0);
+    index[t] = (slot - head + cap) % cap;
+  }
+  if (weight) {
+    double vmax = 0.0;
+    for (int b = 0; b < B; ++b) vmax = std::max(vmax, std::pow((double)n_pos * pick_w[b] / total0, -beta));
+    for (int b = 0; b < B; ++b) weight[b] = (float)(std::pow((double)n_pos * pick_w[b] / total0, -beta) / vmax);
+  }
   return MZGO_OK;
 }
 

@@ -4,7 +4,8 @@
 // ring's arrays and the ingest of one game (a device function: the store's
 // own ingest kernel and k_selfplay_games run the same text), the device
 // priority ledger and the sampler's order of additions, descent rule and
-// fallback (host and device: the sampler's host twin runs them), the window
+// fallback (host and device: the sampler's host twin runs them), the position
+// ledger and its weight rules (host and device likewise), the window
 // of a sample and the item list of a batch's windows (host and device
 // likewise) with the in-place reanalysis queue's arguments, the search-value
 // target rule and the value rows it reads (host and device), and the engine's
@@ -265,11 +266,56 @@ __host__ __device__ __forceinline__ int sample_start(uint64_t key, int t, int le
 __host__ __device__ __forceinline__ int sample_symmetry(uint64_t key, int t, int symmetries) {
   return symmetries ? (int)randbelow(draw(key, TAG_SYM, (uint64_t)t), 8u) : 0;
 }
+constexpr double kPriorityFloor = 1.17549435082228750797e-38;   // float32's smallest normal
 // the stored priority of a loss ``p`` (finite, >= 0): floored at float32's
 // smallest normal, then raised to alpha (exactly the floored value at alpha 1)
 __host__ __device__ __forceinline__ double priority_of(double p, double alpha) {
-  const double v = p > 1.17549435082228750797e-38 ? p : 1.17549435082228750797e-38;
+  const double v = p > kPriorityFloor ? p : kPriorityFloor;
   return alpha == 1.0 ? v : pow(v, alpha);
+}
+
+// ---------------------------------------------------------------------------
+// The position ledger (opt-in: mzgo_replay_enable_positions): a sampling weight
+// per stored POSITION, and a sampler that draws (game, start) with probability
+// w[game][start] / total (mzgo_replay.hip: k_replay_new_positions,
+// k_replay_possample_*, k_replay_update_position_priorities).  Kept apart from
+// Store and Ledger, which the existing kernels take by value; allocated only
+// when enabled.  The generations and the count of refused updates are Ledger's.
+//
+// A game's weight is not stored: it is formed from rows 0 .. L - 1 of its pprio
+// row in the sampler's one order of additions -- chunks of 64 positions, a
+// chunk's sum element 63 of the six-step scan, the game's weight element 63 of
+// the scan over its <= 64 chunk sums, entries past the end 0 -- by the build
+// kernel and again by the draw, so both hold the same bits.
+// ---------------------------------------------------------------------------
+constexpr int kPositionMaxMoves = 64 * 64;         // two levels of 64 inside a game
+enum : int { POS_INIT_TD = 0, POS_INIT_UNIFORM = 1 };
+struct PosLedger {
+  int cap, n1, M;      // slots; level-1 entries = ceil(cap / 64); max_moves (pprio's row length)
+  int td_steps;        // the n of a new position's |root value - n-step target|
+  int init_mode;       // POS_INIT_TD, or POS_INIT_UNIFORM: 1.0 for every new position
+  double discount, alpha, floor;
+  double* pprio;       // [cap][M]  position t's sampling weight (already raised to alpha); rows t >= length: never read
+  double* leaf;        // [cap]  sampler scratch: length > 0 ? the game's weight : 0, picked leaves zeroed
+  double* l1;          // [n1]   sampler scratch: the sums of 64 leaves
+  int* npos1;          // [n1]   sampler scratch: the moves of 64 slots' games
+  double* pick_w;      // [cap]  sampler scratch: the picked positions' weights, in draw order
+  int* n_pos;          // [1]    the stored positions at the last draw (the sum of npos1)
+};
+// the stored weight of a position whose value error is ``err`` (finite, >= 0):
+// floored, then raised to alpha (exactly the floored value at alpha 1)
+__host__ __device__ __forceinline__ double position_priority_of(double err, double floor, double alpha) {
+  const double v = err > floor ? err : floor;
+  return alpha == 1.0 ? v : pow(v, alpha);
+}
+// a new position's weight under POS_INIT_TD: position t of a game of L moves
+// (reward [L + 1], root_value [L]), from search_value_target itself
+__host__ __device__ __forceinline__ double position_td_priority(const double* reward, const double* root_value, int L,
+                                                                int t, int td_steps, double discount, double floor,
+                                                                double alpha) {
+  const double err = fabs(root_value[t] - (double)search_value_target(reward, root_value, L, t, td_steps, discount));
+  // (a stored value that is not finite: the floor, so that the position can still be drawn)
+  return position_priority_of(err <= 1.79769313486231570815e308 ? err : floor, floor, alpha);
 }
 
 // host serial forms of the scan and of one level's pick (the twin's)
@@ -294,6 +340,19 @@ inline int pick64_host(const double* x, int n, double* target) {
   const int j = pick_entry(over, nonzero);
   *target = *target - (j > 0 ? p[j - 1] : 0.0);
   return j;
+}
+
+// host serial form of a game's weight from its position weights row[0..L): the
+// <= 64 chunk sums in csum[64] (the rest 0), the weight returned
+inline double game_weight_host(const double* row, int L, double* csum) {
+  double p[64];
+  for (int c = 0; c < 64; ++c) csum[c] = 0.0;
+  for (int c = 0; c < 64 && c * 64 < L; ++c) {
+    scan64_host(row + (size_t)c * 64, L - c * 64 < 64 ? L - c * 64 : 64, p);
+    csum[c] = p[63];
+  }
+  scan64_host(csum, 64, p);
+  return p[63];
 }
 
 // mzgo_capi.hip: fill *v from an engine (no checks beyond the null pointer)

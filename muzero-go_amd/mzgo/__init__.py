@@ -18,7 +18,10 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
   (``reanalyse``) or exactly the rows a drawn sample reads (``reanalyse_sample``,
   ``TrainConfig.reanalyse_sample``; ``window_items_host`` states the rule on the host);
   opt-in search-value targets from the stored root values (``batch_values``,
-  ``TrainConfig.value_target="search"``, ``td_steps``; ``value_targets_host`` is the rule)
+  ``TrainConfig.value_target="search"``, ``td_steps``; ``value_targets_host`` is the rule);
+  opt-in position-level prioritized replay (``enable_position_priorities``, ``sample_positions``,
+  ``update_position_priorities``, ``TrainConfig.position_priorities``; ``sample_positions_host``
+  and ``position_priorities_host`` are the rules)
 * ``unroll_loss`` -- the trainer's value / policy / reward losses of a whole unroll, their
   per-sample sums and the heads' gradients from one kernel (``TrainConfig.fused_loss``)
 * ``unroll`` -- the trainer's whole K-step unroll (representation, dynamics chain, the heads of
@@ -39,7 +42,8 @@ from .loss import unroll_loss, unroll_loss_host
 from .net import MuZeroNet
 from .optim import DeviceAdam, adam_step_host, optim_chunk
 from .reanalyse import Reanalyser, positions_from_planes, record_ids
-from .replay import DeviceReplay, queue_key_gids, value_targets_host, window_items_host
+from .replay import (DeviceReplay, position_priorities_host, queue_key_gids, sample_positions_host,
+                     value_targets_host, window_items_host)
 from .resnet import ResMuZeroNet
 from .search import MCTS, MainMCTS, MuZeroAgent
 from .selfplay import GameHistory, SelfPlay, history_from_device, save_batches
@@ -50,4 +54,5 @@ __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "
            "GameHistory", "history_from_device", "save_batches", "deterministic_state_dict", "SelfPlayEvaluator",
            "ResMuZeroNet", "deterministic_res_state_dict", "MzgoError", "Reanalyser",
            "positions_from_planes", "record_ids", "DeviceReplay", "queue_key_gids", "unroll_loss",
-           "unroll_loss_host", "unroll", "unroll_heads_host", "bf16_round_host", "window_items_host", "value_targets_host", "DeviceAdam", "adam_step_host", "optim_chunk"]
+           "unroll_loss_host", "unroll", "unroll_heads_host", "bf16_round_host", "window_items_host", "value_targets_host",
+           "sample_positions_host", "position_priorities_host", "DeviceAdam", "adam_step_host", "optim_chunk"]

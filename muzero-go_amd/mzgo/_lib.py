@@ -138,6 +138,20 @@ SIGNATURES = {
     "mzgo_replay_priorities": (_I, [_P, _P, _P, _P]),
     "mzgo_replay_set_priorities": (_I, [_P, _P, _I, _P]),
     "mzgo_replay_skipped_updates": (_I, [_P, _P, _P]),
+    "mzgo_replay_enable_positions": (_I, [_P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P]),
+    "mzgo_replay_sample_positions": (_I, [_P, _I, ctypes.c_uint64, ctypes.c_uint32, _I, ctypes.c_double, _P, _P, _P,
+                                          _P, _P]),
+    "mzgo_replay_sample_positions_batch": (_I, [_P, _I, _I, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _I,
+                                                ctypes.c_double] + [_P] * 13),
+    "mzgo_replay_sample_positions_batch_values": (_I, [_P, _I, _I, _I, ctypes.c_double, ctypes.c_uint64,
+                                                       ctypes.c_uint32, _I, ctypes.c_double] + [_P] * 10),
+    "mzgo_replay_update_position_priorities": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
+    "mzgo_replay_position_priorities": (_I, [_P, _P, _P]),
+    "mzgo_replay_set_position_priorities": (_I, [_P, _P, _I, _P]),
+    "mzgo_replay_sample_positions_host": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_uint64, ctypes.c_uint32, _I,
+                                               ctypes.c_double, _P, _P, _P]),
+    "mzgo_replay_position_priorities_host": (_I, [_P, _P, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                  _P]),
     "mzgo_unroll_loss": (_I, [_P] * 6 + [_I] * 3 + [ctypes.c_float] * 3 + [_I] + [_P] * 6),
     "mzgo_unroll_loss_host": (_I, [_P] * 6 + [_I] * 3 + [ctypes.c_float] * 3 + [_I] + [_P] * 5),
     "mzgo_unroll_workspace": (_I, [_I] * 5 + [ctypes.POINTER(ctypes.c_int64)] * 2),

@@ -37,6 +37,16 @@ a generation per slot -- with a sampler on the GPU (``sample_batch``,
 sampling without replacement from a 64-ary sum tree, with a priority exponent
 and importance weights, nothing on the host but the count of games.  The two
 ledgers are independent: neither reads or writes the other.
+
+Opt-in on top of the device ledger, position-level prioritized replay
+(MuZero, App. G; ``enable_position_priorities``, ``sample_positions`` /
+``sample_positions_batch`` / ``sample_positions_batch_values``,
+``update_position_priorities``, ``position_priorities``;
+``TrainConfig.position_priorities``): a weight per stored position, one draw
+picking (game, start) with probability proportional to it, importance weights
+over positions, and the sampled windows' weights rewritten from the step's
+|value - target|.  ``sample_positions_host`` and ``position_priorities_host``
+are the rules without a GPU.
 """
 import ctypes
 
@@ -140,6 +150,46 @@ def sample_host(prio, length, head, batch_size, *, seed, step, symmetries=False,
                                       int(step) & 0xFFFFFFFF, int(bool(symmetries)), float(beta), ptr(items),
                                       ptr(index), ptr(weight)))
     return dict(items=items, index=index, weight=weight)
+
+
+def sample_positions_host(pprio, length, head, batch_size, *, seed, step, symmetries=False, beta=0.0):
+    """The position sampler's host twin (mzgo_replay_sample_positions_host: the
+    kernels' own scan, descent and fallback functions run serially; no GPU).
+    ``pprio`` f64 [cap, M] (position weights, rows t >= length unread) and
+    ``length`` i32 [cap] are per ring SLOT, ``head`` is the slot of logical
+    game 0.  Returns ``sample_host``'s dict; ``items[:, 1]`` is the drawn
+    position."""
+    pprio = np.ascontiguousarray(np.asarray(pprio, dtype=np.float64))
+    length = np.ascontiguousarray(np.asarray(length, dtype=np.int32).reshape(-1))
+    if pprio.ndim != 2 or len(pprio) != len(length):
+        raise ValueError("sample_positions_host: pprio is [cap, M] and length has one entry per slot")
+    B = int(batch_size)
+    items = np.empty((max(B, 0), 3), np.int32)
+    index = np.empty(max(B, 0), np.int32)
+    weight = np.empty(max(B, 0), np.float32)
+    check(lib.mzgo_replay_sample_positions_host(ptr(pprio), ptr(length), pprio.shape[0], pprio.shape[1], int(head), B,
+                                                int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF,
+                                                int(bool(symmetries)), float(beta), ptr(items), ptr(index),
+                                                ptr(weight)))
+    return dict(items=items, index=index, weight=weight)
+
+
+def position_priorities_host(rewards, root_values, td_steps, discount, alpha=1.0, floor=None):
+    """The weights a new game's positions get under ``init="td"``
+    (mzgo_replay_position_priorities_host: the fill kernel's own rule, no GPU):
+    f64 [L], entry t = ``max(|root_values[t] - target_t|, floor) ** alpha`` with
+    target_t the search-value target of index t (``value_targets_host``'s
+    float32, widened) and ``floor`` = float32's smallest normal by default."""
+    r = np.ascontiguousarray(np.asarray(rewards, dtype=np.float64).reshape(-1))
+    rv = np.ascontiguousarray(np.asarray(root_values, dtype=np.float64).reshape(-1))
+    if len(r) != len(rv) + 1:
+        raise ValueError(f"position_priorities_host: a game of L moves has L + 1 rewards and L root values, got "
+                         f"{len(r)} and {len(rv)}")
+    out = np.empty(len(rv), np.float64)
+    check(lib.mzgo_replay_position_priorities_host(ptr(r), ptr(rv) if len(rv) else None, len(rv), int(td_steps),
+                                                   float(discount), float(alpha), 0.0 if floor is None else float(floor),
+                                                   ptr(out) if len(rv) else None))
+    return out
 
 
 def window_items_host(length, items, unroll_steps, td_steps=None):
@@ -549,6 +599,119 @@ class DeviceReplay:
         length[slots] = lengths
         return sample_host(prio, length, head.value, batch_size, seed=seed, step=step, symmetries=symmetries,
                            beta=beta)
+
+    # ---- position-level priorities (opt-in on top of the device ledger) ----
+    def enable_position_priorities(self, td_steps, discount, alpha=1.0, floor=None, init="td"):
+        """Keep a sampling weight per stored position (MuZero's prioritized
+        replay, App. G; mzgo_replay_enable_positions): f64 [capacity,
+        max_moves] on the device, allocated here.  A position's weight is
+        ``max(err, floor) ** alpha`` (``floor``: float32's smallest normal by
+        default; raise it so that no position starves).  With ``init="td"`` a
+        new game's positions start from err = |root value - n-step search-value
+        target| (n = ``td_steps``, under ``discount``:
+        ``position_priorities_host`` is the rule), with ``init="uniform"`` from
+        1.0; the games already held get the same.  A second call with the same
+        parameters is a no-op, with others an error."""
+        if init not in ("td", "uniform"):
+            raise ValueError(f"init must be 'td' or 'uniform', not {init!r}")
+        check(lib.mzgo_replay_enable_positions(self._h, int(td_steps), float(discount), float(alpha),
+                                               0.0 if floor is None else float(floor), int(init == "uniform"),
+                                               stream_of(self.device)))
+
+    def sample_positions(self, batch_size, *, seed, step, symmetries=False, beta=0.0):
+        """``sample`` over positions (mzgo_replay_sample_positions, two
+        launches, nothing on the host): ``batch_size`` distinct games, game s
+        from position t with probability w[s, t] / total on the first draw --
+        one uniform picks both.  ``sample``'s tensors; ``items[:, 1]`` is the
+        drawn position and ``weight`` the importance weights over positions,
+        (n_positions w / total) ** -beta over the batch's largest."""
+        B = int(batch_size)
+        s = self._sample_out(B)
+        check(lib.mzgo_replay_sample_positions(self._h, B, int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF,
+                                               int(bool(symmetries)), float(beta), ptr(s["items"]), ptr(s["index"]),
+                                               ptr(s["gen"]), ptr(s["weight"]), stream_of(self.device)))
+        return s
+
+    def sample_positions_batch(self, batch_size, unroll_steps, discount, *, seed, step, symmetries=False, beta=0.0):
+        """``sample_batch`` with the position sampler's draw
+        (mzgo_replay_sample_positions_batch)."""
+        B, K = int(batch_size), int(unroll_steps)
+        out = self._batch_out(B, K)
+        out.update(self._sample_out(B))
+        check(lib.mzgo_replay_sample_positions_batch(self._h, B, K, float(discount), int(seed) & (2 ** 64 - 1),
+                                                     int(step) & 0xFFFFFFFF, int(bool(symmetries)), float(beta),
+                                                     ptr(out["items"]), ptr(out["index"]), ptr(out["gen"]),
+                                                     ptr(out["weight"]), ptr(out["obs0"]), ptr(out["boot_obs"]),
+                                                     ptr(out["acts"]), ptr(out["t_rew"]), ptr(out["t_pol"]),
+                                                     ptr(out["val"]), ptr(out["factor"]), ptr(out["has_boot"]),
+                                                     stream_of(self.device)))
+        return out
+
+    def sample_positions_batch_values(self, batch_size, unroll_steps, td_steps, discount, *, seed, step,
+                                      symmetries=False, beta=0.0):
+        """``sample_batch_values`` with the position sampler's draw
+        (mzgo_replay_sample_positions_batch_values)."""
+        B, K = int(batch_size), int(unroll_steps)
+        out = self._values_out(B, K)
+        out.update(self._sample_out(B))
+        check(lib.mzgo_replay_sample_positions_batch_values(self._h, B, K, int(td_steps), float(discount),
+                                                            int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF,
+                                                            int(bool(symmetries)), float(beta), ptr(out["items"]),
+                                                            ptr(out["index"]), ptr(out["gen"]), ptr(out["weight"]),
+                                                            ptr(out["obs0"]), ptr(out["acts"]), ptr(out["t_rew"]),
+                                                            ptr(out["t_pol"]), ptr(out["t_val"]),
+                                                            stream_of(self.device)))
+        return out
+
+    def update_position_priorities(self, sample, value, t_val):
+        """New position weights for a sampled batch's windows
+        (mzgo_replay_update_position_priorities): position start_b + k of
+        sample b's game gets ``max(|value[b, k] - t_val[b, k]|, floor) **
+        alpha`` from ``value`` and ``t_val``, CUDA f32 [B, K + 1] -- the raw
+        value head outputs and the raw value targets (``use_value_transform``
+        shapes the loss, not the priority).  Rows past the game's end and
+        slots that have taken a newer game since the draw are left alone; so
+        is an error that is NaN or infinite, which is counted
+        (``skipped_updates``).  No synchronisation."""
+        B = sample["items"].shape[0]
+        value = value.detach().to(self.device, torch.float32).contiguous()
+        t_val = t_val.detach().to(self.device, torch.float32).contiguous()
+        if value.dim() != 2 or value.shape[0] != B or value.shape[1] < 2 or t_val.shape != value.shape:
+            raise ValueError(f"update_position_priorities: value and t_val are [B, K + 1] with B = {B}, got "
+                             f"{tuple(value.shape)} and {tuple(t_val.shape)}")
+        check(lib.mzgo_replay_update_position_priorities(self._h, ptr(sample["items"]), ptr(sample["gen"]), ptr(value),
+                                                         ptr(t_val), B, value.shape[1] - 1, stream_of(self.device)))
+
+    def position_priorities(self):
+        """The position weights of the games held: f64 CUDA tensor
+        [len(self), max_moves] in logical order (oldest first); entries t >= a
+        game's length are unspecified."""
+        out = torch.empty(len(self), self.max_moves, dtype=torch.float64, device=self.device)
+        check(lib.mzgo_replay_position_priorities(self._h, ptr(out), stream_of(self.device)))
+        return out
+
+    def set_position_priorities(self, values):
+        """Set the position weights of the games held ([len(self), max_moves],
+        logical order; a test hook): finite entries >= 0, and every game with
+        moves keeps at least one entry > 0 among its positions."""
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.float64))
+        if v.ndim != 2 or v.shape[1] != self.max_moves:
+            raise ValueError(f"set_position_priorities: values are [games, max_moves = {self.max_moves}], got {v.shape}")
+        check(lib.mzgo_replay_set_position_priorities(self._h, ptr(v), len(v), stream_of(self.device)))
+
+    def sample_positions_host(self, batch_size, *, seed, step, symmetries=False, beta=0.0):
+        """The position sampler's host twin on this store's present position
+        weights (copied back) and lengths: numpy ``items``, ``index``,
+        ``weight``."""
+        size, head = ctypes.c_int32(), ctypes.c_int32()
+        check(lib.mzgo_replay_info(self._h, ctypes.byref(size), ctypes.byref(head), None, None))
+        lengths, _ = self._info()
+        slots = (head.value + np.arange(size.value)) % self.capacity
+        pprio, length = np.zeros((self.capacity, self.max_moves)), np.zeros(self.capacity, np.int32)
+        pprio[slots] = self.position_priorities().cpu().numpy()
+        length[slots] = lengths
+        return sample_positions_host(pprio, length, head.value, batch_size, seed=seed, step=step,
+                                     symmetries=symmetries, beta=beta)
 
     # ---- reanalysis in place ----
     def reanalyse(self, reanalyser, games=None):

@@ -104,6 +104,18 @@ on the device, every game of a batch at once) and trains on it:
   bootstrap observations, no ``initial_inference``, no ``finish_values``; with
   ``reanalyse_sample`` the searched rows include those the value targets read.
 
+  ``TrainConfig.position_priorities`` (default off; ``device_sampling``) is
+  MuZero's own prioritized replay (paper, App. G) in place of the per-game
+  weights: the store keeps a weight per stored position, the sampler draws
+  (game, start) with probability proportional to it
+  (``DeviceReplay.sample_positions*``; importance weights over positions), and
+  after the loss the sampled windows' positions get ``max(|value - target|,
+  priority_floor) ** priority_alpha`` from the step's raw value outputs and
+  raw value targets (``update_position_priorities``; ``use_value_transform``
+  shapes the loss, not the priority) in place of the per-game update.  A new
+  game's positions start from |root value - n-step search-value target|, n =
+  ``td_steps`` (``unroll_steps`` under network targets).
+
 ``initial_inference_torch`` / ``recurrent_inference_torch`` restate
 main.py:72-144 with torch ops on the module's own parameters (reference
 mode, and the CPU).  Replay buffers restate main.py:158-244.
@@ -150,6 +162,8 @@ class TrainConfig:
     value_target: str = "network"     # "network": main.py's bootstrap; "search": the stored root values (batched mode)
     td_steps: int = 0                 # value_target="search": the n-step horizon; 0 = unroll_steps
     unroll_precision: str = "fp32"    # fused_unroll: "bf16" runs the dynamics conv's products on bf16 MFMA
+    position_priorities: bool = False  # device_sampling: sample positions by |value - target| (MuZero, App. G)
+    priority_floor: float = 0.0       # position_priorities: the smallest value error a weight is formed from; 0 = FLT_MIN
 
 
 def reward_value_transform(x, epsilon=0.001):
@@ -516,6 +530,14 @@ class MuZeroTrainer:
                              "(TrainConfig.device_sampling=True)")
         if c.importance_beta < 0 or not c.priority_alpha > 0:
             raise ValueError("importance_beta must be >= 0 and priority_alpha > 0")
+        if c.position_priorities and not c.device_sampling:
+            raise ValueError("position_priorities needs device_sampling (TrainConfig.device_sampling=True) in "
+                             "mode='batched': the position weights live in the DeviceReplay's device ledger")
+        if not c.position_priorities and c.priority_floor != 0.0:
+            raise ValueError("priority_floor belongs to position_priorities (TrainConfig.position_priorities=True)")
+        if not (0.0 <= c.priority_floor < float("inf")):
+            raise ValueError(f"priority_floor must be finite and >= 0 (0 = float32's smallest normal), got "
+                             f"{c.priority_floor}")
         if c.unroll_precision not in ("fp32", "bf16"):
             raise ValueError(f"unroll_precision must be 'fp32' or 'bf16', not {c.unroll_precision!r}")
         if c.unroll_precision == "bf16":
@@ -808,16 +830,23 @@ class MuZeroTrainer:
         from .replay import finish_values
         c, N, td = self.config, self.net.board_size, self.td_steps
         draw = dict(seed=self.sample_seed, step=self.sample_step, symmetries=c.symmetries, beta=c.importance_beta)
+        sample, sample_batch, sample_batch_values = replay.sample, replay.sample_batch, replay.sample_batch_values
+        if c.position_priorities:
+            # (a no-op after the first step; the store refuses other parameters than it was enabled with)
+            replay.enable_position_priorities(td or c.unroll_steps, c.discount, alpha=c.priority_alpha,
+                                              floor=c.priority_floor or None)
+            sample, sample_batch, sample_batch_values = (replay.sample_positions, replay.sample_positions_batch,
+                                                         replay.sample_positions_batch_values)
         if c.reanalyse_sample and self.sample_step % c.reanalyse_every == 0:
-            s = replay.sample(batch_size, **draw)
+            s = sample(batch_size, **draw)
             self.reanalyser.refresh()
             self.last_searched_device = replay.reanalyse_sample(self.reanalyser, s, c.unroll_steps, td_steps=td)
             s.update(replay.batch_from(s, c.unroll_steps, c.discount) if td is None
                      else replay.batch_values_from(s, c.unroll_steps, td, c.discount))
         elif td is None:
-            s = replay.sample_batch(batch_size, c.unroll_steps, c.discount, **draw)
+            s = sample_batch(batch_size, c.unroll_steps, c.discount, **draw)
         else:
-            s = replay.sample_batch_values(batch_size, c.unroll_steps, td, c.discount, **draw)
+            s = sample_batch_values(batch_size, c.unroll_steps, td, c.discount, **draw)
         self.sample_step += 1
         if td is None:
             with torch.no_grad():
@@ -831,13 +860,17 @@ class MuZeroTrainer:
         self._scheduler_step()
         return avg
 
-    def _finish_device(self, device_sample, per, totals, B, lr):
+    def _finish_device(self, device_sample, per, totals, B, lr, value=None, t_val=None):
         """The tail of a device-sampled step: the priorities from ``per`` (f32
-        [B], unweighted) or the batch mean, and the totals (f64 [4], unweighted)
-        left on the device for ``read_stats``."""
+        [B], unweighted) or the batch mean -- with ``position_priorities`` the
+        sampled windows' position weights from ``value`` and ``t_val`` (f32
+        [B, K+1]: the raw value outputs and targets) instead -- and the totals
+        (f64 [4], unweighted) left on the device for ``read_stats``."""
         replay, sample = device_sample
         c = self.config
-        if c.sample_priorities:
+        if c.position_priorities:
+            replay.update_position_priorities(sample, value, t_val)
+        elif c.sample_priorities:
             replay.update_device_priorities(sample, per, c.priority_alpha)
         else:
             replay.update_device_priorities(sample, alpha=c.priority_alpha, mean=totals[:1] / B)
@@ -967,8 +1000,11 @@ class MuZeroTrainer:
         p_l = c.policy_loss_weight * kl(logits, t_pol[:, 0])
         per = v_l + p_l
         tot_v, tot_p, tot_r = tot(v_l), tot(p_l), 0.0
+        values = [value.detach()] if c.position_priorities else None     # the raw value outputs of the K + 1 steps
         for k in range(1, K + 1):
             reward, value, logits = next(steps)
+            if values is not None:
+                values.append(value.detach())
             r_l = c.reward_loss_weight * F.mse_loss(reward, t_rew[:, k - 1], reduction="none")
             v_l = c.value_loss_weight * self._value_loss(value, t_val[:, k])
             p_l = c.policy_loss_weight * kl(logits, t_pol[:, k])
@@ -983,7 +1019,8 @@ class MuZeroTrainer:
         if device_sample is not None:
             d = per.detach()
             totals = torch.stack([d.sum().double(), tot_v, tot_p, tot_r])
-            return self._finish_device(device_sample, d, totals, B, lr)
+            value = torch.stack(values, dim=1) if values is not None else None
+            return self._finish_device(device_sample, d, totals, B, lr, value, t_val)
         if device_totals and c.sample_priorities:
             back = torch.cat([torch.stack([loss.detach().double(), tot_v, tot_p, tot_r]),
                               per.detach().double()]).tolist()
@@ -1056,7 +1093,8 @@ class MuZeroTrainer:
         lr = self._optimizer_step()
         self.last_per_sample = None
         if device_sample is not None:
-            return self._finish_device(device_sample, per.detach(), totals, B, lr)
+            value = vals.detach().t().contiguous() if c.position_priorities else None    # [K+1, B] -> [B, K+1]
+            return self._finish_device(device_sample, per.detach(), totals, B, lr, value, t_val)
         if c.sample_priorities:
             back = torch.cat([totals, per.detach().double()]).tolist()
             self.last_per_sample = np.asarray(back[4:], dtype=np.float32)

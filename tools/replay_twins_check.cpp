@@ -1,5 +1,7 @@
 // replay_twins_check.cpp -- the replay store's two search-value host twins,
-// mzgo_replay_value_targets_host and mzgo_replay_window_items_values_host
+// mzgo_replay_value_targets_host and mzgo_replay_window_items_values_host, and
+// the position ledger's two, mzgo_replay_sample_positions_host and
+// mzgo_replay_position_priorities_host
 // (csrc/mzgo_replay.hip), called from a stand-alone host program so that the C
 // wrappers themselves -- their vectors, the index clamp, the writes into the
 // caller's buffers -- can run under AddressSanitizer and UBSan on a machine
@@ -166,6 +168,64 @@ int main() {
     CHECK(mzgo_replay_window_items_values_host(length, 1, items, 1, 3, 0, out, &n) == MZGO_EINVAL);
     CHECK(mzgo_replay_window_items_values_host(length, 1, items, 1, 3, INT_MIN, out, &n) == MZGO_EINVAL);
   }
-  printf("ok: %ld targets, %ld pairs\n", targets, pairs);
+
+  // ---- mzgo_replay_sample_positions_host and mzgo_replay_position_priorities_host ----
+  long draws = 0, weights = 0;
+  const int lens[] = {0, 1, 2, 63, 64, 65, 127, 128, 129, 130};
+  for (int cap : {1, 63, 64, 65, 130, 4097})
+    for (int M : {1, 64, 130, 4096}) {
+      if (M == 4096 && cap > 65) continue;
+      std::vector<double> w((size_t)cap * M);              // exactly [cap][M]
+      std::vector<int32_t> length(cap);
+      int valid = 0;
+      for (int i = 0; i < cap; ++i) {
+        length[i] = std::min(lens[rand() % 10] * (M == 4096 ? 31 : 1), M);
+        valid += length[i] > 0;
+        for (int t = 0; t < M; ++t) w[(size_t)i * M + t] = rand() % 4 ? (rand() % 1000 + 1) * 1e-3 : 0.0;
+        if (length[i] > 0) w[(size_t)i * M + rand() % length[i]] = 1.0;
+      }
+      if (!valid) { length[0] = M; w[0] = 1.0; valid = 1; }
+      for (int B : {1, valid}) {
+        std::vector<int32_t> items((size_t)B * 3, -1), index(B, -1);
+        std::vector<float> weight(B, -1.f);
+        CHECK(mzgo_replay_sample_positions_host(w.data(), length.data(), cap, M, cap / 3, B, 5, (uint32_t)draws, 1, 0.5,
+                                                items.data(), index.data(), weight.data()) == MZGO_OK);
+        std::set<int> seen;
+        for (int b = 0; b < B; ++b) {
+          const int s = items[3 * b], t = items[3 * b + 1];
+          CHECK(s >= 0 && s < cap && t >= 0 && t < length[s] && w[(size_t)s * M + t] > 0.0);
+          CHECK(items[3 * b + 2] >= 0 && items[3 * b + 2] < 8 && index[b] == (s - cap / 3 + cap) % cap);
+          CHECK(weight[b] > 0.f && weight[b] <= 1.f && seen.insert(s).second);
+          ++draws;
+        }
+      }
+      CHECK(mzgo_replay_sample_positions_host(w.data(), length.data(), cap, M, 0, valid + 1, 5, 0, 0, 0.0, nullptr,
+                                              nullptr, nullptr) == MZGO_EINVAL);
+    }
+  for (int L : {0, 1, 2, 54, 4096}) {
+    std::vector<double> r(L + 1), nu(L), out(L, -1.0);     // exactly L weights
+    for (auto& x : r) x = unit();
+    for (auto& x : nu) x = unit();
+    for (int n : {1, 5, L + 3, INT_MAX})
+      for (double floor : {0.0, 0.25}) {
+        CHECK(mzgo_replay_position_priorities_host(r.data(), L ? nu.data() : nullptr, L, n, 0.99, 1.0, floor,
+                                                   L ? out.data() : nullptr) == MZGO_OK);
+        for (int t = 0; t < L; ++t) {
+          const double err = std::fabs(nu[t] - (double)restated(r, nu, t, n, 0.99));
+          const double fl = floor == 0.0 ? 1.17549435082228750797e-38 : floor;
+          CHECK(out[t] == (err > fl ? err : fl));
+          ++weights;
+        }
+      }
+  }
+  {
+    double r[2] = {1.0, 2.0}, nu[1] = {0.5}, out[1];
+    CHECK(mzgo_replay_position_priorities_host(nullptr, nu, 1, 1, 0.99, 1.0, 0.0, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_position_priorities_host(r, nu, 4097, 1, 0.99, 1.0, 0.0, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_position_priorities_host(r, nu, 1, 0, 0.99, 1.0, 0.0, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_position_priorities_host(r, nu, 1, 1, 0.99, 0.0, 0.0, out) == MZGO_EINVAL);
+    CHECK(mzgo_replay_position_priorities_host(r, nu, 1, 1, 0.99, 1.0, -1.0, out) == MZGO_EINVAL);
+  }
+  printf("ok: %ld targets, %ld pairs, %ld draws, %ld weights\n", targets, pairs, draws, weights);
   return 0;
 }
