@@ -78,6 +78,19 @@ typedef struct mzgo_config {
                                the dynamics, the reference's heads), bf16 MFMA with fp32
                                accumulation, latent_dim a multiple of 64, N in {5, 9, 19} */
   int res_blocks;           /* residual blocks per tower network (tower = 1) */
+  int fast_simulations;     /* playout cap randomization (KataGo): 0 = off (default); F in
+                               1..num_simulations = a self-play move is searched with F
+                               simulations instead of num_simulations with probability
+                               1 - full_search_prob, and its record's flags carry bit3.  A
+                               fast search is the same search with fewer simulations (same
+                               noise, temperature and move rule).  Self-play moves only
+                               (mzgo_selfplay_move(s), mzgo_replay_play_games): mzgo_search,
+                               mzgo_reanalyse, mzgo_replay_reanalyse* and the arena always
+                               search with num_simulations.  Refused on tower engines;
+                               board-only engines ignore it */
+  double full_search_prob;  /* probability of a full search, in [0, 1]; default 1.0.  The
+                               choice is mzgo_playout_budget_host's, a pure function of
+                               (seed, key game id, move) */
 } mzgo_config;
 
 typedef struct mzgo_engine mzgo_engine;
@@ -87,6 +100,17 @@ void mzgo_default_config(mzgo_config* cfg, int board_size);
 
 int mzgo_engine_create(const mzgo_config* cfg, mzgo_engine** out);
 void mzgo_engine_destroy(mzgo_engine* eng);
+/* The simulations of self-play move `move` of the game with key id key_gid
+ * ((game_base + g) ^ (epoch << 24)) under playout cap randomization -- the
+ * function the self-play kernels run, on the host, no device work:
+ *   *budget = num_simulations                  if fast_simulations == 0
+ *           = num_simulations                  if u01(draw(stream_key(seed, key_gid, move), 8, 0)) < full_search_prob
+ *           = fast_simulations                 otherwise
+ * u01 is in [0, 1): full_search_prob 1.0 is always full, 0.0 always fast.
+ * MZGO_EINVAL for a null budget, num_simulations < 1, fast_simulations
+ * outside 0..num_simulations, move < 0 or full_search_prob outside [0, 1]. */
+int mzgo_playout_budget_host(uint64_t seed, uint32_t key_gid, int move, int num_simulations, int fast_simulations,
+                             double full_search_prob, int* budget);
 const char* mzgo_last_error(void);
 /* Bytes of device memory the engine owns. */
 int64_t mzgo_engine_device_bytes(const mzgo_engine* eng);
@@ -153,7 +177,9 @@ int mzgo_search(mzgo_engine* eng, const float* root_obs, const double* noise, in
  * current weights and search parameters.  All pointers are device pointers.
  * Position i is given in the self-play record format (mzgo_records_export):
  * stones i8 [n][N*N] (0 / 1 black / 2 white), invd u8 [n][N*N], flags u8 [n]
- * (bit0 turn, bit1 passed, bit2 done), and ids i32 [n][2] = (key game id, move
+ * (bit0 turn, bit1 passed, bit2 done; bit3: searched with the fast budget,
+ * which reanalysis ignores -- it always searches with num_simulations), and
+ * ids i32 [n][2] = (key game id, move
  * index): the search's RNG streams are keyed by (seed, ids[i][0], ids[i][1]).
  * The key game id of a self-play record is (game_base + g) ^ (epoch << 24);
  * with it and the record's move index the search is the record's own.  noise
@@ -370,7 +396,8 @@ int mzgo_tower_record_nodes(mzgo_engine* eng, float* dst);
 /* Copy slot g's game record to host buffers (synchronises ``stream``).
  * length: moves recorded; ended: 1 if the game ended by double pass; status.
  * stones i8 [M][N*N], invd u8 [M][N*N], flags u8 [M] (bit0 turn, bit1 passed,
- * bit2 done), action i32 [M], value f64 [M], policy f64 [M][A], reward f64 [M],
+ * bit2 done, bit3: searched with the fast budget -- playout cap randomization,
+ * mzgo_config::fast_simulations), action i32 [M], value f64 [M], policy f64 [M][A], reward f64 [M],
  * final_reward f64.  M = length; NULL pointers are skipped. */
 int mzgo_records_export(mzgo_engine* eng, int g, int32_t* length_host, int32_t* status_host,
                         int8_t* stones_host, uint8_t* invd_host, uint8_t* flags_host,
@@ -469,14 +496,19 @@ int mzgo_replay_add_games(mzgo_replay* replay, mzgo_engine* eng, void* stream);
 int mzgo_replay_play_games(mzgo_replay* replay, mzgo_engine* eng, int n_games, int first_epoch, void* stream);
 /* Add one game from host buffers (synchronises ``stream``): stones i8
  * [L+1][C], invd u8 [L+1][C], flags u8 [L+1], action i32 [L], policy f64
- * [L][A], reward f64 [L+1], root_value f64 [L] (NULL = zeros).
+ * [L][A], reward f64 [L+1], root_value f64 [L] (NULL = zeros).  The flags are
+ * stored as given (bit0 turn, bit1 passed, bit2 done; bit3: searched with the
+ * fast budget -- such a position's t_pol row is all zero in every batch until
+ * a reanalysis into the store rewrites the row and clears the bit).
  * MZGO_EINVAL: null replay or required buffer; length outside 0..max_moves. */
 int mzgo_replay_add(mzgo_replay* replay, int length, const int8_t* stones_host, const uint8_t* invd_host,
                     const uint8_t* flags_host, const int32_t* action_host, const double* policy_host,
                     const double* reward_host, const double* root_value_host, int32_t key_gid, void* stream);
 /* Copy logical game i to host buffers sized for max_moves (the shapes of
  * mzgo_replay_add with L = max_moves; NULL pointers are skipped; synchronises
- * ``stream``).  MZGO_EINVAL: null replay; i outside 0..size-1. */
+ * ``stream``).  flags: bit0 turn, bit1 passed, bit2 done, bit3: searched with
+ * the fast budget and not reanalysed since (never set on the final board's
+ * row L).  MZGO_EINVAL: null replay; i outside 0..size-1. */
 int mzgo_replay_export(mzgo_replay* replay, int i, int32_t* length_host, int32_t* key_gid_host, int8_t* stones_host,
                        uint8_t* invd_host, uint8_t* flags_host, int32_t* action_host, double* policy_host,
                        double* reward_host, double* root_value_host, void* stream);
@@ -491,7 +523,10 @@ int mzgo_replay_export(mzgo_replay* replay, int i, int32_t* length_host, int32_t
  *   acts i64 [B][K]                the actions from ``start``; pass (A-1) past the end
  *   t_rew f32 [B][K]               the rewards from ``start``; 0 past the winner
  *   t_pol f32 [B][K+1][A]          the stored f64 rows rounded to f32;
- *                                  (float)(1.0 / A) past the end
+ *                                  (float)(1.0 / A) past the end; ALL ZERO for a
+ *                                  position whose flags carry bit3 (searched with
+ *                                  the fast budget: no policy target -- the loss
+ *                                  and its gradient are exactly 0 on such a row)
  *   val, factor f64 [B][K+1]       compute_target_value's reward part and the
  *                                  bootstrap's weight: target += factor * r;
  *                                  factor *= discount, in that order in f64,
@@ -519,7 +554,9 @@ int mzgo_replay_finish_values(const double* val, const double* factor, const uin
 /* Reanalysis in place: search the L stored positions of the given logical
  * games (games_host NULL: every game) under ``eng``'s weights and search
  * parameters, position t of a game keyed (key_gid, t), queued latest move
- * first; the fresh policy rows and root values replace the stored ones.  The
+ * first; the fresh policy rows and root values replace the stored ones, and
+ * bit3 of every rewritten row's flags is cleared (it is a full-budget target
+ * now; mzgo_replay_reanalyse_sample* do the same for the rows they search).  The
  * positions are gathered into staging the store owns, searched by
  * mzgo_reanalyse (whose conditions and errors apply) and scattered back:
  * nothing but the item list (slot, move) crosses the bus.

@@ -364,6 +364,17 @@ struct mzgo_engine {
     sp.lazy_rows = lz && atoi(lz) == 0 ? 0 : 1;
     sp.value_cache = value_cache;
     sp.arrival_conv = arrival_conv;
+    sp.fast_simulations = 0;                          // searches, reanalysis, the arena: always S
+    sp.full_search_prob = 1.0;
+    return sp;
+  }
+  // ... of a self-play launch: the playout caps of the configuration (move_budget, mzgo_move.hpp)
+  SearchParams selfplay_params() const {
+    SearchParams sp = search_params();
+    if (!tower && cfg.full_search_prob < 1.0) {       // (p = 1: every move is full, the caps are off)
+      sp.fast_simulations = cfg.fast_simulations;
+      sp.full_search_prob = cfg.full_search_prob;
+    }
     return sp;
   }
 };
@@ -397,6 +408,28 @@ void mzgo_default_config(mzgo_config* c, int N) {
   c->temperature = 1.0;
   c->komi = 0.0;
   c->seed = 1234;
+  c->fast_simulations = 0;
+  c->full_search_prob = 1.0;
+}
+
+int mzgo_playout_budget_host(uint64_t seed, uint32_t key_gid, int move, int num_simulations, int fast_simulations,
+                             double full_search_prob, int* budget) {
+  if (!budget) return fail(MZGO_EINVAL, "mzgo_playout_budget_host: null budget");
+  if (num_simulations < 1 || move < 0)
+    return fail(MZGO_EINVAL, "mzgo_playout_budget_host: num_simulations %d must be >= 1 and move %d >= 0",
+                num_simulations, move);
+  if (fast_simulations < 0 || fast_simulations > num_simulations)
+    return fail(MZGO_EINVAL, "fast_simulations must be in 0..num_simulations (%d), got %d", num_simulations,
+                fast_simulations);
+  if (!(full_search_prob >= 0.0 && full_search_prob <= 1.0))
+    return fail(MZGO_EINVAL, "full_search_prob must be in [0, 1], got %g", full_search_prob);
+  SearchParams sp{};
+  sp.seed = seed;
+  sp.num_simulations = num_simulations;
+  sp.fast_simulations = fast_simulations;
+  sp.full_search_prob = full_search_prob;
+  *budget = playout_budget(sp, key_gid, move);
+  return MZGO_OK;
 }
 
 int mzgo_engine_create(const mzgo_config* cfg, mzgo_engine** out) {
@@ -420,6 +453,15 @@ int mzgo_engine_create(const mzgo_config* cfg, mzgo_engine** out) {
   if (cfg->num_games < 1) return fail(MZGO_EINVAL, "num_games must be >= 1");
   if (C != 0 && cfg->num_simulations < 1) return fail(MZGO_EINVAL, "num_simulations must be >= 1");
   if (cfg->compat != 0 && cfg->compat != 1) return fail(MZGO_EINVAL, "compat must be 0 or 1");
+  if (C != 0) {                                       // (board-only engines search nothing: both fields ignored)
+    if (cfg->fast_simulations < 0 || cfg->fast_simulations > cfg->num_simulations)
+      return fail(MZGO_EINVAL, "fast_simulations must be in 0..num_simulations (%d), got %d", cfg->num_simulations,
+                  cfg->fast_simulations);
+    if (!(cfg->full_search_prob >= 0.0 && cfg->full_search_prob <= 1.0))
+      return fail(MZGO_EINVAL, "full_search_prob must be in [0, 1], got %g", cfg->full_search_prob);
+    if (TW && cfg->fast_simulations > 0)
+      return fail(MZGO_EINVAL, "fast_simulations > 0 (playout cap randomization) is not supported on tower engines");
+  }
   if (cfg->direct_dynamics != 0 && cfg->direct_dynamics != 1)
     return fail(MZGO_EINVAL, "direct_dynamics must be 0 (factored expansion) or 1 (a conv per simulation)");
   if (cfg->search_variant != 0 && cfg->search_variant != 1)
@@ -894,7 +936,7 @@ static bool move_parallel(const mzgo_engine* e, const SearchParams& sp, const Pl
 }
 
 static int launch_selfplay(mzgo_engine* e, const NetParams& np_b, const PlayParams& pp, hipStream_t s) {
-  SearchParams sp = e->search_params();
+  SearchParams sp = pp.arena ? e->search_params() : e->selfplay_params();   // (the arena: no playout caps)
   if (move_parallel(e, sp, pp)) {
     hipEvent_t* ev = nullptr;
     if (e->timing) {
@@ -967,7 +1009,7 @@ bool mzgo::engine_noise_hooked(const mzgo_engine* e) { return e->noise != nullpt
 int mzgo::engine_play_games(mzgo_engine* e, const GamesArgs& ga, hipStream_t s) {
   int rc = e->sync_weights();
   if (rc) return rc;
-  const SearchParams sp = e->search_params();          // (no helpers, no tail phase, network 0)
+  const SearchParams sp = e->selfplay_params();        // (no helpers, no tail phase, network 0)
   PlayParams pp = play_params(e, 0, e->M);
   pp.epoch = ga.epoch0;                                // (the kernel derives every game's own epoch from it)
   pp.noise = nullptr;

@@ -57,7 +57,9 @@ struct Geo {
 //   key  = mix64(mix64(seed) ^ (game << 32 | move))
 //   draw = mix64(key ^ (tag << 56) ^ idx)
 // ---------------------------------------------------------------------------
-enum : uint32_t { TAG_SELECT = 1, TAG_DIRICHLET = 2, TAG_ACTION = 3, TAG_WEIGHT = 4 };
+// (TAG_BUDGET: a self-play move's playout cap, idx 0 -- playout_budget, mzgo_search.hpp.  Its
+// number is used by no other draw: 5-7 are the replay sampler's, mzgo_replay.hpp.)
+enum : uint32_t { TAG_SELECT = 1, TAG_DIRICHLET = 2, TAG_ACTION = 3, TAG_WEIGHT = 4, TAG_BUDGET = 8 };
 
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;

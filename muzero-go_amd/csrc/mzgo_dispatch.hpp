@@ -75,17 +75,30 @@ struct Launch {
   }
   static hipError_t move(const NetParams& np, const NetParams& np_b, const SearchParams& sp,
                          const PlayParams& pp, const EngineArrays& E, int G, hipStream_t s) {
-    hipLaunchKernelGGL((k_selfplay_move<N, C>), dim3(G + sp.helpers), dim3(Geo<N, C>::THREADS), 0, s, np, np_b, sp,
-                       pp, E);
+    // (playout caps, sp.fast_simulations > 0, have kernel instantiations of their own: the ones without
+    // are the code an engine without caps always ran)
+    if (sp.fast_simulations > 0)
+      hipLaunchKernelGGL((k_selfplay_move<N, C, true>), dim3(G + sp.helpers), dim3(Geo<N, C>::THREADS), 0, s, np, np_b,
+                         sp, pp, E);
+    else
+      hipLaunchKernelGGL((k_selfplay_move<N, C>), dim3(G + sp.helpers), dim3(Geo<N, C>::THREADS), 0, s, np, np_b, sp,
+                         pp, E);
     return hipGetLastError();
   }
   static hipError_t boards(const SearchParams& sp, const PlayParams& pp, const EngineArrays& E, int G, hipStream_t s) {
-    hipLaunchKernelGGL((k_selfplay_boards<N, C>), dim3(G), dim3(BoardsGeo<Geo<N, C>>::THREADS), 0, s, sp, pp, E);
+    if (sp.fast_simulations > 0)
+      hipLaunchKernelGGL((k_selfplay_boards<N, C, true>), dim3(G), dim3(BoardsGeo<Geo<N, C>>::THREADS), 0, s, sp, pp, E);
+    else
+      hipLaunchKernelGGL((k_selfplay_boards<N, C>), dim3(G), dim3(BoardsGeo<Geo<N, C>>::THREADS), 0, s, sp, pp, E);
     return hipGetLastError();
   }
   static hipError_t queue(const NetParams& np, const SearchParams& sp, const PlayParams& pp, const EngineArrays& E,
                           int G, int workgroups, hipStream_t s) {
-    hipLaunchKernelGGL((k_search_queue<N, C>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, pp, E, G);
+    if (sp.fast_simulations > 0)
+      hipLaunchKernelGGL((k_search_queue<N, C, true>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, pp, E,
+                         G);
+    else
+      hipLaunchKernelGGL((k_search_queue<N, C>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, pp, E, G);
     return hipGetLastError();
   }
   static hipError_t reanalyse(const NetParams& np, const SearchParams& sp, const EngineArrays& E,
@@ -100,7 +113,11 @@ struct Launch {
   }
   static hipError_t games(const NetParams& np, const SearchParams& sp, const PlayParams& pp, const EngineArrays& E,
                           const GamesArgs& ga, int workgroups, hipStream_t s) {
-    hipLaunchKernelGGL((k_selfplay_games<N, C>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, pp, E, ga);
+    if (sp.fast_simulations > 0)
+      hipLaunchKernelGGL((k_selfplay_games<N, C, true>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, pp, E,
+                         ga);
+    else
+      hipLaunchKernelGGL((k_selfplay_games<N, C>), dim3(workgroups), dim3(Geo<N, C>::THREADS), 0, s, np, sp, pp, E, ga);
     return hipGetLastError();
   }
   static KernelSet table() {

@@ -1680,11 +1680,15 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
 // launches store game g of one epoch in slot g.)  All threads; returns
 // whether the game is over (finish_move).  The kernels that play whole games
 // a workgroup each call this: k_selfplay_move and k_selfplay_games.
+// CAPS: the launch set playout caps (SearchParams::fast_simulations > 0): the
+// move's simulations are move_budget's; without it the instantiation is the
+// code it was before the caps existed (the budget is sp.num_simulations at
+// compile time), so an engine without caps pays nothing for them.
 // (The id is a callable, evaluated where the key is formed: as a value
 // computed by the caller it is live across the move's laundered arguments,
 // and k_selfplay_move<19,96> spilled a second VGPR, 8 -> 12 B/lane.)
 // ---------------------------------------------------------------------------
-template <class G, class KeyId>
+template <class G, bool CAPS, class KeyId>
 __device__ __forceinline__ bool selfplay_one_move(Smem<G>& sm, const NetParams& np_a_arg, const NetParams& np_b_arg,
                                                   const SearchParams& sp, const PlayParams& pp,
                                                   const EngineArrays& E_arg, int g, KeyId key_id, BoardMeta& m) {
@@ -1705,8 +1709,11 @@ __device__ __forceinline__ bool selfplay_one_move(Smem<G>& sm, const NetParams& 
   // arguments would copy both to scratch)
   const NetParams np = select_params(pp.arena && (((pp.game_base + g) + mv) & 1), np_b, np_a);
   const size_t rec = (size_t)g * E.max_moves + mv;
-  record_observation<G>(E, rec, sm.stone, sm.invd, m);
   const uint64_t key = move_key(sp, key_id(), mv);
+  // playout cap randomization: this move's simulations, the engine's unless
+  // the launch set a fast budget (wave-uniform: a scalar register)
+  const int budget = move_budget<CAPS>(sp, key);
+  record_observation<G>(E, rec, sm.stone, sm.invd, m, CAPS && budget != sp.num_simulations);
   const BoardMeta m0 = m;
   const double* noise = pp.noise ? pp.noise + ((size_t)g * E.max_moves + mv) * G::A : nullptr;
   double* noise_out = pp.noise_out ? pp.noise_out + ((size_t)g * E.max_moves + mv) * G::A : nullptr;
@@ -1715,6 +1722,7 @@ __device__ __forceinline__ bool selfplay_one_move(Smem<G>& sm, const NetParams& 
 #endif
   SearchParams spm = launder_search(sp);
   spm.net = (pp.arena && (((pp.game_base + g) + mv) & 1)) ? 1 : 0;
+  if constexpr (CAPS) spm.num_simulations = budget;
   run_search<G>(sm, np, spm, E, g, [&](int c, int j) { return board_plane<G>(sm.stone, sm.invd, m0, c, j); },
                 noise, key, tm ? tm + 2 : nullptr, noise_out);
 #ifdef MZGO_STAMPS
@@ -1750,7 +1758,7 @@ __device__ __forceinline__ bool selfplay_one_move(Smem<G>& sm, const NetParams& 
     sl[90] += tm[2] - tm[6];                     //   conv3 + heads
   }
 #endif
-  return finish_move<G>(E, sp, g, rec, st, m, w);
+  return finish_move<G>(E, budget, g, rec, st, m, w);
 }
 
 // ---------------------------------------------------------------------------
@@ -1758,7 +1766,7 @@ __device__ __forceinline__ bool selfplay_one_move(Smem<G>& sm, const NetParams& 
 // body, self_play.py:465-507): record the observation, search, choose, step
 // the board, record the result; finish the game on double pass or N*N moves.
 // ---------------------------------------------------------------------------
-template <int N, int C>
+template <int N, int C, bool CAPS = false>
 __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_waves_per_eu(Geo<N, C>::WPE, Geo<N, C>::WPE))) k_selfplay_move(NetParams np_a_arg, NetParams np_b_arg,
                                                              SearchParams sp, PlayParams pp, EngineArrays E_arg) {
   typedef Geo<N, C> G;
@@ -1823,7 +1831,7 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
   // them): a game's moves run back to back on its CU instead of every move of
   // every game waiting for the slowest game's move at a launch boundary
   for (int step = 0; step < pp.moves; ++step) {
-    if (selfplay_one_move<G>(sm, np_a_arg, np_b_arg, sp, pp, E_arg, g,
+    if (selfplay_one_move<G, CAPS>(sm, np_a_arg, np_b_arg, sp, pp, E_arg, g,
                              [&]() { return game_key_id(pp.game_base, g, pp.epoch); }, m))
       break;
     __syncthreads();                               // this move's LDS reads before the next move's writes
@@ -1864,7 +1872,7 @@ struct BoardsSmem {
   int bc[8];
 };
 
-template <int N, int C>
+template <int N, int C, bool CAPS = false>
 __global__ void __launch_bounds__((BoardsGeo<Geo<N, C>>::THREADS)) k_selfplay_boards(SearchParams sp, PlayParams pp,
                                                                                     EngineArrays E) {
   typedef Geo<N, C> G;
@@ -1886,9 +1894,10 @@ __global__ void __launch_bounds__((BoardsGeo<Geo<N, C>>::THREADS)) k_selfplay_bo
   for (int step = 0; step < pp.moves; ++step) {
     const int mv = m.moves;
     const size_t rec = (size_t)g * E.max_moves + mv;
-    record_observation<G, T>(E, rec, sm.stone, sm.invd, m);
-    ++played;
     const uint64_t key = move_key(sp, pp, g, mv);
+    const int budget = move_budget<CAPS>(sp, key);       // (k_search_queue derives the same from the same key)
+    record_observation<G, T>(E, rec, sm.stone, sm.invd, m, CAPS && budget != sp.num_simulations);
+    ++played;
     build_mask<G, T>(sm.t, sp.pass_epsilon, [&](int a) { return sm.invd[a]; });
     if (wave_id() == 0) {
       // (the host launches this schedule for search variant 0 only: choose_move_action's self_play.py arm)
@@ -1901,7 +1910,7 @@ __global__ void __launch_bounds__((BoardsGeo<Geo<N, C>>::THREADS)) k_selfplay_bo
     __syncthreads();
     double w;
     const int st = play_action<G, T>(E, g, b, m, sm.bc[0], pp.komi, w);
-    if (finish_move<G, T>(E, sp, g, rec, st, m, w)) break;
+    if (finish_move<G, T>(E, budget, g, rec, st, m, w)) break;
     __syncthreads();                               // this move's LDS reads before the next move's writes
   }
   if (tid == 0) {
@@ -1923,7 +1932,7 @@ __global__ void __launch_bounds__((BoardsGeo<Geo<N, C>>::THREADS)) k_selfplay_bo
 // (a game's whole remaining move sequence on one CU while the others idle)
 // shrinks to one search.
 // ---------------------------------------------------------------------------
-template <int N, int C>
+template <int N, int C, bool CAPS = false>
 __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_waves_per_eu(Geo<N, C>::WPE, Geo<N, C>::WPE))) k_search_queue(NetParams np_arg, SearchParams sp, PlayParams pp,
                                                             EngineArrays E_arg, int games) {
   typedef Geo<N, C> G;
@@ -1967,6 +1976,7 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
     double* noise_out = pp.noise_out ? pp.noise_out + rec * G::A : nullptr;
     SearchParams spm = launder_search(sp);
     spm.net = 0;
+    if constexpr (CAPS) spm.num_simulations = move_budget<CAPS>(sp, key);   // the budget k_selfplay_boards recorded
     run_search<G>(sm, np, spm, E, slot, [&](int c, int jj) { return board_plane<G>(sm.stone, sm.invd, m0, c, jj); },
                   noise, key, nullptr, noise_out);
     if (tid_local() == 0) E.rec_value[rec] = root_value(TreeViewOf<G>::make(E, slot));
@@ -2013,8 +2023,13 @@ struct ReanalyseArgs {
 // key_gid[slot], t) -- mzgo_replay_reanalyse's for the same position -- and the
 // policy row and root value go straight into the store's: no visits, no
 // staging.  A search reads position rows and writes policy and value rows,
-// never the other way round, so distinct items share nothing; the queue head
-// stays the only word two workgroups touch.
+// never the other way round, with one exception: it clears bit 3 (kFlagFast)
+// of the flags byte of the position row it read.  Bits 0-2, all a search
+// reads of that byte, never change, and every writer of a row stores the same
+// byte, so a row listed twice (overlapping windows) may be read by one
+// workgroup while another clears its bit without either seeing a difference.
+// Otherwise distinct items share nothing; the queue head stays the only word
+// two workgroups contend for.
 // ---------------------------------------------------------------------------
 template <int N, int C, bool INPLACE = false>
 __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_waves_per_eu(Geo<N, C>::WPE, Geo<N, C>::WPE))) k_reanalyse_queue(NetParams np_arg, SearchParams sp,
@@ -2052,7 +2067,12 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
                     nullptr, key);
       const TreeView T = TreeViewOf<G>::make(E, slot);
       const size_t o = (size_t)rs * ra.R.M + t;
-      if (tid_local() == 0) launder_global(ra.R.root_value)[o] = root_value(T);
+      if (tid_local() == 0) {
+        launder_global(ra.R.root_value)[o] = root_value(T);
+        // the row is a full-budget search's now: no longer a fast one (a row listed twice gets the same byte twice)
+        uint8_t* fl = launder_global(ra.R.flags) + q;
+        if (*fl & kFlagFast) *fl = (uint8_t)(*fl & ~kFlagFast);
+      }
       if (wave_id() == 0) {
         double vc[G::AP], msum;
         visit_policy<G>(sm.t, T, sp.variant, 1, launder_global(ra.R.policy) + o * G::A, vc, msum);
@@ -2123,7 +2143,7 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
 // share one word, the queue head.  The ingest reads what this workgroup's own
 // threads stored, so the barrier before it (workgroup scope) is all it needs.
 // ---------------------------------------------------------------------------
-template <int N, int C>
+template <int N, int C, bool CAPS = false>
 __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_waves_per_eu(Geo<N, C>::WPE, Geo<N, C>::WPE))) k_selfplay_games(NetParams np_arg, SearchParams sp, PlayParams pp,
                                                               EngineArrays E_arg, GamesArgs ga) {
   typedef Geo<N, C> G;
@@ -2148,7 +2168,7 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
     BoardMeta m{0, 0, 0, 0};
     __syncthreads();
     for (int step = 0; step < pp.moves; ++step) {
-      if (selfplay_one_move<G>(sm, np_arg, np_arg, sp, pp, E_arg, slot, [&]() { return kid; }, m)) break;
+      if (selfplay_one_move<G, CAPS>(sm, np_arg, np_arg, sp, pp, E_arg, slot, [&]() { return kid; }, m)) break;
       __syncthreads();                             // this move's LDS reads before the next move's writes
     }
     __syncthreads();                               // the game's record and board: every thread's stores

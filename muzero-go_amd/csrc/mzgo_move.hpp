@@ -46,7 +46,7 @@ struct EngineArrays {
   // self-play records
   int8_t* rec_stones;    // [G][M][CELLS]
   uint8_t* rec_invd;     // [G][M][CELLS]
-  uint8_t* rec_flags;    // [G][M]   bit0 turn, bit1 passed, bit2 done
+  uint8_t* rec_flags;    // [G][M]   bit0 turn, bit1 passed, bit2 done, bit3 searched with the fast budget
   int* rec_action;       // [G][M]
   double* rec_value;     // [G][M]
   double* rec_policy;    // [G][M][A]
@@ -146,15 +146,21 @@ __device__ __forceinline__ BoardMeta flags_unpack(int fl, int mv) {
   return BoardMeta{fl & 1, (fl >> 1) & 1, (fl >> 2) & 1, mv};
 }
 
-// record ``rec`` (= g * max_moves + move) <- the board before the move
+// bit 3 of a record's flags: the move was searched with the fast budget
+// (playout cap randomization), so its policy row is no training target.  The
+// board bits 0-2 are all flags_unpack reads.
+constexpr int kFlagFast = 8;
+
+// record ``rec`` (= g * max_moves + move) <- the board before the move; fast:
+// the move's search runs on the fast budget (move_budget)
 template <class G, class T = BoardWG<G>>
 __device__ __forceinline__ void record_observation(const EngineArrays& E, size_t rec, const int8_t* stone,
-                                                   const uint8_t* invd, const BoardMeta& m) {
+                                                   const uint8_t* invd, const BoardMeta& m, bool fast = false) {
   for (int c = T::id(); c < G::CELLS; c += T::SIZE) {
     E.rec_stones[rec * G::CELLS + c] = stone[c];
     E.rec_invd[rec * G::CELLS + c] = invd[c];
   }
-  if (T::leader()) E.rec_flags[rec] = flags_pack(m);
+  if (T::leader()) E.rec_flags[rec] = (uint8_t)(flags_pack(m) | (fast ? kFlagFast : 0));
 }
 
 // A game's key id: its global id and generation.  The id, not the slot that
@@ -171,6 +177,18 @@ __device__ __forceinline__ uint64_t move_key(const SearchParams& sp, uint32_t ki
 // ... of slot g's move mv, where slot g holds game g of epoch pp.epoch
 __device__ __forceinline__ uint64_t move_key(const SearchParams& sp, const PlayParams& pp, int g, int mv) {
   return move_key(sp, game_key_id(pp.game_base, g, pp.epoch), mv);
+}
+
+// The simulations of the self-play move with key ``key`` (playout_budget,
+// mzgo_search.hpp).  CAPS: the kernel instantiation of launches that set the
+// caps (sp.fast_simulations > 0; the host picks it, mzgo_dispatch.hpp); the
+// other one is sp.num_simulations at compile time -- the code without caps.
+// The same value on every thread, in a scalar register.
+template <bool CAPS>
+__device__ __forceinline__ int move_budget(const SearchParams& sp, uint64_t key) {
+  if constexpr (!CAPS) return sp.num_simulations;
+  else return __builtin_amdgcn_readfirstlane(
+      playout_budget(key, sp.num_simulations, sp.fast_simulations, sp.full_search_prob));
 }
 
 // valid_mask from the INVD plane (self_play.py:152-158); call with all of T
@@ -378,17 +396,18 @@ __device__ __forceinline__ int play_action(const EngineArrays& E, int g, BoardLd
   return st;
 }
 
-// The move's reward record, the counters it bumps, and the slot's status,
+// The move's reward record, the counters it bumps (sims: the simulations its
+// search ran, move_budget), and the slot's status,
 // length and final reward when the game ends (double pass, max_moves moves or
 // a board error, status 16 + BOARD_*).  All of T call it, the leader writes;
 // returns whether the game is over.
 template <class G, class T = BoardWG<G>>
-__device__ __forceinline__ bool finish_move(const EngineArrays& E, const SearchParams& sp, int g, size_t rec, int st,
+__device__ __forceinline__ bool finish_move(const EngineArrays& E, int sims, int g, size_t rec, int st,
                                             const BoardMeta& m, double w) {
   const bool ended = m.done || m.moves >= E.max_moves;
   if (T::leader()) {
     E.rec_reward[rec] = w;
-    atomicAdd(&E.counters[0], (unsigned long long)sp.num_simulations);
+    atomicAdd(&E.counters[0], (unsigned long long)sims);
     atomicAdd(&E.counters[1], 1ull);
     if (st != BOARD_OK) {
       E.status[g] = 16 + st;

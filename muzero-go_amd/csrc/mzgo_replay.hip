@@ -144,7 +144,9 @@ __global__ void __launch_bounds__(kThreads) k_replay_batch(Store R, const int* i
   for (int e = tid; e < (K + 1) * A; e += kThreads) {
     const int k = e / A, a = e - k * A, i = start + k;
     float v = uniform;
-    if (i < L) v = (float)R.policy[(mv + i) * A + (a < CELLS ? perm[a] : a)];
+    // a position searched with the fast budget (kFlagFast) is no policy target: an all-zero row,
+    // on which the loss and its gradient are exactly 0
+    if (i < L) v = (R.flags[pos + i] & kFlagFast) ? 0.f : (float)R.policy[(mv + i) * A + (a < CELLS ? perm[a] : a)];
     O.t_pol[(size_t)b * (K + 1) * A + e] = v;
   }
 }
@@ -183,7 +185,12 @@ __global__ void __launch_bounds__(64) k_replay_scatter(Store R, const int* items
   const int i = blockIdx.x, slot = items[2 * i], t = items[2 * i + 1];
   const size_t q = (size_t)slot * R.M + t;
   for (int a = threadIdx.x; a < R.A; a += 64) R.policy[q * R.A + a] = policy[(size_t)i * R.A + a];
-  if (threadIdx.x == 0) R.root_value[q] = value[i];
+  if (threadIdx.x == 0) {
+    R.root_value[q] = value[i];
+    // the row is a full-budget search's now (bits 0-2 never change: a row listed twice gets the same byte twice)
+    uint8_t* fl = R.flags + (size_t)slot * (R.M + 1) + t;
+    if (*fl & kFlagFast) *fl = (uint8_t)(*fl & ~kFlagFast);
+  }
 }
 
 // ---------------------------------------------------------------------------

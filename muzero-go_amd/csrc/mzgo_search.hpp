@@ -41,7 +41,26 @@ struct SearchParams {
   int arrival_conv;         // 9x9 LDS trees: a select's first arrival at a lazily expanded node runs the
                             // node's parent conv first and forms its priors and pick under it (sim_loop);
                             // 0: priors and pick first, then the conv (MZGO_ARRIVAL_CONV=0, an A/B switch)
+  int fast_simulations;     // playout cap randomization: a self-play move's "fast" budget (0: off; only the
+                            // self-play launches set it -- searches, reanalysis and the arena leave it 0)
+  double full_search_prob;  // ... and the probability that a move is searched with num_simulations
 };
+
+// Playout cap randomization (KataGo): the simulations of the self-play move
+// whose RNG key is ``key`` (stream_key(seed, game key id, move)) -- the full
+// budget S with probability p, else the fast one F; S when the caps are off (F
+// = 0).  A pure function of the move's key, on a tag of its own: every engine
+// that plays the move, and the host, find the same budget, and no other
+// stream of the move changes.  u01 is in [0, 1): p = 1 is always full, p = 0
+// always fast.
+__host__ __device__ __forceinline__ int playout_budget(uint64_t key, int S, int F, double p) {
+  if (F == 0) return S;
+  return u01(draw(key, TAG_BUDGET, 0)) < p ? S : F;
+}
+__host__ __device__ __forceinline__ int playout_budget(const SearchParams& sp, uint32_t kid, int mv) {
+  return playout_budget(stream_key(sp.seed, kid, (uint32_t)mv), sp.num_simulations, sp.fast_simulations,
+                        sp.full_search_prob);
+}
 
 // One game's tree (global memory).  Node 0 is the root; node ids grow by one
 // per expansion, so a search of S simulations uses at most S + 1 nodes.

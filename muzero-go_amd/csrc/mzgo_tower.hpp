@@ -1290,7 +1290,7 @@ __global__ void __launch_bounds__(64) k_tchoose(TowerArrays T, SearchParams sp, 
   BoardLds<G> bl = make_board_lds<G>(stone, invd, label, libs, gsize, killed, misc);
   double w;
   const int st = play_action<G>(E, g, bl, m, a, pp.komi, w);
-  finish_move<G>(E, sp, g, rec, st, m, w);
+  finish_move<G>(E, sp.num_simulations, g, rec, st, m, w);
 }
 
 // search API end: every prior row a select never reached (lazy, k_texpand)

@@ -8,7 +8,8 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
 * ``MCTS``, ``MuZeroAgent`` -- device search (select / expand / backup kernels)
 * ``MainMCTS`` -- main.py's MCTS variant (trainer self-play / arena) on the same kernels
 * ``GoEnv``       -- GymGo rules as bit-exact integer kernels
-* ``SelfPlay``    -- G concurrent games per GPU, one fused kernel step per move
+* ``SelfPlay``    -- G concurrent games per GPU, one fused kernel step per move; opt-in playout cap
+  randomization (``fast_simulations``, ``full_search_prob``; ``playout_budget_host`` is the rule)
 * ``SelfPlayEvaluator`` -- main.py's arena (two networks, all games at once)
 * ``GameHistory``, ``save_batches`` -- the reference's record / pickle format
 * ``Reanalyser``, ``Engine.reanalyse`` -- stored positions searched again under the
@@ -36,7 +37,7 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
 """
 from ._lib import MzgoError
 from .arena import SelfPlayEvaluator
-from .engine import Engine, EngineConfig
+from .engine import Engine, EngineConfig, playout_budget_host
 from .env import GoEnv
 from .loss import unroll_loss, unroll_loss_host
 from .net import MuZeroNet
@@ -55,4 +56,5 @@ __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "
            "ResMuZeroNet", "deterministic_res_state_dict", "MzgoError", "Reanalyser",
            "positions_from_planes", "record_ids", "DeviceReplay", "queue_key_gids", "unroll_loss",
            "unroll_loss_host", "unroll", "unroll_heads_host", "bf16_round_host", "window_items_host", "value_targets_host",
-           "sample_positions_host", "position_priorities_host", "DeviceAdam", "adam_step_host", "optim_chunk"]
+           "sample_positions_host", "position_priorities_host", "DeviceAdam", "adam_step_host", "optim_chunk",
+           "playout_budget_host"]

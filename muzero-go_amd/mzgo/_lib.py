@@ -42,6 +42,8 @@ class Config(ctypes.Structure):
         ("direct_dynamics", ctypes.c_int),
         ("tower", ctypes.c_int),
         ("res_blocks", ctypes.c_int),
+        ("fast_simulations", ctypes.c_int),
+        ("full_search_prob", ctypes.c_double),
     ]
 
 
@@ -69,6 +71,8 @@ SIGNATURES = {
     "mzgo_default_config": (None, [ctypes.POINTER(Config), _I]),
     "mzgo_engine_create": (_I, [ctypes.POINTER(Config), ctypes.POINTER(_P)]),
     "mzgo_engine_destroy": (None, [_P]),
+    "mzgo_playout_budget_host": (_I, [ctypes.c_uint64, ctypes.c_uint32, _I, _I, _I, ctypes.c_double,
+                                      ctypes.POINTER(_I)]),
     "mzgo_last_error": (ctypes.c_char_p, []),
     "mzgo_engine_device_bytes": (ctypes.c_int64, [_P]),
     "mzgo_set_weights": (_I, [_P, ctypes.c_char_p, _P, ctypes.POINTER(ctypes.c_int64), _I]),

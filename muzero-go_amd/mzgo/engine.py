@@ -39,6 +39,8 @@ class EngineConfig:
     dynamics: str = "factored"    # "factored" (conv once per parent, mzgo_expand.hpp) or "direct"
     tower: int = 0                # 1: the residual-tower network (BASELINE config 5, mzgo.resnet)
     res_blocks: int = 0           # its residual blocks per network
+    fast_simulations: int = 0     # playout cap randomization: a self-play move's fast budget (0 = off)
+    full_search_prob: float = 1.0  # ... and the probability of a full search (playout_budget_host)
 
     def to_c(self):
         c = _lib.Config()
@@ -60,6 +62,18 @@ class EngineConfig:
                 continue
             setattr(c, f.name, v)
         return c
+
+
+def playout_budget_host(seed, key_gid, move, num_simulations, fast_simulations, full_search_prob):
+    """The simulations of self-play move ``move`` of the game with key id
+    ``key_gid`` under playout cap randomization -- the function the self-play
+    kernels run, on the host (mzgo_playout_budget_host): ``num_simulations``
+    when ``fast_simulations`` is 0 or the move's draw falls below
+    ``full_search_prob``, else ``fast_simulations``."""
+    out = ctypes.c_int()
+    check(lib.mzgo_playout_budget_host(int(seed), int(key_gid) & 0xFFFFFFFF, int(move), int(num_simulations),
+                                       int(fast_simulations), float(full_search_prob), ctypes.byref(out)))
+    return out.value
 
 
 class Engine:
@@ -205,7 +219,8 @@ class Engine:
         under the current weights (mzgo_reanalyse).
 
         ``stones`` int8 [n, N*N] (0 / 1 black / 2 white), ``invd`` uint8
-        [n, N*N], ``flags`` uint8 [n] (bit0 turn, bit1 passed, bit2 done) -- the
+        [n, N*N], ``flags`` uint8 [n] (bit0 turn, bit1 passed, bit2 done; bit3,
+        searched with the fast budget, is ignored: reanalysis is always full) -- the
         record format, see ``mzgo.reanalyse.positions_from_planes`` -- and
         ``ids`` int32 [n, 2] = (key game id, move index), the searches' RNG
         keys (``mzgo.reanalyse.record_ids``).  ``noise``: injected Dirichlet

@@ -21,6 +21,11 @@ import torch
 from .engine import Engine, EngineConfig
 
 
+# record flags bit 3: the move was searched with the fast budget of playout cap
+# randomization (csrc/mzgo_move.hpp kFlagFast); bits 0-2 are the board's
+FLAG_FAST = 8
+
+
 def positions_from_planes(obs):
     """GoEnv observations [n, 6, N, N] (black, white, turn, invalid, passed,
     done) -> (stones int8 [n, N*N]: 0 / 1 black / 2 white, invd uint8
@@ -136,7 +141,8 @@ class Reanalyser:
         ids = [np.asarray(i, np.int32).reshape(-1, 2) for i in ids]
         if [len(i) for i in ids] != lens:
             raise ValueError("ids must hold one (key game id, move index) row per searched observation")
-        out = [dict(tr) for tr in trajectories]
+        # (every move is searched with the full budget here: no row stays a fast search's)
+        out = [{k: v for k, v in tr.items() if k != "fast_search"} for tr in trajectories]
         if sum(lens) == 0:
             for tr in out:
                 tr["policies"], tr["root_values"] = [], []

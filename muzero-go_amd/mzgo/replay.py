@@ -54,7 +54,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib, ptr, stream_of
-from .reanalyse import positions_from_planes
+from .reanalyse import FLAG_FAST, positions_from_planes
 
 
 def symmetry_tables(board_size, symmetry):
@@ -324,7 +324,9 @@ class DeviceReplay:
 
     def add(self, trajectory, key_gid=None):
         """One main.py-format trajectory (observations T+2, actions T, policies
-        T, rewards T+1; ``root_values`` T optional) from the host.  ``key_gid``:
+        T, rewards T+1; ``root_values`` T optional; ``fast_search`` T optional:
+        the moves searched with the fast budget, whose policy rows every batch
+        masks to zero until a reanalysis rewrites them) from the host.  ``key_gid``:
         the game's search key id for ``reanalyse`` (default: a running count
         of the games added this way)."""
         T = len(trajectory["actions"])
@@ -337,6 +339,12 @@ class DeviceReplay:
         if len(trajectory["rewards"]) != T + 1 or len(trajectory["policies"]) != T:
             raise ValueError("a trajectory has T actions, T policies and T + 1 rewards")
         stones, invd, flags = (np.ascontiguousarray(t.numpy()) for t in positions_from_planes(obs))
+        fast = trajectory.get("fast_search")
+        if fast is not None:
+            fast = np.asarray(fast, dtype=bool).reshape(-1)
+            if fast.shape[0] != T:
+                raise ValueError(f"fast_search has {fast.shape[0]} entries for {T} moves")
+            flags[:T] |= np.where(fast, FLAG_FAST, 0).astype(np.uint8)   # (never the final board's row T)
         action = np.ascontiguousarray(np.asarray(trajectory["actions"], dtype=np.int32))
         policy = np.ascontiguousarray(np.asarray(trajectory["policies"], dtype=np.float64).reshape(T, self.A))
         reward = np.ascontiguousarray(np.asarray(trajectory["rewards"], dtype=np.float64))
@@ -351,7 +359,9 @@ class DeviceReplay:
 
     def export(self, i):
         """Game i (0 = oldest) as a main.py-format dict: T+2 observations, T
-        actions, T policies, T+1 rewards, plus ``root_values`` and ``key_gid``."""
+        actions, T policies, T+1 rewards, plus ``root_values`` and ``key_gid``
+        -- and ``fast_search`` (T bools) when at least one move's row is a
+        fast-budget search that no reanalysis has rewritten."""
         from .trainer import _planes
         M, C, A, N = self.max_moves, self.N * self.N, self.A, self.N
         length, gid = ctypes.c_int32(), ctypes.c_int32()
@@ -368,7 +378,7 @@ class DeviceReplay:
                                      ptr(rv), stream_of(self.device)))
         T = length.value
         obs = [_planes(stones[t], invd[t], int(flags[t]), N) for t in range(T + 1)]
-        return {
+        out = {
             "observations": obs + [obs[-1].copy()],
             "actions": [int(a) for a in action[:T]],
             "rewards": [float(r) for r in reward[:T + 1]],
@@ -376,6 +386,10 @@ class DeviceReplay:
             "root_values": [float(v) for v in rv[:T]],
             "key_gid": gid.value,
         }
+        fast = [bool(int(f) & FLAG_FAST) for f in flags[:T]]
+        if any(fast):
+            out["fast_search"] = fast
+        return out
 
     # ---- the trainer's batch ----
     def batch(self, indices, starts, unroll_steps, discount, symmetries=None):

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from .net import MuZeroNet
+from .reanalyse import FLAG_FAST
 from .weights import deterministic_state_dict
 
 
@@ -35,6 +36,8 @@ class GameHistory:
         self.observations, self.actions, self.rewards = [], [], []
         self.policies, self.values, self.dones = [], [], []
         self.final_reward = 0
+        # per move: searched with the fast budget (playout cap randomization; all False with the caps off)
+        self.fast_search = []
 
     def calculate_returns(self):
         acc = self.final_reward
@@ -91,6 +94,7 @@ def history_from_device(rec, board_size, discount):
         h.values.append(float(rec["value"][t]))
         h.rewards.append(np.float64(rec["reward"][t]) if (ended and last) else 0)
         h.dones.append(int(ended and last))
+        h.fast_search.append(bool(f & FLAG_FAST))
     h.final_reward = np.float64(rec["final_reward"]) if ended else 0
     return h
 
@@ -101,7 +105,8 @@ class SelfPlay:
     def __init__(self, net, num_games, num_simulations, *, seed=1234, compat="reference",
                  max_moves=0, temperature=1.0, temperature_moves=15, komi=0.0, game_base=0,
                  discount=0.99, c_puct=2.5, dirichlet_alpha=0.15, dirichlet_epsilon=0.02,
-                 pass_epsilon=0.01, search_variant="self_play", dynamics="factored"):
+                 pass_epsilon=0.01, search_variant="self_play", dynamics="factored", fast_simulations=0,
+                 full_search_prob=1.0):
         self.net = net
         self.N = net.board_size
         self.G = num_games
@@ -113,6 +118,11 @@ class SelfPlay:
                                  dirichlet_alpha=dirichlet_alpha,
                                  dirichlet_epsilon=dirichlet_epsilon, pass_epsilon=pass_epsilon,
                                  search_variant=search_variant, dynamics=dynamics)
+        # playout cap randomization (EngineConfig.fast_simulations): only named when on, so an
+        # engine without caps is the one every other caller of net.engine shares
+        if fast_simulations:
+            self._engine_args.update(fast_simulations=int(fast_simulations),
+                                     full_search_prob=float(full_search_prob))
         self.engine = net.engine(num_games, num_simulations, **self._engine_args)
         self.max_moves = self.engine.M
         self.epoch = 0
@@ -260,6 +270,10 @@ def main(argv=None):
     ap.add_argument("--compat", choices=["reference", "fixed"], default="reference")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--save-interval", type=int, default=10)
+    ap.add_argument("--fast-simulations", type=int, default=0,
+                    help="playout cap randomization: the fast budget (0 = off)")
+    ap.add_argument("--full-search-prob", type=float, default=1.0,
+                    help="... and the probability that a move is searched with --simulations")
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks (one per GPU); without a launcher N > 1 starts N child processes")
     args = ap.parse_args(argv)
@@ -313,7 +327,8 @@ def main(argv=None):
     done = 0
     while done < per:
         G = min(args.parallel_games, per - done)
-        sp = SelfPlay(net, G, args.simulations, seed=args.seed, compat=args.compat, game_base=base + done)
+        sp = SelfPlay(net, G, args.simulations, seed=args.seed, compat=args.compat, game_base=base + done,
+                      fast_simulations=args.fast_simulations, full_search_prob=args.full_search_prob)
         if world == 1:
             histories.extend((base + done + g, h) for g, h in enumerate(sp.play()))
         else:

@@ -129,6 +129,7 @@ import torch
 import torch.nn.functional as F
 
 from .net import MuZeroNet
+from .reanalyse import FLAG_FAST
 from .selfplay import SelfPlay
 
 
@@ -428,12 +429,18 @@ def trajectory_from_record(rec, final_obs, board_size, max_moves):
     if not done and L >= max_moves and rewards:
         rewards[-1] += -0.5                      # main.py:699-702 (move cap)
     winner = float(rec["final_reward"]) if done else 0.0   # env.winner(): 0 unless ended
-    return {
+    out = {
         "observations": obs + [final_obs, final_obs],
         "actions": acts,
         "rewards": rewards + [winner],
         "policies": [np.array(p, dtype=np.float64) for p in rec["policy"][:L]],
     }
+    # playout cap randomization: the moves searched with the fast budget (flags
+    # bit 3), whose policies are no targets -- only when the game has one
+    fast = [bool(int(rec["flags"][t]) & FLAG_FAST) for t in range(L)]
+    if any(fast):
+        out["fast_search"] = fast
+    return out
 
 
 class MainSelfPlay:
@@ -443,13 +450,15 @@ class MainSelfPlay:
     move cap int(1.5 N^2) (main.py:51).  ``play()`` returns main.py
     trajectories."""
 
-    def __init__(self, net, num_games, num_simulations, *, seed=1234, game_base=0, dynamics="factored"):
+    def __init__(self, net, num_games, num_simulations, *, seed=1234, game_base=0, dynamics="factored",
+                 fast_simulations=0, full_search_prob=1.0):
         N = net.board_size
         self.max_moves = int(N * N * 1.5)
         self.N = N
         self.sp = SelfPlay(net, num_games, num_simulations, seed=seed, compat="fixed", max_moves=self.max_moves,
                            game_base=game_base, c_puct=2.0, dirichlet_alpha=0.03, dirichlet_epsilon=0.25,
-                           pass_epsilon=0.05, search_variant="main", dynamics=dynamics)
+                           pass_epsilon=0.05, search_variant="main", dynamics=dynamics,
+                           fast_simulations=fast_simulations, full_search_prob=full_search_prob)
 
     def refresh(self):
         """The net's current weights into the self-play engine (``SelfPlay.refresh``)."""
@@ -680,7 +689,15 @@ class MuZeroTrainer:
 
     def _policy_target(self, trajectory, i):
         pol = trajectory["policies"]
-        return pol[i] if i < len(pol) else np.ones(self.action_size) / self.action_size
+        if i >= len(pol):
+            return np.ones(self.action_size) / self.action_size
+        # a move searched with the fast budget (playout cap randomization) is no
+        # policy target: the all-zero row the device assembly writes, on which
+        # the loss and its gradient are exactly 0
+        fast = trajectory.get("fast_search")
+        if fast is not None and fast[i]:
+            return np.zeros(self.action_size)
+        return pol[i]
 
     def _value_loss(self, value, target):
         if self.config.use_value_transform:
