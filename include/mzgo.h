@@ -1037,6 +1037,96 @@ int mzgo_unroll_heads_host(const char* const* keys, const float* const* params, 
                            int C, int N, float* logits, float* value, float* reward, const float* g_logits,
                            const float* g_value, const float* g_reward, float* g_latent);
 
+/* The unroll's latents, for an auxiliary loss on them.
+ *
+ * mzgo_unroll_latents: where the latents of a forward call lie inside its
+ * ``saved`` buffer -- *bytes = (K + 1) B C N N floats from byte *offset_bytes
+ * (a multiple of 256), step-major [K+1][B][C][N][N], float32 in both
+ * precisions -- so that a caller can read them in place.  They are the
+ * backward's saved activations: they must not be written.
+ *
+ * mzgo_unroll_backward_l: mzgo_unroll_backward_p with ``g_latent``, the
+ * caller's gradient with respect to those latents, laid out like them and
+ * 16-byte aligned (``work`` too), or NULL.  When given it is added to the
+ * heads' latent gradient after step (a) and before the chain by one elementwise
+ * launch (a thread per four floats; float32 in both precisions): the latents
+ * are post-ReLU, and the chain and the representation mask with the saved
+ * latents, so nothing else changes.  With NULL the launches and every bit are
+ * mzgo_unroll_backward_p's (which is this call with NULL).  The same
+ * MZGO_EINVAL conditions, and a misaligned g_latent. */
+int mzgo_unroll_latents(int B, int K, int C, int N, int emb_rows, int precision, int64_t* offset_bytes,
+                        int64_t* bytes);
+int mzgo_unroll_backward_l(const char* const* keys, const float* const* params, const int64_t* const* shapes,
+                           const int* ndims, float* const* grads, int n_params, const void* saved,
+                           int64_t saved_bytes, const float* g_logits, const float* g_value, const float* g_reward,
+                           const float* g_latent, int B, int K, int C, int N, int emb_rows, void* work,
+                           int64_t work_bytes, int precision, void* stream);
+
+/* --------------------------------------------------------------------------
+ * The ownership auxiliary target (KataGo's ownership head on MuZero's unrolled
+ * latents; not in main.py): a 1x1 conv C -> 1 on every latent predicts, per
+ * board point, who owns it on the game's final board, from the side of the
+ * colour to move at that unroll step.
+ *
+ * Targets.  On the stored final board (row L of a game: 1 black, 2 white, 0
+ * empty) a stone is owned by its colour, an empty point by the one colour its
+ * empty region touches, by nobody when the region touches both colours or none
+ * (oracle/gogame.py: areas, cell by cell).  For sample (slot, start, symmetry)
+ * and unroll step k, with at = start + k and mover = 1 + (flags[at] & 1):
+ *   t_own [B][K+1][N*N]  +1 where the owner of cell sym_src(N, sym, c) is the
+ *                        mover, -1 where it is the other colour, 0 for nobody
+ *   own_mask [B][K+1]    1 if at <= L and the game ended (the done bit, bit 2,
+ *                        of row L's flags: the condition under which reward[L]
+ *                        is the winner), else 0 with an all-zero row -- a game
+ *                        cut off by the move cap has no ownership target
+ * mzgo_replay_ownership takes host indices, starts and symmetries (NULL:
+ * identity) as mzgo_replay_batch does, with its checks;
+ * mzgo_replay_ownership_items takes the sampler's DEVICE items [B][3]: nothing
+ * crosses the bus and nothing synchronises.  One launch, a workgroup per
+ * sample, next to the batch assembly (which is unchanged).  unroll_steps in
+ * 0..63.  mzgo_ownership_host is the owner map alone on HOST arrays (stones
+ * int8 [N*N] -> owner int8 [N*N]: 0, 1, 2) and mzgo_ownership_targets_host one
+ * sample's rows from the final board's stones and the game's flags [L + 1]:
+ * the kernel's own functions (csrc/mzgo_replay.hpp), no device work. */
+int mzgo_replay_ownership(mzgo_replay* replay, const int32_t* indices_host, const int32_t* starts_host,
+                          const int32_t* symmetries_host, int B, int unroll_steps, float* t_own, float* own_mask,
+                          void* stream);
+int mzgo_replay_ownership_items(mzgo_replay* replay, const int32_t* items, int B, int unroll_steps, float* t_own,
+                                float* own_mask, void* stream);
+int mzgo_ownership_host(const int8_t* stones, int board_size, int8_t* owner);
+int mzgo_ownership_targets_host(const int8_t* final_stones, const uint8_t* flags, int L, int board_size, int start,
+                                int symmetry, int unroll_steps, float* t_own, float* own_mask);
+
+/* The head and its loss on ``latents`` [K+1][B][C][N][N] (mzgo_unroll_latents'
+ * layout), head weight w [C] and bias [1]:
+ *   x[s][b][c]  = sum_ch w[ch] latents[s][b][ch][c] + bias        (f64 sum, rounded to float32)
+ *   l(x, t)     = softplus(2 x) - (1 + t) x,  softplus(z) = max(z, 0) + log1p(exp(-|z|))
+ *                 (the cross entropy of (1 + tanh x) / 2 against (1 + t) / 2; d l / d x = tanh(x) - t)
+ *   per[b]      = weight sum_k own_mask[b][k] (1 / N^2) sum_c l(x[k][b][c], t_own[b][k][c])
+ * mzgo_ownership_loss writes per f32 [B], *total (f64, the samples' sums) and
+ * g_x f32 [K+1][B][N*N], the derivative of sum_b per[b] with respect to x:
+ * two launches.  mzgo_ownership_loss_backward takes the incoming g_per [B] and
+ * writes g_latents[s][b][ch][c] = g_per[b] w[ch] g_x[s][b][c], g_w [C] and
+ * g_bias [1]: two launches.  Both use the caller-owned ``work``
+ * (mzgo_ownership_loss_workspace bytes: the rows' losses, then the rows'
+ * partial sums), which the pair may share; all sums are f64 in a fixed order,
+ * no atomics, so repeats are bit-identical.  A row whose mask is 0 is not read
+ * and contributes an exact 0 to the loss and to every gradient.  All pointers
+ * are device pointers; nothing allocates or synchronises.
+ * mzgo_ownership_loss_host is both on HOST arrays with serial sums in index
+ * order (csrc/mzgo_ownership.hpp's functions): no device work.  MZGO_EINVAL: a
+ * null pointer, B < 1, K < 0, C < 1, N outside 2..19, work too small. */
+int mzgo_ownership_loss_workspace(int B, int K, int C, int64_t* work_bytes);
+int mzgo_ownership_loss(const float* latents, const float* w, const float* bias, const float* t_own,
+                        const float* own_mask, int B, int K, int C, int N, float weight, float* per, double* total,
+                        float* g_x, void* work, int64_t work_bytes, void* stream);
+int mzgo_ownership_loss_backward(const float* latents, const float* w, const float* own_mask, const float* g_x,
+                                 const float* g_per, int B, int K, int C, int N, float* g_latents, float* g_w,
+                                 float* g_bias, void* work, int64_t work_bytes, void* stream);
+int mzgo_ownership_loss_host(const float* latents, const float* w, const float* bias, const float* t_own,
+                             const float* own_mask, const float* g_per, int B, int K, int C, int N, float weight,
+                             float* per, double* total, float* g_x, float* g_latents, float* g_w, float* g_bias);
+
 /* --------------------------------------------------------------------------
  * The trainer's optimizer tail in one call (main.py:481-484 and :379:
  * clip_grad_norm_, torch.optim.Adam.step and StepLR.step over the parameter

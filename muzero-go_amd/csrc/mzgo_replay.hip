@@ -16,7 +16,9 @@
 // Opt-in on top of that ledger, a weight per stored position (PosLedger) and a
 // sampler that carries one draw's target through two more levels inside the
 // picked game (k_replay_possample_build, k_replay_possample_draw), with the
-// positions' weights written back from the step's value errors.
+// positions' weights written back from the step's value errors.  Next to the
+// batch assembly, one more launch on the same items turns the games' final
+// boards into the ownership head's targets (k_replay_ownership).
 //
 // Kernels here use plain vector loads and stores only (and one vector atomic,
 // the count of refused priority updates); workgroups never communicate.  Compiled with -ffp-contract=off like every unit: the value
@@ -158,6 +160,67 @@ __global__ void __launch_bounds__(kThreads) k_replay_finish(const double* val, c
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
   t_val[i] = has_boot[i] ? (float)(val[i] + factor[i] * (double)v[i]) : (float)val[i];
+}
+
+// ---------------------------------------------------------------------------
+// Ownership targets: one workgroup per sample (slot, start, symmetry).  The
+// final board (row L) goes to LDS; the reached-colour masks of its empty cells
+// are iterated to their fixed point in two LDS buffers, a pass reading one and
+// writing the other, with the barrier that also ORs the threads' "changed"
+// between passes (own_reach_step, mzgo_replay.hpp; at most CELLS + 1 passes,
+// whatever the board holds); then the K + 1 rows are written, element e on
+// thread e % 256, through the symmetry's cell permutation.  A game that did
+// not end, a slot outside the ring and a row past the final board give zeros
+// and mask 0.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) k_replay_ownership(Store R, const int* items, int K,
+                                                               float* __restrict__ t_own,
+                                                               float* __restrict__ own_mask) {
+  __shared__ int8_t st[kMaxBoard * kMaxBoard];
+  __shared__ uint8_t reach[2][kMaxBoard * kMaxBoard];
+  __shared__ int perm[kMaxBoard * kMaxBoard];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int slot = items[3 * b], start = items[3 * b + 1], sym = items[3 * b + 2] & 7;
+  const int CELLS = R.CELLS, N = R.N;
+  const bool held = slot >= 0 && slot < R.cap;
+  int L = held ? R.length[slot] : 0;
+  L = L < 0 ? 0 : L > R.M ? R.M : L;
+  const size_t pos = held ? (size_t)slot * (R.M + 1) : 0;
+  const int final_flags = held ? R.flags[pos + L] : 0;
+  float* out = t_own + (size_t)b * (K + 1) * CELLS;
+  if (tid <= K) own_mask[(size_t)b * (K + 1) + tid] = own_row_valid((long long)start + tid, L, final_flags) ? 1.f : 0.f;
+  if (!own_row_valid(start < 0 ? 0 : start, L, final_flags)) {    // (block-uniform) no row of the sample has a target
+    for (int e = tid; e < (K + 1) * CELLS; e += kThreads) out[e] = 0.f;
+    return;
+  }
+  for (int c = tid; c < CELLS; c += kThreads) {
+    st[c] = R.stones[(pos + L) * CELLS + c];
+    reach[0][c] = 0;
+    perm[c] = sym_src(N, sym, c);
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int pass = 0; pass <= CELLS; ++pass) {
+    int changed = 0;
+    for (int c = tid; c < CELLS; c += kThreads) {
+      const int m = st[c] ? 0 : own_reach_step(st, reach[cur], N, c);
+      changed |= m != reach[cur][c];
+      reach[cur ^ 1][c] = (uint8_t)m;
+    }
+    cur ^= 1;
+    if (!__syncthreads_or(changed)) break;                // (the same answer on every thread)
+  }
+  // the owners over the stones (each thread its own cells: the passes are done with st)
+  for (int c = tid; c < CELLS; c += kThreads) reach[cur ^ 1][c] = (uint8_t)own_owner(st[c], reach[cur][c]);
+  __syncthreads();
+  const uint8_t* owner = reach[cur ^ 1];
+  for (int e = tid; e < (K + 1) * CELLS; e += kThreads) {
+    const int k = e / CELLS, c = e - k * CELLS;
+    const long long at = (long long)start + k;
+    float v = 0.f;
+    if (own_row_valid(at, L, final_flags)) v = own_target(owner[perm[c]], 1 + (R.flags[pos + at] & 1));
+    out[e] = v;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1132,6 +1195,77 @@ int mzgo_replay_batch_items(mzgo_replay* r, const int32_t* items, int B, int unr
   hipLaunchKernelGGL(k_replay_batch<false>, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, r->R, items, unroll_steps,
                      0, discount, O);
   RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+// the checks the two ownership assemblies share, and their launch
+static int ownership_check(const mzgo_replay* r, const char* who, int B, int unroll_steps, const float* t_own,
+                           const float* own_mask) {
+  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
+  if (unroll_steps < 0 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (0..%d)", who, unroll_steps, kMaxUnroll);
+  if (!t_own || !own_mask) return set_error(MZGO_EINVAL, "%s: null %s", who, !t_own ? "t_own" : "own_mask");
+  return MZGO_OK;
+}
+static int ownership_launch(mzgo_replay* r, const int* items, int B, int unroll_steps, float* t_own, float* own_mask,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(k_replay_ownership, dim3(B), dim3(kThreads), 0, s, r->R, items, unroll_steps, t_own, own_mask);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+int mzgo_replay_ownership(mzgo_replay* r, const int32_t* indices_host, const int32_t* starts_host,
+                          const int32_t* symmetries_host, int B, int unroll_steps, float* t_own, float* own_mask,
+                          void* stream) {
+  const char* who = "mzgo_replay_ownership";
+  if (int rc = ownership_check(r, who, B, unroll_steps, t_own, own_mask)) return rc;
+  if (!indices_host || !starts_host)
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !indices_host ? "indices" : "starts");
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = upload_samples(r, who, indices_host, starts_host, symmetries_host, B, s)) return rc;
+  return ownership_launch(r, r->d_items, B, unroll_steps, t_own, own_mask, s);
+}
+
+int mzgo_replay_ownership_items(mzgo_replay* r, const int32_t* items, int B, int unroll_steps, float* t_own,
+                                float* own_mask, void* stream) {
+  const char* who = "mzgo_replay_ownership_items";
+  if (int rc = ownership_check(r, who, B, unroll_steps, t_own, own_mask)) return rc;
+  if (!items) return set_error(MZGO_EINVAL, "%s: null items", who);
+  return ownership_launch(r, items, B, unroll_steps, t_own, own_mask, (hipStream_t)stream);
+}
+
+int mzgo_ownership_host(const int8_t* stones, int board_size, int8_t* owner) {
+  const char* who = "mzgo_ownership_host";
+  if (board_size < 2 || board_size > kMaxBoard)
+    return set_error(MZGO_EINVAL, "%s: board_size %d (2..%d)", who, board_size, kMaxBoard);
+  if (!stones || !owner) return set_error(MZGO_EINVAL, "%s: null %s", who, !stones ? "stones" : "owner");
+  ownership_host(stones, board_size, owner);
+  return MZGO_OK;
+}
+
+int mzgo_ownership_targets_host(const int8_t* final_stones, const uint8_t* flags, int L, int board_size, int start,
+                                int symmetry, int unroll_steps, float* t_own, float* own_mask) {
+  const char* who = "mzgo_ownership_targets_host";
+  if (board_size < 2 || board_size > kMaxBoard)
+    return set_error(MZGO_EINVAL, "%s: board_size %d (2..%d)", who, board_size, kMaxBoard);
+  if (!final_stones || !flags || !t_own || !own_mask)
+    return set_error(MZGO_EINVAL, "%s: null %s", who,
+                     !final_stones ? "final_stones" : !flags ? "flags" : !t_own ? "t_own" : "own_mask");
+  if (L < 0 || L > (1 << 30)) return set_error(MZGO_EINVAL, "%s: L %d outside 0..2^30", who, L);
+  if (symmetry < 0 || symmetry > 7) return set_error(MZGO_EINVAL, "%s: symmetry %d (0..7)", who, symmetry);
+  if (unroll_steps < 0 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (0..%d)", who, unroll_steps, kMaxUnroll);
+  const int N = board_size, CELLS = N * N;
+  int8_t owner[kMaxBoard * kMaxBoard];
+  ownership_host(final_stones, N, owner);
+  for (int k = 0; k <= unroll_steps; ++k) {
+    const long long at = (long long)start + k;
+    const bool valid = own_row_valid(at, L, flags[L]);
+    own_mask[k] = valid ? 1.f : 0.f;
+    for (int c = 0; c < CELLS; ++c)
+      t_own[(size_t)k * CELLS + c] = valid ? own_target(owner[sym_src(N, symmetry, c)], 1 + (flags[at] & 1)) : 0.f;
+  }
   return MZGO_OK;
 }
 

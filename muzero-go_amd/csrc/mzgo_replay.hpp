@@ -8,7 +8,8 @@
 // ledger and its weight rules (host and device likewise), the window
 // of a sample and the item list of a batch's windows (host and device
 // likewise) with the in-place reanalysis queue's arguments, the search-value
-// target rule and the value rows it reads (host and device), and the engine's
+// target rule and the value rows it reads (host and device), the ownership
+// rule of a final board and its targets (host and device), and the engine's
 // side of the store's engine-facing calls (mzgo_capi.hip owns struct
 // mzgo_engine and the thread-local error string).
 #pragma once
@@ -208,6 +209,63 @@ __host__ __device__ __forceinline__ int value_rows(const int* length, int cap, i
 // whether row t is one of a sample's rows (its window, or its value rows past the window)
 __host__ __device__ __forceinline__ bool sample_has(int start, int rows, int vfirst, int vrows, int t) {
   return window_has(start, rows, t) || window_has(vfirst, vrows, t);
+}
+
+// ---------------------------------------------------------------------------
+// Ownership targets (mzgo.h: mzgo_replay_ownership): who owns each point of a
+// game's final board under the area rule (oracle/gogame.py: areas, cell by
+// cell).  A stone is owned by its colour (1 black, 2 white); an empty point by
+// the one colour its empty region touches, by nobody (0) when the region
+// touches both or none.  The region's colours are found as a fixed point: a
+// mask of reached colours per empty cell (bit 0 black, bit 1 white -- a stone's
+// colour IS its mask), each pass OR-ing in the four neighbours' masks of the
+// pass before, until a pass changes nothing.  OR is monotone, so the fixed
+// point does not depend on the order of visits, and at most CELLS passes reach
+// it.  k_replay_ownership and the host twin run these functions.
+// ---------------------------------------------------------------------------
+// what a neighbour hands on: its colour if it is a stone, its reached mask if empty
+__host__ __device__ __forceinline__ int own_seen(const int8_t* stones, const uint8_t* reach, int n) {
+  return stones[n] ? (stones[n] & 3) : reach[n];
+}
+// one pass at the empty cell c: the masks of its neighbours OR-ed into its own
+__host__ __device__ __forceinline__ int own_reach_step(const int8_t* stones, const uint8_t* reach, int N, int c) {
+  const int i = c / N, j = c - i * N;
+  int m = reach[c];
+  if (i > 0) m |= own_seen(stones, reach, c - N);
+  if (i < N - 1) m |= own_seen(stones, reach, c + N);
+  if (j > 0) m |= own_seen(stones, reach, c - 1);
+  if (j < N - 1) m |= own_seen(stones, reach, c + 1);
+  return m;
+}
+// the owner of a cell from its stone and, where it is empty, its region's mask at the fixed point
+__host__ __device__ __forceinline__ int own_owner(int stone, int reach) {
+  return stone ? (stone & 3) : reach == 1 ? 1 : reach == 2 ? 2 : 0;
+}
+// whether unroll step k of a sample has an ownership target: position at = start + k is one of the game's
+// L + 1 rows and the game ended (the done bit of the final row's flags: the condition for reward[L] = the winner)
+__host__ __device__ __forceinline__ bool own_row_valid(long long at, int L, int final_flags) {
+  return at >= 0 && at <= L && ((final_flags >> 2) & 1);
+}
+// the target of a cell owned by ``owner`` (0 nobody) seen by ``mover``, the colour to move (1 or 2)
+__host__ __device__ __forceinline__ float own_target(int owner, int mover) {
+  return owner == 0 ? 0.f : owner == mover ? 1.f : -1.f;
+}
+// host serial form: owner [CELLS] of stones [CELLS]; two buffers, a pass reads one and writes the other
+inline void ownership_host(const int8_t* stones, int N, int8_t* owner) {
+  const int CELLS = N * N;
+  uint8_t reach[2][19 * 19] = {};
+  int cur = 0;
+  for (int pass = 0; pass <= CELLS; ++pass) {
+    bool changed = false;
+    for (int c = 0; c < CELLS; ++c) {
+      const int m = stones[c] ? 0 : own_reach_step(stones, reach[cur], N, c);
+      changed |= m != reach[cur][c];
+      reach[cur ^ 1][c] = (uint8_t)m;
+    }
+    cur ^= 1;
+    if (!changed) break;
+  }
+  for (int c = 0; c < CELLS; ++c) owner[c] = (int8_t)own_owner(stones[c], reach[cur][c]);
 }
 
 // One mzgo_replay_reanalyse_sample call: the in-place form of the reanalysis

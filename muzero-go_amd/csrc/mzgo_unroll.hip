@@ -1,6 +1,7 @@
 // mzgo_unroll.hip -- the trainer's whole K-step unroll in one forward and one
 // backward call (mzgo.h: mzgo_unroll_workspace, mzgo_unroll_forward,
-// mzgo_unroll_backward, mzgo_unroll_heads_host).
+// mzgo_unroll_backward, mzgo_unroll_latents, mzgo_unroll_backward_l,
+// mzgo_unroll_heads_host).
 //
 // main.py:431-482 unrolls a trajectory step by step: the representation
 // (main.py:72-84), then K times the dynamics conv (main.py:97-103) with the
@@ -24,6 +25,9 @@
 //             (conv_weight_partials, conv_bwd_reduce, conv_bwd_bias),
 //             k_unroll_emb_grad, and the representation's three layers on
 //             conv_backward from the saved activations: K + 17 launches.
+//             mzgo_unroll_backward_l with a latent gradient (an auxiliary
+//             loss on the latents, mzgo_unroll_latents) adds it to the heads'
+//             after the first two: one elementwise launch more.
 //
 // fp32 throughout, unless the _p entry points are given MZGO_PREC_BF16: then
 // the dynamics conv's three matrix products -- the K forward convs, the K
@@ -388,6 +392,16 @@ __global__ void __launch_bounds__(256) k_unroll_emb_grad(const float* __restrict
   gemb[idx] = s;
 }
 
+// G += g: the caller's gradient with respect to the latents added to the heads', before the chain.  A thread
+// per four floats (n4 of them: every step's latents are a multiple of 16 floats, both bases 16-byte aligned).
+__global__ void __launch_bounds__(256) k_unroll_latent_grad_add(float4* __restrict__ G, const float4* __restrict__ g,
+                                                                size_t n4) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const float4 a = G[i], b = g[i];
+  G[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+
 HeadW head_weights(const float* const* P) {
   return HeadW{P[WK_POLICY_W], P[WK_POLICY_B], P[WK_VALUE_W], P[WK_VALUE_B], P[WK_VFC_W], P[WK_VFC_B],
                P[WK_PASS_LOGIT], P[WK_REWARD_W], P[WK_REWARD_B], P[WK_FC1_W], P[WK_FC1_B], P[WK_FC2_W], P[WK_FC2_B]};
@@ -447,6 +461,18 @@ int mzgo_unroll_workspace_p(int B, int K, int C, int N, int emb_rows, int precis
   const Layout L = layout(B, K, C, N, precision);
   *saved_bytes = (int64_t)(L.saved_floats * sizeof(float));
   *work_bytes = (int64_t)(L.work_floats * sizeof(float));
+  return MZGO_OK;
+}
+
+int mzgo_unroll_latents(int B, int K, int C, int N, int emb_rows, int precision, int64_t* offset_bytes,
+                        int64_t* bytes) {
+  if (int rc = check_dims("mzgo_unroll_latents", B, K, C, N, emb_rows)) return rc;
+  if (int rc = check_precision("mzgo_unroll_latents", precision, C)) return rc;
+  if (!offset_bytes || !bytes)
+    return set_error(MZGO_EINVAL, "mzgo_unroll_latents: null %s", !offset_bytes ? "offset_bytes" : "bytes");
+  const Layout L = layout(B, K, C, N, precision);
+  *offset_bytes = (int64_t)(L.s_lat * sizeof(float));
+  *bytes = (int64_t)(((size_t)K + 1) * L.LS * sizeof(float));
   return MZGO_OK;
 }
 
@@ -513,6 +539,15 @@ int mzgo_unroll_backward_p(const char* const* keys, const float* const* params, 
                            int64_t saved_bytes, const float* g_logits, const float* g_value, const float* g_reward,
                            int B, int K, int C, int N, int emb_rows, void* work, int64_t work_bytes, int precision,
                            void* stream) {
+  return mzgo_unroll_backward_l(keys, params, shapes, ndims, grads, n_params, saved, saved_bytes, g_logits, g_value,
+                                g_reward, nullptr, B, K, C, N, emb_rows, work, work_bytes, precision, stream);
+}
+
+int mzgo_unroll_backward_l(const char* const* keys, const float* const* params, const int64_t* const* shapes,
+                           const int* ndims, float* const* grads, int n_params, const void* saved,
+                           int64_t saved_bytes, const float* g_logits, const float* g_value, const float* g_reward,
+                           const float* g_latent, int B, int K, int C, int N, int emb_rows, void* work,
+                           int64_t work_bytes, int precision, void* stream) {
   const char* fn = "mzgo_unroll_backward";
   if (int rc = check_dims(fn, B, K, C, N, emb_rows)) return rc;
   if (int rc = check_precision(fn, precision, C)) return rc;
@@ -520,6 +555,8 @@ int mzgo_unroll_backward_p(const char* const* keys, const float* const* params, 
                      : !grads ? "grads" : nullptr;
   if (!null && K > 0 && !g_reward) null = "g_reward";
   if (null) return set_error(MZGO_EINVAL, "%s: null %s", fn, null);
+  if (g_latent && ((uintptr_t)g_latent & 15 || (uintptr_t)work & 15))
+    return set_error(MZGO_EINVAL, "%s: g_latent and work must be 16-byte aligned", fn);
   const float* P[WK_COUNT];
   float* Gd[WK_COUNT];
   if (int rc = resolve(fn, keys, params, shapes, ndims, grads, n_params, C, emb_rows, kAllSet, kAllSet,
@@ -551,6 +588,14 @@ int mzgo_unroll_backward_p(const char* const* keys, const float* const* params, 
   hipLaunchKernelGGL(k_unroll_heads_reduce, dim3((unsigned)(3 * C + 48 + HS_COUNT)), dim3(64), 0, s, hp, rows, C,
                      head_grads(Gd));
   MZGO_HIPCHK(hipGetLastError());
+  if (g_latent) {
+    // (a') the caller's latent gradient, laid out like the latents: G is the gradient with respect to the post-ReLU
+    // latents and the chain and the representation mask with the saved latents, so an addition is all it takes
+    const size_t n4 = ((size_t)K + 1) * L.LS / 4;
+    hipLaunchKernelGGL(k_unroll_latent_grad_add, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s,
+                       reinterpret_cast<float4*>(G), reinterpret_cast<const float4*>(g_latent), n4);
+    MZGO_HIPCHK(hipGetLastError());
+  }
   if (K > 0) {
     // (b) the chain: step s's input gradient into step s - 1's latent gradient (bf16: from the packed weights the
     // forward left in `saved`)

@@ -30,6 +30,12 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
   (``TrainConfig.fused_unroll``); ``precision="bf16"`` (``TrainConfig.unroll_precision``) runs the
   dynamics conv's three matrix products on bf16 MFMA with float32 accumulation and float32 master
   weights, and ``bf16_round_host`` is the kernels' rounding on host arrays
+* ``OwnershipHead``, ``ownership_loss`` -- the ownership auxiliary target (KataGo's, on the
+  unrolled latents): ``unroll(..., return_latents=True)`` hands out the K + 1 latents and takes a
+  gradient on them, the head and its loss are two HIP launches each way, and the targets come
+  from the store's final boards (``DeviceReplay.ownership``;
+  ``TrainConfig.ownership_loss_weight``); ``ownership_host``, ``ownership_targets_host`` and
+  ``ownership_loss_host`` are the rules on host arrays
 * ``DeviceAdam`` -- the optimizer tail (gradient-norm clip, Adam / AdamW, StepLR) of any float32
   module in one stream-ordered HIP call that refuses and counts a non-finite gradient
   (``TrainConfig.device_optimizer``); ``adam_step_host`` is its host twin on numpy arrays
@@ -42,9 +48,10 @@ from .env import GoEnv
 from .loss import unroll_loss, unroll_loss_host
 from .net import MuZeroNet
 from .optim import DeviceAdam, adam_step_host, optim_chunk
+from .ownership import OwnershipHead, ownership_loss, ownership_loss_host
 from .reanalyse import Reanalyser, positions_from_planes, record_ids
-from .replay import (DeviceReplay, position_priorities_host, queue_key_gids, sample_positions_host,
-                     value_targets_host, window_items_host)
+from .replay import (DeviceReplay, ownership_host, ownership_targets_host, position_priorities_host, queue_key_gids,
+                     sample_positions_host, value_targets_host, window_items_host)
 from .resnet import ResMuZeroNet
 from .search import MCTS, MainMCTS, MuZeroAgent
 from .selfplay import GameHistory, SelfPlay, history_from_device, save_batches
@@ -57,4 +64,5 @@ __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "
            "positions_from_planes", "record_ids", "DeviceReplay", "queue_key_gids", "unroll_loss",
            "unroll_loss_host", "unroll", "unroll_heads_host", "bf16_round_host", "window_items_host", "value_targets_host",
            "sample_positions_host", "position_priorities_host", "DeviceAdam", "adam_step_host", "optim_chunk",
-           "playout_budget_host"]
+           "playout_budget_host", "OwnershipHead", "ownership_loss", "ownership_loss_host", "ownership_host",
+           "ownership_targets_host"]

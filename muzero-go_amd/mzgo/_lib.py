@@ -171,6 +171,17 @@ SIGNATURES = {
     "mzgo_unroll_forward_p": (_I, [_P] * 4 + [_I] + [_P] * 2 + [_I] * 5 + [_P, ctypes.c_int64] + [_P] * 3 + [_I, _P]),
     "mzgo_unroll_backward_p": (_I, [_P] * 5 + [_I] + [_P, ctypes.c_int64] + [_P] * 3 + [_I] * 5
                                + [_P, ctypes.c_int64, _I, _P]),
+    "mzgo_unroll_latents": (_I, [_I] * 6 + [ctypes.POINTER(ctypes.c_int64)] * 2),
+    "mzgo_unroll_backward_l": (_I, [_P] * 5 + [_I] + [_P, ctypes.c_int64] + [_P] * 4 + [_I] * 5
+                               + [_P, ctypes.c_int64, _I, _P]),
+    "mzgo_replay_ownership": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),
+    "mzgo_replay_ownership_items": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "mzgo_ownership_host": (_I, [_P, _I, _P]),
+    "mzgo_ownership_targets_host": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "mzgo_ownership_loss_workspace": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
+    "mzgo_ownership_loss": (_I, [_P] * 5 + [_I] * 4 + [ctypes.c_float] + [_P] * 4 + [ctypes.c_int64, _P]),
+    "mzgo_ownership_loss_backward": (_I, [_P] * 5 + [_I] * 4 + [_P] * 4 + [ctypes.c_int64, _P]),
+    "mzgo_ownership_loss_host": (_I, [_P] * 6 + [_I] * 4 + [ctypes.c_float] + [_P] * 6),
     "mzgo_optim_chunk": (_I, []),
     "mzgo_optim_create": (_I, [_I, _P, _I, ctypes.POINTER(_P)]),
     "mzgo_optim_destroy": (None, [_P]),

@@ -17,7 +17,12 @@ and serves both consumers of stored games from there:
   engine, the fresh policies and root values written into the store;
   ``reanalyse_sample`` -- the same for exactly the rows a drawn sample is about
   to read, from the sampler's device items (``sample`` -> ``reanalyse_sample``
-  -> ``batch_from``; ``TrainConfig.reanalyse_sample``).
+  -> ``batch_from``; ``TrainConfig.reanalyse_sample``);
+* ``ownership`` / ``ownership_from`` -- one more small launch on the same
+  samples (k_replay_ownership): who owns each point of the game's final board,
+  seen by the colour to move at every unroll step, the targets of the ownership
+  head (``TrainConfig.ownership_loss_weight``; ``ownership_host`` and
+  ``ownership_targets_host`` are the rules).
 
 Ingest is ``add_games(engine)`` (device to device, one launch; what
 ``MainSelfPlay.play_into`` calls), the playing launch itself
@@ -237,6 +242,46 @@ def value_targets_host(rewards, root_values, start, unroll_steps, td_steps, disc
     return out
 
 
+def ownership_host(stones, board_size):
+    """Who owns each point of a board (mzgo_ownership_host: the ownership
+    kernel's own fixed-point rule, no GPU).  ``stones`` [N, N] or [N*N] (1 =
+    black, 2 = white, 0 = empty); returns int8 [N, N]: a stone's colour, for an
+    empty point the one colour its empty region touches, 0 where the region
+    touches both colours or none -- ``oracle.gogame.areas`` cell by cell."""
+    N = int(board_size)
+    s = np.ascontiguousarray(np.asarray(stones, dtype=np.int8).reshape(-1))
+    if len(s) != N * N:
+        raise ValueError(f"ownership_host: stones has {len(s)} cells, a {N}x{N} board {N * N}")
+    owner = np.empty(N * N, np.int8)
+    check(lib.mzgo_ownership_host(ptr(s), N, ptr(owner)))
+    return owner.reshape(N, N)
+
+
+def ownership_targets_host(final_stones, flags, board_size, start, unroll_steps, symmetry=0):
+    """The ownership targets of one sample on the host
+    (mzgo_ownership_targets_host: the kernel's own rule, no GPU).
+    ``final_stones`` [N*N] is the board after the last move of a game of L
+    moves (the store's row L) and ``flags`` u8 [L + 1] its positions' flag
+    bytes (bit 0: white to move; bit 2 of the last: the game ended).  Returns
+    ``(t_own f32 [K+1, N*N], own_mask f32 [K+1])``: row k is position
+    ``start`` + k seen by its colour to move -- +1 the mover owns cell
+    ``src[c]`` of ``symmetry``'s table, -1 the opponent does, 0 nobody -- with
+    mask 1, or zeros with mask 0 past the final board or when the game did not
+    end."""
+    N = int(board_size)
+    s = np.ascontiguousarray(np.asarray(final_stones, dtype=np.int8).reshape(-1))
+    fl = np.ascontiguousarray(np.asarray(flags, dtype=np.uint8).reshape(-1))
+    if len(s) != N * N or len(fl) < 1:
+        raise ValueError(f"ownership_targets_host: final_stones has {len(s)} cells for a {N}x{N} board, flags "
+                         f"{len(fl)} entries (L + 1 >= 1)")
+    K1 = max(int(unroll_steps), 0) + 1
+    t_own = np.empty((K1, N * N), np.float32)
+    mask = np.empty(K1, np.float32)
+    check(lib.mzgo_ownership_targets_host(ptr(s), ptr(fl), len(fl) - 1, N, int(start), int(symmetry),
+                                          int(unroll_steps), ptr(t_own), ptr(mask)))
+    return t_own, mask
+
+
 class DeviceReplay:
     """``DeviceReplay(board_size, capacity, max_moves, device)``: a ring of
     ``capacity`` games of at most ``max_moves`` moves on ``device``.
@@ -447,6 +492,44 @@ class DeviceReplay:
                                            ptr(out["obs0"]), ptr(out["acts"]), ptr(out["t_rew"]), ptr(out["t_pol"]),
                                            ptr(out["t_val"]), stream_of(self.device)))
         return out
+
+    # ---- ownership targets ----
+    def ownership(self, indices, starts, unroll_steps, symmetries=None):
+        """The ownership targets of B samples in one launch
+        (mzgo_replay_ownership; ``batch``'s indices, starts and symmetries):
+        ``(t_own f32 [B, K+1, N*N], own_mask f32 [B, K+1])`` on the device.
+        Row (b, k) is the final board of sample b's game seen by the colour to
+        move at position start + k under the sample's symmetry: +1 the mover
+        owns the point, -1 the opponent, 0 nobody, with mask 1 -- or zeros with
+        mask 0 past the final board and for a game that did not end (a game cut
+        off by the move cap has no winner and no ownership).
+        ``ownership_targets_host`` is the rule; the batch assembly is untouched."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int32).reshape(-1))
+        B, K = len(idx), int(unroll_steps)
+        st = np.ascontiguousarray(np.asarray(starts, dtype=np.int32).reshape(-1))
+        sy = None if symmetries is None else np.ascontiguousarray(np.asarray(symmetries, dtype=np.int32).reshape(-1))
+        if len(st) != B or (sy is not None and len(sy) != B):
+            raise ValueError("ownership: indices, starts and symmetries must have one entry per sample")
+        t_own, mask = self._ownership_out(B, K)
+        check(lib.mzgo_replay_ownership(self._h, ptr(idx), ptr(st), ptr(sy), B, K, ptr(t_own), ptr(mask),
+                                        stream_of(self.device)))
+        return t_own, mask
+
+    def ownership_from(self, sample, unroll_steps):
+        """``ownership`` for a drawn ``sample`` (what ``sample`` / ``sample_batch``
+        returned, or its ``items`` tensor), from the device items
+        (mzgo_replay_ownership_items): nothing crosses the bus, nothing
+        synchronises."""
+        items = self._items_of(sample)
+        B, K = items.shape[0], int(unroll_steps)
+        t_own, mask = self._ownership_out(B, K)
+        check(lib.mzgo_replay_ownership_items(self._h, ptr(items), B, K, ptr(t_own), ptr(mask),
+                                              stream_of(self.device)))
+        return t_own, mask
+
+    def _ownership_out(self, B, K):
+        K1 = max(K, 0) + 1
+        return (torch.empty(B, K1, self.N * self.N, device=self.device), torch.empty(B, K1, device=self.device))
 
     # ---- the device ledger and sampler ----
     # Independent of ``ledger`` above: the host ledger (``priorities``,

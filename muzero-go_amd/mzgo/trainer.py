@@ -116,6 +116,20 @@ on the device, every game of a batch at once) and trains on it:
   game's positions start from |root value - n-step search-value target|, n =
   ``td_steps`` (``unroll_steps`` under network targets).
 
+  ``TrainConfig.ownership_loss_weight`` (default 0 = off; batched mode with
+  ``fused_unroll`` and ``fused_loss``, the net on the GPU, a ``DeviceReplay``)
+  trains KataGo's ownership auxiliary target on the unroll's latents: a 1x1
+  conv of its own (``mzgo.OwnershipHead``, ``trainer.ownership_head``; the
+  net keeps its 22 tensors) predicts for every point who owns it on the game's
+  final board, seen by the colour to move at each unroll step.  The store gives
+  the targets for the step's items (``DeviceReplay.ownership`` /
+  ``ownership_from``, one small launch), ``mzgo.unroll(..., return_latents=True)``
+  the latents, ``mzgo.ownership_loss`` the per-sample losses, which are added to
+  the unroll loss's under the same importance weights; the head's two
+  parameters join the optimizer and the clip norm.  Priorities,
+  ``training_loss`` and the three totals keep their meaning (without
+  ownership); ``last["ownership_loss"]`` reports the ownership total.
+
 ``initial_inference_torch`` / ``recurrent_inference_torch`` restate
 main.py:72-144 with torch ops on the module's own parameters (reference
 mode, and the CPU).  Replay buffers restate main.py:158-244.
@@ -165,6 +179,7 @@ class TrainConfig:
     unroll_precision: str = "fp32"    # fused_unroll: "bf16" runs the dynamics conv's products on bf16 MFMA
     position_priorities: bool = False  # device_sampling: sample positions by |value - target| (MuZero, App. G)
     priority_floor: float = 0.0       # position_priorities: the smallest value error a weight is formed from; 0 = FLT_MIN
+    ownership_loss_weight: float = 0.0  # > 0: the ownership head's loss on the fused unroll's latents (DeviceReplay)
 
 
 def reward_value_transform(x, epsilon=0.001):
@@ -515,7 +530,7 @@ class MuZeroTrainer:
     trained on, under either ``value_target``; held until the next step)."""
 
     def __init__(self, net: MuZeroNet, config: TrainConfig = None, mode="reference", start_index=None,
-                 hip_forward=None, sample_seed=0, reanalyser=None):
+                 hip_forward=None, sample_seed=0, reanalyser=None, ownership_head=None):
         if mode not in ("reference", "batched"):
             raise ValueError(f"mode must be 'reference' or 'batched', not {mode!r}")
         self.net = net
@@ -547,6 +562,33 @@ class MuZeroTrainer:
         if not (0.0 <= c.priority_floor < float("inf")):
             raise ValueError(f"priority_floor must be finite and >= 0 (0 = float32's smallest normal), got "
                              f"{c.priority_floor}")
+        if not (0.0 <= c.ownership_loss_weight < float("inf")):
+            raise ValueError(f"ownership_loss_weight must be finite and >= 0 (0 = off), got {c.ownership_loss_weight}")
+        if c.ownership_loss_weight > 0:
+            if mode != "batched":
+                raise ValueError("ownership_loss_weight needs mode='batched' with fused_unroll and fused_loss: "
+                                 "mode='reference' is main.py's per-trajectory step, which has no ownership head")
+            if not c.fused_unroll:
+                raise ValueError("ownership_loss_weight needs fused_unroll=True: the ownership head reads the latents "
+                                 "mzgo.unroll returns (return_latents=True)")
+            if not c.fused_loss:
+                raise ValueError("ownership_loss_weight needs fused_loss=True: the ownership loss joins the per-sample "
+                                 "losses of mzgo.unroll_loss")
+            if next(net.parameters()).device.type != "cuda":
+                raise ValueError("ownership_loss_weight needs the net on the GPU (net.to('cuda')): "
+                                 "mzgo.ownership_loss has no eager fall-back")
+            from .ownership import OwnershipHead
+            if ownership_head is None:
+                ownership_head = OwnershipHead(net.latent_dim).to(next(net.parameters()).device)
+            if not isinstance(ownership_head, OwnershipHead) or ownership_head.latent_dim != net.latent_dim:
+                raise ValueError(f"ownership_head must be an OwnershipHead({net.latent_dim}) (the net's latent_dim)")
+            if ownership_head.conv.weight.device != next(net.parameters()).device:
+                raise ValueError("ownership_head must be on the net's device")
+        elif ownership_head is not None:
+            raise ValueError("ownership_head belongs to ownership_loss_weight > 0 (TrainConfig.ownership_loss_weight)")
+        # the ownership head (None: off): a module of its own -- the net keeps the reference's 22 tensors, and the
+        # engines, the weight packers and the search never see the head; its two parameters join the optimizer's
+        self.ownership_head = ownership_head
         if c.unroll_precision not in ("fp32", "bf16"):
             raise ValueError(f"unroll_precision must be 'fp32' or 'bf16', not {c.unroll_precision!r}")
         if c.unroll_precision == "bf16":
@@ -623,11 +665,11 @@ class MuZeroTrainer:
         if c.device_optimizer:
             from .optim import DeviceAdam
             # clip_grad_norm_, Adam and StepLR in one: ``scheduler`` has nothing left to step
-            self.optimizer = DeviceAdam(net.parameters(), lr=c.learning_rate, max_grad_norm=c.max_grad_norm,
+            self.optimizer = DeviceAdam(self._parameters(), lr=c.learning_rate, max_grad_norm=c.max_grad_norm,
                                         lr_step_size=c.lr_step_size, lr_gamma=c.lr_gamma)
             self.scheduler = None
         else:
-            self.optimizer = torch.optim.Adam(net.parameters(), lr=self.config.learning_rate)
+            self.optimizer = torch.optim.Adam(self._parameters(), lr=self.config.learning_rate)
             self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=self.config.lr_step_size,
                                                              gamma=self.config.lr_gamma)
         self.start_index = start_index or (lambda T: random.randint(0, T - 1))
@@ -638,6 +680,13 @@ class MuZeroTrainer:
     @property
     def device(self):
         return next(self.net.parameters()).device
+
+    def _parameters(self):
+        """What the optimizer steps and one clip norm covers: the net's 22 tensors, then the ownership head's two."""
+        params = list(self.net.parameters())
+        if self.ownership_head is not None:
+            params += list(self.ownership_head.parameters())
+        return params
 
     # -- targets ------------------------------------------------------------
     def _discounted(self, trajectory, index):
@@ -711,6 +760,9 @@ class MuZeroTrainer:
             return self._train_device(replay_buffer, batch_size)
         if self.config.device_sampling:
             raise ValueError("device_sampling needs a DeviceReplay: a host buffer has no device ledger to sample")
+        if self.ownership_head is not None:
+            raise ValueError("ownership_loss_weight needs a DeviceReplay: the ownership targets come from the final "
+                             "boards the store keeps (host trajectories are out of scope)")
         batch, indices = replay_buffer.sample(batch_size)
         if not batch or len(batch) < batch_size:
             return None
@@ -733,7 +785,7 @@ class MuZeroTrainer:
             lr = self.optimizer.lr
             self.optimizer.step()
             return lr
-        torch.nn.utils.clip_grad_norm_(self.net.parameters(), max_norm=self.config.max_grad_norm)
+        torch.nn.utils.clip_grad_norm_(self._parameters(), max_norm=self.config.max_grad_norm)
         self.optimizer.step()
         return self.optimizer.param_groups[0]["lr"]
 
@@ -814,7 +866,9 @@ class MuZeroTrainer:
         indices = replay.sample_indices(batch_size)
         starts = [self.start_index(replay.lengths[i]) for i in indices]
         syms = [self.symmetry_index() for _ in indices] if self.config.symmetries else None
-        avg = self._unroll_step(*self.device_targets(replay, indices, starts, syms), device_totals=True)
+        own = (replay.ownership(indices, starts, self.config.unroll_steps, syms)
+               if self.ownership_head is not None else None)
+        avg = self._unroll_step(*self.device_targets(replay, indices, starts, syms), device_totals=True, ownership=own)
         replay.update_priorities(indices, self._priorities(avg, len(indices)))
         self._scheduler_step()
         return avg
@@ -872,17 +926,20 @@ class MuZeroTrainer:
         else:                               # value_target="search": the assembly wrote the targets
             t_val = s["t_val"]
         self.last_t_val_device = t_val
+        # the ownership targets of the same items: one more small launch, nothing on the host
+        own = replay.ownership_from(s, c.unroll_steps) if self.ownership_head is not None else None
         avg = self._unroll_step(s["obs0"], s["acts"], t_val, s["t_rew"], s["t_pol"], device_totals=True,
-                                device_sample=(replay, s))
+                                device_sample=(replay, s), ownership=own)
         self._scheduler_step()
         return avg
 
-    def _finish_device(self, device_sample, per, totals, B, lr, value=None, t_val=None):
+    def _finish_device(self, device_sample, per, totals, B, lr, value=None, t_val=None, own_total=None):
         """The tail of a device-sampled step: the priorities from ``per`` (f32
         [B], unweighted) or the batch mean -- with ``position_priorities`` the
         sampled windows' position weights from ``value`` and ``t_val`` (f32
         [B, K+1]: the raw value outputs and targets) instead -- and the totals
-        (f64 [4], unweighted) left on the device for ``read_stats``."""
+        (f64 [4], unweighted; ``own_total`` f64 [1]: the ownership loss's, apart) left on the device for
+        ``read_stats``."""
         replay, sample = device_sample
         c = self.config
         if c.position_priorities:
@@ -893,7 +950,7 @@ class MuZeroTrainer:
             replay.update_device_priorities(sample, alpha=c.priority_alpha, mean=totals[:1] / B)
         self.last_per_sample = None
         self.last_per_sample_device = per if c.sample_priorities else None
-        self._pending = (totals, B, lr)
+        self._pending = (totals, B, lr, own_total)
         if c.deferred_stats:
             self.last = {}
             return totals[0] / B
@@ -903,11 +960,15 @@ class MuZeroTrainer:
         """``last`` of the latest step; with ``deferred_stats`` this is where the
         totals are copied from the device (one synchronising copy)."""
         if self._pending is not None:
-            totals, B, lr = self._pending
+            totals, B, lr, own_total = self._pending
             self._pending = None
-            total, tot_v, tot_p, tot_r = totals.tolist()
+            if own_total is not None:                   # (still one copy)
+                totals = torch.cat([totals, own_total])
+            total, tot_v, tot_p, tot_r, *own = totals.tolist()
             self.last = dict(training_loss=total / B, value_loss=tot_v / B, policy_loss=tot_p / B,
                              reward_loss=tot_r / B, lr=lr)
+            if own:
+                self.last["ownership_loss"] = own[0] / B
         return self.last
 
     def device_targets(self, replay, indices, starts, symmetries=None):
@@ -989,7 +1050,7 @@ class MuZeroTrainer:
         obs0 = np.stack([np.asarray(tr["observations"][s]) for tr, s in zip(batch, starts)])
         return obs0, acts, t_val, t_rew, t_pol
 
-    def _unroll_step(self, obs0, acts, t_val, t_rew, t_pol, device_totals=False, device_sample=None):
+    def _unroll_step(self, obs0, acts, t_val, t_rew, t_pol, device_totals=False, device_sample=None, ownership=None):
         """One optimizer step on the summed losses of B samples unrolled K
         steps, from targets on the device (obs0 f32 [B,6,N,N], acts i64 [B,K],
         t_val f32 [B,K+1], t_rew f32 [B,K], t_pol f32 [B,K+1,A]); returns the
@@ -1007,7 +1068,7 @@ class MuZeroTrainer:
         c, net = self.config, self.net
         B, K = acts.shape
         if c.fused_loss:
-            return self._unroll_step_fused(obs0, acts, t_val, t_rew, t_pol, device_sample)
+            return self._unroll_step_fused(obs0, acts, t_val, t_rew, t_pol, device_sample, ownership)
         tot = (lambda x: x.detach().sum().double()) if device_totals else (lambda x: x.sum().item())
         self.optimizer.zero_grad()
         steps = self._head_outputs(obs0, acts)
@@ -1080,18 +1141,33 @@ class MuZeroTrainer:
         priorities and the reported totals stay unweighted)."""
         return device_sample is not None and self.config.importance_beta > 0
 
-    def _unroll_step_fused(self, obs0, acts, t_val, t_rew, t_pol, device_sample=None):
+    def _unroll_step_fused(self, obs0, acts, t_val, t_rew, t_pol, device_sample=None, ownership=None):
         """``_unroll_step`` with the loss on the HIP kernel: the K + 1 steps'
         head outputs are collected and stacked once (``fused_unroll``:
         they come stacked from ``mzgo.unroll``), ``mzgo.unroll_loss`` gives
         ``per`` and the f64 totals in one call, and autograd enters the network
         through its saved head gradients.  One copy brings the totals (and,
-        with ``sample_priorities``, the per-sample losses) back."""
+        with ``sample_priorities``, the per-sample losses) back.
+
+        With ``ownership`` = (t_own, own_mask) (``ownership_loss_weight`` > 0;
+        ``fused_unroll``) the unroll also returns its latents, the ownership
+        head's per-sample losses (``mzgo.ownership_loss``) are added to ``per``
+        under the same importance weights, and the gradient that reaches the
+        latents goes back into the unroll's backward.  The priorities,
+        ``training_loss`` and the three totals stay those of ``per`` without
+        ownership; the ownership total is ``last["ownership_loss"]``."""
         from .loss import unroll_loss
         c, net = self.config, self.net
         B, K = acts.shape
         self.optimizer.zero_grad()
-        if c.fused_unroll:
+        per_own = own_total = None
+        if ownership is not None:
+            from .ownership import ownership_loss
+            from .unroll import unroll
+            lgs, vals, rews, latents = unroll(net, obs0, acts, c.unroll_precision, return_latents=True)
+            per_own, own_total = ownership_loss(latents, self.ownership_head, *ownership,
+                                                weight=c.ownership_loss_weight)
+        elif c.fused_unroll:
             from .unroll import unroll
             lgs, vals, rews = unroll(net, obs0, acts, c.unroll_precision)   # stacked as they come
         else:
@@ -1105,19 +1181,25 @@ class MuZeroTrainer:
         per, totals = unroll_loss(lgs, vals, rews, t_pol, t_val, t_rew, value_loss_weight=c.value_loss_weight,
                                   policy_loss_weight=c.policy_loss_weight, reward_loss_weight=c.reward_loss_weight,
                                   value_transform=c.use_value_transform)
-        loss = per.sum() if not self._weighted(device_sample) else (per * device_sample[1]["weight"]).sum()
+        trained = per if per_own is None else per + per_own
+        loss = trained.sum() if not self._weighted(device_sample) else (trained * device_sample[1]["weight"]).sum()
         loss.backward()
         lr = self._optimizer_step()
         self.last_per_sample = None
         if device_sample is not None:
             value = vals.detach().t().contiguous() if c.position_priorities else None    # [K+1, B] -> [B, K+1]
-            return self._finish_device(device_sample, per.detach(), totals, B, lr, value, t_val)
+            return self._finish_device(device_sample, per.detach(), totals, B, lr, value, t_val, own_total)
+        if own_total is not None:                       # (still one copy; the per-sample losses follow from index 5)
+            totals = torch.cat([totals, own_total])
+        n = totals.numel()
         if c.sample_priorities:
             back = torch.cat([totals, per.detach().double()]).tolist()
-            self.last_per_sample = np.asarray(back[4:], dtype=np.float32)
+            self.last_per_sample = np.asarray(back[n:], dtype=np.float32)
         else:
             back = totals.tolist()
         total, tot_v, tot_p, tot_r = back[:4]
         self.last = dict(training_loss=total / B, value_loss=tot_v / B, policy_loss=tot_p / B,
                          reward_loss=tot_r / B, lr=lr)
+        if own_total is not None:
+            self.last["ownership_loss"] = back[4] / B
         return total / B

@@ -6,8 +6,11 @@ C++) and one backward call (K + 17), instead of some forty torch ops per
 unroll step with their autograd nodes.
 
 ``unroll`` is differentiable in the net's 22 parameters only (there is no
-observation gradient); ``unroll_heads_host`` runs the heads' scalar functions
-serially on host arrays (the formulas' CPU check).
+observation gradient); with ``return_latents`` it also returns the K + 1
+latents and takes a gradient with respect to them, which is how an auxiliary
+loss (``mzgo.ownership``) attaches to the fused step; ``unroll_heads_host``
+runs the heads' scalar functions serially on host arrays (the formulas' CPU
+check).
 """
 import ctypes
 
@@ -75,9 +78,23 @@ def _net_table(net):
     return _tables[key]
 
 
+_latents = {}    # (B, K, C, N, emb_rows, precision) -> (offset_bytes, bytes) of the latents inside ``saved``
+
+
+def latents_span(B, K, C, N, emb_rows, precision="fp32"):
+    """``mzgo_unroll_latents``: (offset_bytes, bytes) of the step-major latents inside a call's ``saved``."""
+    key = (B, K, C, N, emb_rows, precision)
+    if key not in _latents:
+        off, size = ctypes.c_int64(), ctypes.c_int64()
+        check(lib.mzgo_unroll_latents(B, K, C, N, emb_rows, _precision(precision), ctypes.byref(off),
+                                      ctypes.byref(size)))
+        _latents[key] = (off.value, size.value)
+    return _latents[key]
+
+
 class _Unroll(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, obs0, acts, table, names, dims, precision, *params):
+    def forward(ctx, obs0, acts, table, names, dims, precision, return_latents, *params):
         B, K, C, N, emb_rows = dims
         dev = obs0.device
         A = N * N + 1
@@ -94,14 +111,25 @@ class _Unroll(torch.autograd.Function):
                                             PRECISIONS[precision], stream_of(dev)))
         ctx.save_for_backward(saved, *params)
         ctx.table, ctx.names, ctx.dims, ctx.precision = table, names, dims, precision
-        if K == 0:
-            return logits, value
-        return logits, value, reward
+        ctx.return_latents = return_latents
+        out = (logits, value) if K == 0 else (logits, value, reward)
+        if return_latents:
+            # a view of ``saved``, no copy: the backward reads the same memory, and autograd's version counter
+            # (shared by a view and its base) turns an in-place write into an error at backward() instead of
+            # wrong gradients.  A gradient that never arrives stays None (-> NULL), not a tensor of zeros.
+            ctx.set_materialize_grads(False)
+            off, size = latents_span(*dims, precision)
+            out += (saved[off:off + size].view(torch.float32).view(K + 1, B, C, N, N),)
+        return out
 
     @staticmethod
     @once_differentiable                 # the HIP backward builds no graph: create_graph=True is an error, not silence
-    def backward(ctx, g_logits, g_value, g_reward=None):
+    def backward(ctx, *g_out):
         saved, *params = ctx.saved_tensors
+        g_out = list(g_out)
+        g_latent = g_out.pop() if ctx.return_latents else None
+        g_logits, g_value = g_out[0], g_out[1]
+        g_reward = g_out[2] if len(g_out) > 2 else None
         table, names, dims, precision = ctx.table, ctx.names, ctx.dims, ctx.precision
         B, K, C, N, emb_rows = dims
         dev = saved.device
@@ -115,16 +143,27 @@ class _Unroll(torch.autograd.Function):
 
         g_logits, g_value = grad(g_logits, K + 1, B, A), grad(g_value, K + 1, B)
         g_reward = grad(g_reward, K, B) if K > 0 else None
+        if g_latent is not None:
+            g_latent = g_latent.to(torch.float32).contiguous()
+            if g_latent.data_ptr() % 16:             # (a slice of a larger tensor: the add kernel loads float4)
+                g_latent = g_latent.clone()
         work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
         # at K = 0 the dynamics take no part: no gradient, as autograd gives
         grads = [None if K == 0 and k.startswith("dynamics.") else torch.empty_like(p) for k, p in zip(names, params)]
         data = [p.detach() for p in params]
         with torch.cuda.device(dev):
-            check(lib.mzgo_unroll_backward_p(table.keys, table.pointers(data), table.shapes, table.ndims,
-                                             table.pointers(grads), table.n, ptr(saved), saved_bytes, ptr(g_logits),
-                                             ptr(g_value), ptr(g_reward), B, K, C, N, emb_rows, ptr(work), work_bytes,
-                                             PRECISIONS[precision], stream_of(dev)))
-        return (None, None, None, None, None, None, *grads)
+            if g_latent is None:         # (mzgo_unroll_backward_l with NULL: the same call)
+                check(lib.mzgo_unroll_backward_p(table.keys, table.pointers(data), table.shapes, table.ndims,
+                                                 table.pointers(grads), table.n, ptr(saved), saved_bytes,
+                                                 ptr(g_logits), ptr(g_value), ptr(g_reward), B, K, C, N, emb_rows,
+                                                 ptr(work), work_bytes, PRECISIONS[precision], stream_of(dev)))
+            else:
+                check(lib.mzgo_unroll_backward_l(table.keys, table.pointers(data), table.shapes, table.ndims,
+                                                 table.pointers(grads), table.n, ptr(saved), saved_bytes,
+                                                 ptr(g_logits), ptr(g_value), ptr(g_reward), ptr(g_latent), B, K, C, N,
+                                                 emb_rows, ptr(work), work_bytes, PRECISIONS[precision],
+                                                 stream_of(dev)))
+        return (None, None, None, None, None, None, None, *grads)
 
 
 def bf16_round_host(x):
@@ -136,7 +175,7 @@ def bf16_round_host(x):
     return out
 
 
-def unroll(net, obs0, acts, precision="fp32"):
+def unroll(net, obs0, acts, precision="fp32", return_latents=False):
     """The K-step unroll of ``net`` (a ``MuZeroNet`` on the GPU) from the
     observations ``obs0`` f32 [B, 6, N, N] under the actions ``acts`` i64
     [B, K] (``device_targets``' layout; None or [B, 0] for K = 0), values in
@@ -155,7 +194,17 @@ def unroll(net, obs0, acts, precision="fp32"):
     operands rounded to bfloat16 (nearest even) and float32 accumulation
     (``mzgo_unroll_forward_p`` with ``MZGO_PREC_BF16``, mzgo.h); the weights,
     the latents, every gradient and everything else stay float32.  It needs
-    ``latent_dim`` to be a multiple of 32.  Any other string is a ValueError."""
+    ``latent_dim`` to be a multiple of 32.  Any other string is a ValueError.
+
+    ``return_latents=True`` adds a fourth output, ``latents`` f32 [K+1, B, C, N,
+    N]: the K + 1 latents the heads read, step-major, handed out without a copy
+    as a view of the call's saved buffer (``mzgo_unroll_latents``; so they must
+    not be written in place, which autograd refuses at ``backward()``).
+    ``latents`` is differentiable: a gradient that arrives there -- an
+    auxiliary loss on the latents, ``mzgo.ownership_loss`` for one -- is added
+    to the heads' latent gradient before the chain
+    (``mzgo_unroll_backward_l``); when none arrives the backward is the call it
+    is without the flag, bit for bit."""
     from .resnet import ResMuZeroNet
     _precision(precision)
     if isinstance(net, ResMuZeroNet):
@@ -192,8 +241,10 @@ def unroll(net, obs0, acts, precision="fp32"):
             raise ValueError(f"mzgo.unroll: parameter '{k}' must be contiguous float32")
     table, names = _net_table(net)
     obs0 = obs0.detach().to(torch.float32).contiguous()
-    out = _Unroll.apply(obs0, acts, table, names, (B, K, C, N, net.max_action_size), precision, *params)
-    return (out[0], out[1], out[2] if K > 0 else None)
+    out = _Unroll.apply(obs0, acts, table, names, (B, K, C, N, net.max_action_size), precision, bool(return_latents),
+                        *params)
+    heads = (out[0], out[1], out[2] if K > 0 else None)
+    return heads + (out[-1],) if return_latents else heads
 
 
 def unroll_heads_host(params, latents, g_logits, g_value, g_reward):
