@@ -427,7 +427,8 @@ int mzgo_records_pack(mzgo_engine* eng, uint8_t* dst, int64_t capacity, int64_t*
  * key ids (mzgo_replay_info); priorities and sampling are the caller's
  * (mzgo.DeviceReplay keeps main.py's np.random sequence) unless the device
  * ledger and sampler further down are used (mzgo_replay_sample).  Calls on one store
- * must be ordered (one stream, or synchronised): they share index staging.
+ * must be ordered (one stream, or synchronised): they share index staging and
+ * the samplers' working tree.
  * A store is not thread-safe.  Every failure below is reported through
  * mzgo_last_error().
  *
@@ -745,7 +746,9 @@ int mzgo_replay_skipped_updates(mzgo_replay* replay, int64_t* count_host, void* 
  * App. G): a sampling weight per stored POSITION, pprio f64 [capacity][max_moves]
  * (already raised to alpha; rows t >= the game's length are never read), and a
  * sampler that draws (game, start) with probability w[game][start] / total.
- * Nothing is allocated until mzgo_replay_enable_positions; until then every
+ * Nothing is allocated until mzgo_replay_enable_positions (pprio and the
+ * counts of positions; the sampler's working tree is the store's one, which
+ * mzgo_replay_sample draws from as well); until then every
  * device call below returns MZGO_EINVAL and mzgo_last_error() names it.
  *
  * The weight of a position whose value error is err is

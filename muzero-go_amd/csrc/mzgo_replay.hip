@@ -14,8 +14,9 @@
 // between the draw and the assembly, the sampled windows' positions searched
 // again in place (k_replay_window_items, then the engine's in-place queue).
 // Opt-in on top of that ledger, a weight per stored position (PosLedger) and a
-// sampler that carries one draw's target through two more levels inside the
-// picked game (k_replay_possample_build, k_replay_possample_draw), with the
+// sampler that draws from the same tree and carries one draw's target through
+// two more levels inside the picked game (k_replay_possample_build,
+// k_replay_possample_draw), with the
 // positions' weights written back from the step's value errors.  Next to the
 // batch assembly, one more launch on the same items turns the games' final
 // boards into the ownership head's targets (k_replay_ownership).
@@ -337,9 +338,13 @@ __global__ void __launch_bounds__(kThreads) k_replay_new_games(Ledger L, int fir
 }
 
 // ---------------------------------------------------------------------------
-// The sampler: successive sampling without replacement from a 64-ary sum tree
+// The samplers: successive sampling without replacement from a 64-ary sum tree
 // (leaves = slots, level 1 = sums of 64 leaves, level 2 = sums of 64 of those;
-// every sum is element 63 of mzgo_replay.hpp's six-step scan).
+// every sum is element 63 of mzgo_replay.hpp's six-step scan).  The tree_*
+// functions below are the tree on one wave, once, for the game sampler's
+// kernels and the position sampler's (SumTreeHost, mzgo_replay.hpp, is their
+// serial form); a kernel adds what is its own: its leaves, how a picked game's
+// start is found, the population of its importance weights.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ double wave_scan64(double v, int lane) {
   for (int d = 1; d < 64; d <<= 1) {
@@ -358,18 +363,67 @@ __device__ __forceinline__ int wave_pick(double x, double p, double* target) {
   return j;
 }
 
-// a wave per group of 64 slots: the working leaves and the group's sum
-__global__ void __launch_bounds__(kThreads) k_replay_sample_build(Ledger L, const int* length) {
-  const int lane = threadIdx.x & 63, g = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
-  if (g >= L.n1) return;                                   // (the whole wave)
+// the build kernels' tail, on one wave: lane i's leaf of group g (the slots past the store's end: 0) and the group's sum
+__device__ __forceinline__ void tree_build_group(const SumTree& T, int g, double x, int lane) {
   const int i = g * 64 + lane;
-  double x = 0.0;
-  if (i < L.cap) {
-    x = length[i] > 0 ? L.prio[i] : 0.0;
-    L.leaf[i] = x;
-  }
+  if (i < T.cap) T.leaf[i] = x;
   const double p = wave_scan64(x, lane);
-  if (lane == 63) L.l1[g] = p;
+  if (lane == 63) T.l1[g] = p;
+}
+// the draw kernels' prologue, on their one wave: level 1 into s1 [64 * 64] (LDS), level 2 a lane each (returned)
+__device__ __forceinline__ double tree_prologue(const SumTree& T, double* s1, int lane) {
+  const int n1 = T.n1, n2 = (n1 + 63) / 64;
+  for (int i = lane; i < n2 * 64; i += 64) s1[i] = i < n1 ? T.l1[i] : 0.0;
+  __syncthreads();
+  double x2 = 0.0;                                         // lane i: level-2 entry i
+  for (int g = 0; g < n2; ++g) {
+    const double s = __shfl(wave_scan64(s1[g * 64 + lane], lane), 63);
+    if (lane == g) x2 = s;
+  }
+  return x2;
+}
+// one draw: target = u x total descends the three levels; the picked leaf is
+// removed and its two ancestors (s1, *x2) are summed again, never subtracted
+// from.  The caller syncs before the next draw reads the leaf and s1.
+__device__ __forceinline__ TreePick tree_draw(const SumTree& T, double* s1, double* x2, double u, int lane) {
+  const double p2 = wave_scan64(*x2, lane);
+  TreePick d;
+  d.total = __shfl(p2, 63);
+  d.target = u * d.total;
+  const int j2 = wave_pick(*x2, p2, &d.target);
+  const double x1 = s1[j2 * 64 + lane];
+  const int j1 = wave_pick(x1, wave_scan64(x1, lane), &d.target);
+  const int g1 = j2 * 64 + j1, i0 = g1 * 64 + lane;
+  double x0 = i0 < T.cap ? T.leaf[i0] : 0.0;
+  const int j0 = wave_pick(x0, wave_scan64(x0, lane), &d.target);
+  d.slot = min(g1 * 64 + j0, T.cap - 1);
+  d.w = __shfl(x0, j0);
+  if (lane == j0) {
+    x0 = 0.0;
+    T.leaf[d.slot] = 0.0;
+  }
+  const double sum0 = __shfl(wave_scan64(x0, lane), 63);
+  const double sum1 = __shfl(wave_scan64(lane == j1 ? sum0 : x1, lane), 63);
+  if (lane == j1) s1[g1] = sum0;
+  if (lane == j2) *x2 = sum1;
+  return d;
+}
+// the draw kernels' epilogue: importance weights out of a population of n, from
+// the picked weights (T.pick_w) and the total before any removal, over the batch's largest
+__device__ __forceinline__ void tree_weights(const SumTree& T, int B, int n, double total0, double beta, float* weight,
+                                             int lane) {
+  double vmax = 0.0;
+  for (int b = lane; b < B; b += 64) vmax = fmax(vmax, pow((double)n * T.pick_w[b] / total0, -beta));
+  for (int d = 32; d > 0; d >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, d));
+  for (int b = lane; b < B; b += 64) weight[b] = (float)(pow((double)n * T.pick_w[b] / total0, -beta) / vmax);
+}
+
+// a wave per group of 64 slots: the working leaves and the group's sum
+__global__ void __launch_bounds__(kThreads) k_replay_sample_build(SumTree T, const double* prio, const int* length) {
+  const int lane = threadIdx.x & 63, g = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+  if (g >= T.n1) return;                                   // (the whole wave)
+  const int i = g * 64 + lane;
+  tree_build_group(T, g, i < T.cap && length[i] > 0 ? prio[i] : 0.0, lane);
 }
 
 struct SampleOut {
@@ -378,59 +432,34 @@ struct SampleOut {
   uint32_t* gen;       // [B]    the slot's generation at the draw
   float* weight;       // [B]    importance weights (may be null)
 };
+// draw t's outputs (one lane): the sample, and its picked weight for the epilogue
+__device__ __forceinline__ void sample_write(const SampleOut& O, const SumTree& T, int t, int slot, int start,
+                                             int symmetry, int head, const uint32_t* gen, double w) {
+  O.items[3 * t] = slot;
+  O.items[3 * t + 1] = start;
+  O.items[3 * t + 2] = symmetry;
+  O.index[t] = (slot - head + T.cap) % T.cap;
+  O.gen[t] = gen[slot];
+  T.pick_w[t] = w;
+}
 
 // one workgroup of one wave: level 1 in LDS, level 2 a lane each, B draws
-__global__ void __launch_bounds__(64) k_replay_sample_draw(Ledger L, const int* length, int head, int B, uint64_t key,
-                                                           int symmetries, double beta, int n_valid, SampleOut O) {
+__global__ void __launch_bounds__(64) k_replay_sample_draw(SumTree T, const uint32_t* gen, const int* length, int head,
+                                                           int B, uint64_t key, int symmetries, double beta,
+                                                           int n_valid, SampleOut O) {
   __shared__ double s1[64 * 64];
   const int lane = threadIdx.x;
-  const int n1 = L.n1, n2 = (n1 + 63) / 64;
-  for (int i = lane; i < n2 * 64; i += 64) s1[i] = i < n1 ? L.l1[i] : 0.0;
-  __syncthreads();
-  double x2 = 0.0;                                         // lane i: level-2 entry i
-  for (int g = 0; g < n2; ++g) {
-    const double s = __shfl(wave_scan64(s1[g * 64 + lane], lane), 63);
-    if (lane == g) x2 = s;
-  }
+  double x2 = tree_prologue(T, s1, lane);
   double total0 = 0.0;
   for (int t = 0; t < B; ++t) {
-    const double p2 = wave_scan64(x2, lane);
-    const double total = __shfl(p2, 63);
-    if (t == 0) total0 = total;
-    double target = sample_u(key, t) * total;
-    const int j2 = wave_pick(x2, p2, &target);
-    const double x1 = s1[j2 * 64 + lane];
-    const int j1 = wave_pick(x1, wave_scan64(x1, lane), &target);
-    const int g1 = j2 * 64 + j1, i0 = g1 * 64 + lane;
-    double x0 = i0 < L.cap ? L.leaf[i0] : 0.0;
-    const int j0 = wave_pick(x0, wave_scan64(x0, lane), &target);
-    const int slot = min(g1 * 64 + j0, L.cap - 1);
-    const double w = __shfl(x0, j0);
-    // remove the leaf; its two ancestors are summed again, never subtracted from
-    if (lane == j0) {
-      x0 = 0.0;
-      L.leaf[slot] = 0.0;
-    }
-    const double sum0 = __shfl(wave_scan64(x0, lane), 63);
-    const double sum1 = __shfl(wave_scan64(lane == j1 ? sum0 : x1, lane), 63);
-    if (lane == j1) s1[g1] = sum0;
-    if (lane == j2) x2 = sum1;
-    if (lane == 0) {
-      O.items[3 * t] = slot;
-      O.items[3 * t + 1] = sample_start(key, t, length[slot]);
-      O.items[3 * t + 2] = sample_symmetry(key, t, symmetries);
-      O.index[t] = (slot - head + L.cap) % L.cap;
-      O.gen[t] = L.gen[slot];
-      L.pick_w[t] = w;
-    }
+    const TreePick d = tree_draw(T, s1, &x2, sample_u(key, t), lane);
+    if (t == 0) total0 = d.total;
+    if (lane == 0)                                         // the start: uniform over the game's moves
+      sample_write(O, T, t, d.slot, sample_start(key, t, length[d.slot]), sample_symmetry(key, t, symmetries), head,
+                   gen, d.w);
     __syncthreads();                                       // (the leaf and s1 before the next draw reads them)
   }
-  if (!O.weight) return;
-  // importance weights from the weights before any removal, over the batch's largest
-  double vmax = 0.0;
-  for (int b = lane; b < B; b += 64) vmax = fmax(vmax, pow((double)n_valid * L.pick_w[b] / total0, -beta));
-  for (int d = 32; d > 0; d >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, d));
-  for (int b = lane; b < B; b += 64) O.weight[b] = (float)(pow((double)n_valid * L.pick_w[b] / total0, -beta) / vmax);
+  if (O.weight) tree_weights(T, B, n_valid, total0, beta, O.weight, lane);
 }
 
 // a thread per sample: the sampled slot's new priority, unless the slot has
@@ -444,7 +473,7 @@ __global__ void __launch_bounds__(kThreads) k_replay_update_priorities(Ledger L,
   const int slot = items[3 * b];
   if (slot < 0 || slot >= L.cap || L.gen[slot] != gen[b]) return;
   const double p = per ? (double)per[b] : *mean;
-  if (!(p >= 0.0 && p <= 1.79769313486231570815e308)) {   // NaN, inf or negative: the slot keeps its weight
+  if (!(p >= 0.0 && p <= kDoubleMax)) {                    // NaN, inf or negative: the slot keeps its weight
     atomicAdd(L.skipped, 1u);
     return;
   }
@@ -487,7 +516,7 @@ __device__ __forceinline__ double wave_game_weight(const double* row, int len, i
 
 // a workgroup per group of 64 slots, a wave per 16 of them: the working leaves
 // (the games' weights), the group's sum and the group's count of positions
-__global__ void __launch_bounds__(kThreads) k_replay_possample_build(PosLedger P, const int* length) {
+__global__ void __launch_bounds__(kThreads) k_replay_possample_build(SumTree T, PosLedger P, const int* length) {
   __shared__ double s_w[64];
   __shared__ int s_len[64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = blockIdx.x;
@@ -503,88 +532,45 @@ __global__ void __launch_bounds__(kThreads) k_replay_possample_build(PosLedger P
   }
   __syncthreads();
   if (wave != 0) return;
-  const int i = g * 64 + lane;
-  const double x = s_w[lane];
-  if (i < P.cap) P.leaf[i] = x;
-  const double p = wave_scan64(x, lane);
+  tree_build_group(T, g, s_w[lane], lane);
   int np = s_len[lane];
   for (int d = 32; d > 0; d >>= 1) np += __shfl_xor(np, d);
-  if (lane == 63) {
-    P.l1[g] = p;
-    P.npos1[g] = np;
-  }
+  if (lane == 63) P.npos1[g] = np;
 }
 
 // k_replay_sample_draw over the games' weights, then the remainder of the same
 // target through the picked game's chunk sums and the picked chunk's positions:
 // one u picks (game, position).  One workgroup of one wave.
-__global__ void __launch_bounds__(64) k_replay_possample_draw(PosLedger P, const uint32_t* gen, const int* length,
-                                                              int head, int B, uint64_t key, int symmetries,
-                                                              double beta, SampleOut O) {
+__global__ void __launch_bounds__(64) k_replay_possample_draw(SumTree T, PosLedger P, const uint32_t* gen,
+                                                              const int* length, int head, int B, uint64_t key,
+                                                              int symmetries, double beta, SampleOut O) {
   __shared__ double s1[64 * 64];
   const int lane = threadIdx.x;
-  const int n1 = P.n1, n2 = (n1 + 63) / 64;
-  int n_pos = 0;
-  for (int i = lane; i < n2 * 64; i += 64) {
-    s1[i] = i < n1 ? P.l1[i] : 0.0;
-    n_pos += i < n1 ? P.npos1[i] : 0;
-  }
+  int n_pos = 0;                                           // the population of the importance weights
+  for (int i = lane; i < T.n1; i += 64) n_pos += P.npos1[i];
   for (int d = 32; d > 0; d >>= 1) n_pos += __shfl_xor(n_pos, d);
   if (lane == 0) *P.n_pos = n_pos;
-  __syncthreads();
-  double x2 = 0.0;                                         // lane i: level-2 entry i
-  for (int g = 0; g < n2; ++g) {
-    const double s = __shfl(wave_scan64(s1[g * 64 + lane], lane), 63);
-    if (lane == g) x2 = s;
-  }
+  double x2 = tree_prologue(T, s1, lane);
   double total0 = 0.0;
   for (int t = 0; t < B; ++t) {
-    const double p2 = wave_scan64(x2, lane);
-    const double total = __shfl(p2, 63);
-    if (t == 0) total0 = total;
-    double target = sample_u(key, t) * total;
-    const int j2 = wave_pick(x2, p2, &target);
-    const double x1 = s1[j2 * 64 + lane];
-    const int j1 = wave_pick(x1, wave_scan64(x1, lane), &target);
-    const int g1 = j2 * 64 + j1, i0 = g1 * 64 + lane;
-    double x0 = i0 < P.cap ? P.leaf[i0] : 0.0;
-    const int j0 = wave_pick(x0, wave_scan64(x0, lane), &target);
-    const int slot = min(g1 * 64 + j0, P.cap - 1);
-    // remove the leaf; its two ancestors are summed again, never subtracted from
-    if (lane == j0) {
-      x0 = 0.0;
-      P.leaf[slot] = 0.0;
-    }
-    const double sum0 = __shfl(wave_scan64(x0, lane), 63);
-    const double sum1 = __shfl(wave_scan64(lane == j1 ? sum0 : x1, lane), 63);
-    if (lane == j1) s1[g1] = sum0;
-    if (lane == j2) x2 = sum1;
-    // inside the game: its chunk sums (the build's additions again), then the chunk's positions
-    const int len = min(max(length[slot], 0), P.M);
-    const double* row = P.pprio + (size_t)slot * P.M;
+    TreePick d = tree_draw(T, s1, &x2, sample_u(key, t), lane);
+    if (t == 0) total0 = d.total;
+    // the start, inside the game: its chunk sums (the build's additions again), then the chunk's positions
+    const int len = min(max(length[d.slot], 0), P.M);
+    const double* row = P.pprio + (size_t)d.slot * P.M;
     double xc;
     (void)wave_game_weight(row, len, lane, &xc);
-    const int jc = wave_pick(xc, wave_scan64(xc, lane), &target);
+    const int jc = wave_pick(xc, wave_scan64(xc, lane), &d.target);
     const int tt = jc * 64 + lane;
     const double xt = tt < len ? row[tt] : 0.0;
-    const int jt = wave_pick(xt, wave_scan64(xt, lane), &target);
+    const int jt = wave_pick(xt, wave_scan64(xt, lane), &d.target);
     const double w = __shfl(xt, jt);
-    if (lane == 0) {
-      O.items[3 * t] = slot;
-      O.items[3 * t + 1] = max(min(jc * 64 + jt, len - 1), 0);
-      O.items[3 * t + 2] = sample_symmetry(key, t, symmetries);
-      O.index[t] = (slot - head + P.cap) % P.cap;
-      O.gen[t] = gen[slot];
-      P.pick_w[t] = w;
-    }
+    if (lane == 0)
+      sample_write(O, T, t, d.slot, max(min(jc * 64 + jt, len - 1), 0), sample_symmetry(key, t, symmetries), head, gen,
+                   w);
     __syncthreads();                                       // (the leaf and s1 before the next draw reads them)
   }
-  if (!O.weight) return;
-  // importance weights over positions, from the weights before any removal, over the batch's largest
-  double vmax = 0.0;
-  for (int b = lane; b < B; b += 64) vmax = fmax(vmax, pow((double)n_pos * P.pick_w[b] / total0, -beta));
-  for (int d = 32; d > 0; d >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, d));
-  for (int b = lane; b < B; b += 64) O.weight[b] = (float)(pow((double)n_pos * P.pick_w[b] / total0, -beta) / vmax);
+  if (O.weight) tree_weights(T, B, n_pos, total0, beta, O.weight, lane);
 }
 
 // a thread per (sample b, unroll step k): position start_b + k of the sampled
@@ -605,7 +591,7 @@ __global__ void __launch_bounds__(kThreads) k_replay_update_position_priorities(
   const int t = start + k;
   if (t >= length[slot] || t >= P.M) return;
   const double err = fabs((double)value[e] - (double)t_val[e]);
-  if (!(err <= 1.79769313486231570815e308)) {              // NaN or inf: the position keeps its weight
+  if (!(err <= kDoubleMax)) {                              // NaN or inf: the position keeps its weight
     atomicAdd(skipped, 1u);
     return;
   }
@@ -637,8 +623,9 @@ struct mzgo_replay {
   int* win_cnt = nullptr;
   int* win_items = nullptr;
   size_t win_cap = 0;                     // pairs win_items holds
-  Ledger L{};                             // device priorities, generations and the sampler's scratch
-  int n_valid = 0;                        // slots whose mirrored length is > 0 (the sampler's population)
+  Ledger L{};                             // device priorities and generations
+  SumTree T{};                            // the sampler's scratch: both samplers build it and draw from it
+  int n_valid = 0;                      // slots whose mirrored length is > 0 (the sampler's population)
   PosLedger P{};                          // the position ledger (mzgo_replay_enable_positions)
   bool positions = false;                 // whether P is allocated and kept
 
@@ -742,13 +729,15 @@ int mzgo_replay_create(int board_size, int capacity, int max_moves, int device, 
   chk(r->alloc(&r->win_cnt, 2 * M));
   Ledger& L = r->L;
   L.cap = capacity;
-  L.n1 = (capacity + 63) / 64;
   chk(r->alloc(&L.prio, cap));
   chk(r->alloc(&L.gen, cap));
-  chk(r->alloc(&L.leaf, cap));
-  chk(r->alloc(&L.l1, (size_t)L.n1));
-  chk(r->alloc(&L.pick_w, cap));
   chk(r->alloc(&L.skipped, 1));
+  SumTree& T = r->T;
+  T.cap = capacity;
+  T.n1 = (capacity + 63) / 64;
+  chk(r->alloc(&T.leaf, cap));
+  chk(r->alloc(&T.l1, (size_t)T.n1));
+  chk(r->alloc(&T.pick_w, cap));
   if (rc == MZGO_OK && (hipMemset(R.length, 0, cap * sizeof(int)) != hipSuccess ||
                         hipMemset(L.prio, 0, cap * sizeof(double)) != hipSuccess ||
                         hipMemset(L.gen, 0, cap * sizeof(uint32_t)) != hipSuccess ||
@@ -1283,6 +1272,7 @@ static int positions_check(const mzgo_replay* r, const char* who) {
 static int sample_launch(mzgo_replay* r, const char* who, bool positions, int B, uint64_t seed, uint32_t step,
                          int symmetries, double beta, int32_t* items, int32_t* index, uint32_t* gen, float* weight,
                          hipStream_t s) {
+  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);    // (every sampling entry point's)
   if (positions)
     if (int rc = positions_check(r, who)) return rc;
   if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
@@ -1296,21 +1286,20 @@ static int sample_launch(mzgo_replay* r, const char* who, bool positions, int B,
     return set_error(MZGO_EINVAL, "%s: null %s", who, !items ? "items" : !index ? "index" : "gen");
   const SampleOut O{items, index, gen, weight};
   const uint64_t key = stream_key(seed, kSamplerDomain, step);
+  const SumTree& T = r->T;
   if (positions) {
-    const PosLedger& P = r->P;
-    hipLaunchKernelGGL(k_replay_possample_build, dim3(P.n1), dim3(kThreads), 0, s, P, r->R.length);
+    hipLaunchKernelGGL(k_replay_possample_build, dim3(T.n1), dim3(kThreads), 0, s, T, r->P, r->R.length);
     RHIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_replay_possample_draw, dim3(1), dim3(64), 0, s, P, r->L.gen, r->R.length, r->head, B, key,
-                       symmetries != 0, beta, O);
+    hipLaunchKernelGGL(k_replay_possample_draw, dim3(1), dim3(64), 0, s, T, r->P, r->L.gen, r->R.length, r->head, B,
+                       key, symmetries != 0, beta, O);
     RHIPCHK(hipGetLastError());
     return MZGO_OK;
   }
-  const Ledger& L = r->L;
-  hipLaunchKernelGGL(k_replay_sample_build, dim3((L.n1 + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads), 0, s,
-                     L, r->R.length);
+  hipLaunchKernelGGL(k_replay_sample_build, dim3((T.n1 + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads), 0, s,
+                     T, r->L.prio, r->R.length);
   RHIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_replay_sample_draw, dim3(1), dim3(64), 0, s, L, r->R.length, r->head, B, key, symmetries != 0,
-                     beta, r->n_valid, O);
+  hipLaunchKernelGGL(k_replay_sample_draw, dim3(1), dim3(64), 0, s, T, r->L.gen, r->R.length, r->head, B, key,
+                     symmetries != 0, beta, r->n_valid, O);
   RHIPCHK(hipGetLastError());
   return MZGO_OK;
 }
@@ -1346,7 +1335,6 @@ static int sample_batch_values(mzgo_replay* r, const char* who, bool positions, 
 
 int mzgo_replay_sample(mzgo_replay* r, int B, uint64_t seed, uint32_t step, int symmetries, double beta,
                        int32_t* items, int32_t* index, uint32_t* gen, float* weight, void* stream) {
-  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_sample: null replay");
   return sample_launch(r, "mzgo_replay_sample", false, B, seed, step, symmetries, beta, items, index, gen, weight,
                        (hipStream_t)stream);
 }
@@ -1395,68 +1383,55 @@ int mzgo_replay_sample_positions_batch_values(mzgo_replay* r, int B, int unroll_
                              (hipStream_t)stream);
 }
 
+// the two sampler twins' common argument checks (``wname``: what the weights
+// ``w`` are called); *n_valid: the slots whose game has moves
+static int sample_host_check(const char* who, int cap, const char* wname, const double* w, const int32_t* length,
+                             const int32_t* items, const int32_t* index, int head, int B, double beta, int* n_valid) {
+  if (cap < 1 || cap > kSampleMaxCap)
+    return set_error(MZGO_EINVAL, "%s: capacity %d outside 1..64^3 = %d", who, cap, kSampleMaxCap);
+  if (!w || !length || !items || !index)
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !w ? wname : !length ? "length" : !items ? "items" : "index");
+  if (head < 0 || head >= cap) return set_error(MZGO_EINVAL, "%s: head %d outside 0..%d", who, head, cap - 1);
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
+  if (!(beta >= 0.0) || std::isinf(beta)) return set_error(MZGO_EINVAL, "%s: beta must be finite and >= 0", who);
+  *n_valid = 0;
+  for (int i = 0; i < cap; ++i) *n_valid += length[i] > 0;
+  if (B > *n_valid)
+    return set_error(MZGO_EINVAL, "%s: B %d exceeds the %d stored games that have moves", who, B, *n_valid);
+  return MZGO_OK;
+}
+// draw t's outputs, as the draw kernels write them
+static void sample_host_write(int32_t* items, int32_t* index, int t, int slot, int start, uint64_t key, int symmetries,
+                              int head, int cap) {
+  items[3 * t] = slot;
+  items[3 * t + 1] = start;
+  items[3 * t + 2] = sample_symmetry(key, t, symmetries != 0);
+  index[t] = (slot - head + cap) % cap;
+}
+
 int mzgo_replay_sample_host(const double* prio, const int32_t* length, int cap, int head, int B, uint64_t seed,
                             uint32_t step, int symmetries, double beta, int32_t* items, int32_t* index,
                             float* weight) {
   const char* who = "mzgo_replay_sample_host";
-  if (cap < 1 || cap > kSampleMaxCap)
-    return set_error(MZGO_EINVAL, "%s: capacity %d outside 1..64^3 = %d", who, cap, kSampleMaxCap);
-  if (!prio || !length || !items || !index)
-    return set_error(MZGO_EINVAL, "%s: null %s", who, !prio ? "prio" : !length ? "length" : !items ? "items" : "index");
-  if (head < 0 || head >= cap) return set_error(MZGO_EINVAL, "%s: head %d outside 0..%d", who, head, cap - 1);
-  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
-  if (!(beta >= 0.0) || std::isinf(beta)) return set_error(MZGO_EINVAL, "%s: beta must be finite and >= 0", who);
   int n_valid = 0;
+  if (int rc = sample_host_check(who, cap, "prio", prio, length, items, index, head, B, beta, &n_valid)) return rc;
   std::vector<double> leaf((size_t)cap);
   for (int i = 0; i < cap; ++i) {
     leaf[i] = length[i] > 0 ? prio[i] : 0.0;
     if (length[i] > 0 && !(prio[i] > 0.0 && !std::isinf(prio[i])))
       return set_error(MZGO_EINVAL, "%s: slot %d: weight %g (finite and > 0)", who, i, prio[i]);
-    n_valid += length[i] > 0;
   }
-  if (B > n_valid) return set_error(MZGO_EINVAL, "%s: B %d exceeds the %d stored games that have moves", who, B, n_valid);
-  // k_replay_sample_build and the draw kernel's prologue
-  const int n1 = (cap + 63) / 64, n2 = (n1 + 63) / 64;
-  std::vector<double> l1((size_t)n2 * 64, 0.0);
-  double x2[64] = {0.0}, p[64];
-  for (int g = 0; g < n1; ++g) {
-    scan64_host(leaf.data() + (size_t)g * 64, std::min(64, cap - g * 64), p);
-    l1[g] = p[63];
-  }
-  for (int g = 0; g < n2; ++g) {
-    scan64_host(l1.data() + (size_t)g * 64, 64, p);
-    x2[g] = p[63];
-  }
+  SumTreeHost tree(std::move(leaf));                        // k_replay_sample_build and the draw kernel's prologue
   const uint64_t key = stream_key(seed, kSamplerDomain, step);
   std::vector<double> pick_w((size_t)B);
   double total0 = 0.0;
   for (int t = 0; t < B; ++t) {
-    scan64_host(x2, 64, p);
-    const double total = p[63];
-    if (t == 0) total0 = total;
-    double target = sample_u(key, t) * total;
-    const int j2 = pick64_host(x2, 64, &target);
-    const int j1 = pick64_host(l1.data() + (size_t)j2 * 64, 64, &target);
-    const int g1 = j2 * 64 + j1;
-    const int n0 = std::max(0, std::min(64, cap - g1 * 64));
-    const int j0 = pick64_host(leaf.data() + (size_t)g1 * 64, n0, &target);
-    const int slot = std::min(g1 * 64 + j0, cap - 1);
-    pick_w[t] = leaf[slot];
-    leaf[slot] = 0.0;
-    scan64_host(leaf.data() + (size_t)g1 * 64, n0, p);
-    l1[g1] = p[63];
-    scan64_host(l1.data() + (size_t)j2 * 64, 64, p);
-    x2[j2] = p[63];
-    items[3 * t] = slot;
-    items[3 * t + 1] = sample_start(key, t, length[slot]);
-    items[3 * t + 2] = sample_symmetry(key, t, symmetries != 0);
-    index[t] = (slot - head + cap) % cap;
+    const TreePick d = tree.draw(sample_u(key, t));
+    if (t == 0) total0 = d.total;
+    pick_w[t] = d.w;
+    sample_host_write(items, index, t, d.slot, sample_start(key, t, length[d.slot]), key, symmetries, head, cap);
   }
-  if (weight) {
-    double vmax = 0.0;
-    for (int b = 0; b < B; ++b) vmax = std::max(vmax, std::pow((double)n_valid * pick_w[b] / total0, -beta));
-    for (int b = 0; b < B; ++b) weight[b] = (float)(std::pow((double)n_valid * pick_w[b] / total0, -beta) / vmax);
-  }
+  if (weight) importance_weights_host(pick_w.data(), B, (double)n_valid, total0, beta, weight);
   return MZGO_OK;
 }
 
@@ -1558,15 +1533,12 @@ int mzgo_replay_enable_positions(mzgo_replay* r, int td_steps, double discount, 
   hipStream_t s = (hipStream_t)stream;
   const size_t cap = r->R.cap, M = r->R.M;
   PosLedger Q{};
-  Q.cap = r->R.cap; Q.n1 = (r->R.cap + 63) / 64; Q.M = r->R.M;
+  Q.cap = r->R.cap; Q.M = r->R.M;
   Q.td_steps = td_steps; Q.init_mode = init_mode; Q.discount = discount; Q.alpha = alpha; Q.floor = floor;
   int rc = MZGO_OK;
   auto chk = [&](int x) { if (rc == MZGO_OK) rc = x; };
   chk(r->alloc(&Q.pprio, cap * M));
-  chk(r->alloc(&Q.leaf, cap));
-  chk(r->alloc(&Q.l1, (size_t)Q.n1));
-  chk(r->alloc(&Q.npos1, (size_t)Q.n1));
-  chk(r->alloc(&Q.pick_w, cap));
+  chk(r->alloc(&Q.npos1, (size_t)r->T.n1));
   chk(r->alloc(&Q.n_pos, 1));
   if (rc != MZGO_OK) return rc;                             // (what was allocated is freed with the store)
   RHIPCHK(hipMemsetAsync(Q.pprio, 0, cap * M * sizeof(double), s));
@@ -1649,22 +1621,15 @@ int mzgo_replay_sample_positions_host(const double* pprio, const int32_t* length
                                       uint64_t seed, uint32_t step, int symmetries, double beta, int32_t* items,
                                       int32_t* index, float* weight) {
   const char* who = "mzgo_replay_sample_positions_host";
-  if (cap < 1 || cap > kSampleMaxCap)
-    return set_error(MZGO_EINVAL, "%s: capacity %d outside 1..64^3 = %d", who, cap, kSampleMaxCap);
   if (M < 1 || M > kPositionMaxMoves)
     return set_error(MZGO_EINVAL, "%s: max_moves %d outside 1..%d", who, M, kPositionMaxMoves);
-  if (!pprio || !length || !items || !index)
-    return set_error(MZGO_EINVAL, "%s: null %s", who,
-                     !pprio ? "pprio" : !length ? "length" : !items ? "items" : "index");
-  if (head < 0 || head >= cap) return set_error(MZGO_EINVAL, "%s: head %d outside 0..%d", who, head, cap - 1);
-  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
-  if (!(beta >= 0.0) || std::isinf(beta)) return set_error(MZGO_EINVAL, "%s: beta must be finite and >= 0", who);
+  int n_valid = 0;
+  if (int rc = sample_host_check(who, cap, "pprio", pprio, length, items, index, head, B, beta, &n_valid)) return rc;
   auto len_of = [&](int i) { return std::min(std::max(length[i], 0), M); };
   // k_replay_possample_build and the draw kernel's prologue
-  int n_valid = 0;
   long long n_pos = 0;
   std::vector<double> leaf((size_t)cap);
-  double csum[64], p[64];
+  double csum[64];
   for (int i = 0; i < cap; ++i) {
     const int L = len_of(i);
     const double* row = pprio + (size_t)i * M;
@@ -1674,59 +1639,26 @@ int mzgo_replay_sample_positions_host(const double* pprio, const int32_t* length
     leaf[i] = L > 0 ? game_weight_host(row, L, csum) : 0.0;
     if (L > 0 && !(leaf[i] > 0.0 && !std::isinf(leaf[i])))
       return set_error(MZGO_EINVAL, "%s: slot %d: the game's weight is %g (finite and > 0)", who, i, leaf[i]);
-    n_valid += L > 0;
     n_pos += L;
   }
-  if (B > n_valid) return set_error(MZGO_EINVAL, "%s: B %d exceeds the %d stored games that have moves", who, B, n_valid);
-  const int n1 = (cap + 63) / 64, n2 = (n1 + 63) / 64;
-  std::vector<double> l1((size_t)n2 * 64, 0.0);
-  double x2[64] = {0.0};
-  for (int g = 0; g < n1; ++g) {
-    scan64_host(leaf.data() + (size_t)g * 64, std::min(64, cap - g * 64), p);
-    l1[g] = p[63];
-  }
-  for (int g = 0; g < n2; ++g) {
-    scan64_host(l1.data() + (size_t)g * 64, 64, p);
-    x2[g] = p[63];
-  }
+  SumTreeHost tree(std::move(leaf));
   const uint64_t key = stream_key(seed, kSamplerDomain, step);
   std::vector<double> pick_w((size_t)B);
   double total0 = 0.0;
   for (int t = 0; t < B; ++t) {
-    scan64_host(x2, 64, p);
-    const double total = p[63];
-    if (t == 0) total0 = total;
-    double target = sample_u(key, t) * total;
-    const int j2 = pick64_host(x2, 64, &target);
-    const int j1 = pick64_host(l1.data() + (size_t)j2 * 64, 64, &target);
-    const int g1 = j2 * 64 + j1;
-    const int n0 = std::max(0, std::min(64, cap - g1 * 64));
-    const int j0 = pick64_host(leaf.data() + (size_t)g1 * 64, n0, &target);
-    const int slot = std::min(g1 * 64 + j0, cap - 1);
-    leaf[slot] = 0.0;
-    scan64_host(leaf.data() + (size_t)g1 * 64, n0, p);
-    l1[g1] = p[63];
-    scan64_host(l1.data() + (size_t)j2 * 64, 64, p);
-    x2[j2] = p[63];
-    // inside the game: its chunk sums, then the chunk's positions
-    const int L = len_of(slot);
-    const double* row = pprio + (size_t)slot * M;
+    TreePick d = tree.draw(sample_u(key, t));
+    if (t == 0) total0 = d.total;
+    // the start, inside the game: its chunk sums, then the chunk's positions
+    const int L = len_of(d.slot);
+    const double* row = pprio + (size_t)d.slot * M;
     (void)game_weight_host(row, L, csum);
-    const int jc = pick64_host(csum, 64, &target);
+    const int jc = pick64_host(csum, 64, &d.target);
     const int nt = std::max(0, std::min(64, L - jc * 64));
-    const int jt = pick64_host(nt > 0 ? row + (size_t)jc * 64 : row, nt, &target);
-    const int start = std::max(std::min(jc * 64 + jt, L - 1), 0);
+    const int jt = pick64_host(nt > 0 ? row + (size_t)jc * 64 : row, nt, &d.target);
     pick_w[t] = jt < nt ? row[(size_t)jc * 64 + jt] : 0.0;
-    items[3 * t] = slot;
-    items[3 * t + 1] = start;
-    items[3 * t + 2] = sample_symmetry(key, t, symmetries != 0);
-    index[t] = (slot - head + cap) % cap;
+    sample_host_write(items, index, t, d.slot, std::max(std::min(jc * 64 + jt, L - 1), 0), key, symmetries, head, cap);
   }
-  if (weight) {
-    double vmax = 0.0;
-    for (int b = 0; b < B; ++b) vmax = std::max(vmax, std::pow((double)n_pos * pick_w[b] / total0, -beta));
-    for (int b = 0; b < B; ++b) weight[b] = (float)(std::pow((double)n_pos * pick_w[b] / total0, -beta) / vmax);
-  }
+  if (weight) importance_weights_host(pick_w.data(), B, (double)n_pos, total0, beta, weight);
   return MZGO_OK;
 }
 

@@ -3,8 +3,10 @@
 // (host and device, so that the tables a test reads are the kernel's), and the
 // ring's arrays and the ingest of one game (a device function: the store's
 // own ingest kernel and k_selfplay_games run the same text), the device
-// priority ledger and the sampler's order of additions, descent rule and
-// fallback (host and device: the sampler's host twin runs them), the position
+// priority ledger, the one sum tree both samplers draw from (its scratch, its
+// order of additions, descent rule and fallback, host and device; its host
+// serial form -- build, one draw with the leaf's removal, importance weights
+// -- which both samplers' host twins run), the position
 // ledger and its weight rules (host and device likewise), the window
 // of a sample and the item list of a batch's windows (host and device
 // likewise) with the in-place reanalysis queue's arguments, the search-value
@@ -15,8 +17,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <utility>
+#include <vector>
 
 #include "mzgo_common.hpp"
 
@@ -285,15 +290,31 @@ struct ReanalyseStoreArgs {
 // Store, which the ingest and self-play kernels take by value.
 // ---------------------------------------------------------------------------
 struct Ledger {
-  int cap, n1;         // slots; level-1 entries = ceil(cap / 64)
+  int cap;             // slots
   double* prio;        // [cap]  the sampling weight (already raised to alpha); 1.0 for a new game
   uint32_t* gen;       // [cap]  + 1 whenever a game is written into the slot
-  double* leaf;        // [cap]  sampler scratch: length > 0 ? prio : 0, picked leaves zeroed
-  double* l1;          // [n1]   sampler scratch: the sums of 64 leaves
-  double* pick_w;      // [cap]  sampler scratch: the picked games' weights, in draw order
   unsigned* skipped;   // [1]    priority updates refused (a loss that is not finite or < 0)
 };
+// The sampler's scratch and nothing else: the 64-ary sum tree a draw descends
+// (leaves = slots, level 1 = sums of 64 leaves; level 2, sums of 64 of those,
+// lives in the draw kernel's lanes).  The store owns one; the game sampler and
+// the position sampler both build it and draw from it (calls on one store are
+// ordered, mzgo.h), each with its own leaves: a game's weight.
+struct SumTree {
+  int cap, n1;         // slots; level-1 entries = ceil(cap / 64)
+  double* leaf;        // [cap]  length > 0 ? the game's weight : 0, picked leaves zeroed
+  double* l1;          // [n1]   the sums of 64 leaves
+  double* pick_w;      // [cap]  the picked games' (or positions') weights, in draw order
+};
+// one draw from the tree (host and device forms: SumTreeHost::draw, tree_draw in mzgo_replay.hip)
+struct TreePick {
+  int slot;            // the picked leaf
+  double w;            // its weight, before the draw removed it
+  double target;       // what is left of the target below the leaf: the position sampler descends on with it
+  double total;        // the tree's total before the draw
+};
 
+constexpr double kDoubleMax = 1.79769313486231570815e308;   // x <= kDoubleMax: x is finite (and no NaN)
 constexpr uint32_t kSamplerDomain = 0x53414D50u;   // stream_key's "game" word of the sampler's draws
 constexpr int kSampleMaxCap = 64 * 64 * 64;        // three levels of 64
 enum : uint32_t { TAG_SAMPLE = 5, TAG_START = 6, TAG_SYM = 7 };
@@ -338,7 +359,8 @@ __host__ __device__ __forceinline__ double priority_of(double p, double alpha) {
 // w[game][start] / total (mzgo_replay.hip: k_replay_new_positions,
 // k_replay_possample_*, k_replay_update_position_priorities).  Kept apart from
 // Store and Ledger, which the existing kernels take by value; allocated only
-// when enabled.  The generations and the count of refused updates are Ledger's.
+// when enabled.  The generations and the count of refused updates are Ledger's,
+// the tree the draw descends over the games' weights is the store's SumTree.
 //
 // A game's weight is not stored: it is formed from rows 0 .. L - 1 of its pprio
 // row in the sampler's one order of additions -- chunks of 64 positions, a
@@ -349,15 +371,12 @@ __host__ __device__ __forceinline__ double priority_of(double p, double alpha) {
 constexpr int kPositionMaxMoves = 64 * 64;         // two levels of 64 inside a game
 enum : int { POS_INIT_TD = 0, POS_INIT_UNIFORM = 1 };
 struct PosLedger {
-  int cap, n1, M;      // slots; level-1 entries = ceil(cap / 64); max_moves (pprio's row length)
+  int cap, M;          // slots; max_moves (pprio's row length)
   int td_steps;        // the n of a new position's |root value - n-step target|
   int init_mode;       // POS_INIT_TD, or POS_INIT_UNIFORM: 1.0 for every new position
   double discount, alpha, floor;
   double* pprio;       // [cap][M]  position t's sampling weight (already raised to alpha); rows t >= length: never read
-  double* leaf;        // [cap]  sampler scratch: length > 0 ? the game's weight : 0, picked leaves zeroed
-  double* l1;          // [n1]   sampler scratch: the sums of 64 leaves
-  int* npos1;          // [n1]   sampler scratch: the moves of 64 slots' games
-  double* pick_w;      // [cap]  sampler scratch: the picked positions' weights, in draw order
+  int* npos1;          // [ceil(cap / 64)]  sampler scratch: the moves of 64 slots' games
   int* n_pos;          // [1]    the stored positions at the last draw (the sum of npos1)
 };
 // the stored weight of a position whose value error is ``err`` (finite, >= 0):
@@ -373,7 +392,7 @@ __host__ __device__ __forceinline__ double position_td_priority(const double* re
                                                                 double alpha) {
   const double err = fabs(root_value[t] - (double)search_value_target(reward, root_value, L, t, td_steps, discount));
   // (a stored value that is not finite: the floor, so that the position can still be drawn)
-  return position_priority_of(err <= 1.79769313486231570815e308 ? err : floor, floor, alpha);
+  return position_priority_of(err <= kDoubleMax ? err : floor, floor, alpha);
 }
 
 // host serial forms of the scan and of one level's pick (the twin's)
@@ -411,6 +430,55 @@ inline double game_weight_host(const double* row, int L, double* csum) {
   }
   scan64_host(csum, 64, p);
   return p[63];
+}
+
+// host serial form of the tree (both twins'): the build kernels' tail and the
+// draw kernels' prologue, one draw, and the importance weights
+struct SumTreeHost {
+  int cap;
+  std::vector<double> leaf, l1;          // [cap]; [n2 * 64], the entries past ceil(cap / 64): 0
+  double x2[64] = {0.0};                 // level 2
+  explicit SumTreeHost(std::vector<double> leaves) : cap((int)leaves.size()), leaf(std::move(leaves)) {
+    const int n1 = (cap + 63) / 64, n2 = (n1 + 63) / 64;
+    double p[64];
+    l1.assign((size_t)n2 * 64, 0.0);
+    for (int g = 0; g < n1; ++g) {
+      scan64_host(leaf.data() + (size_t)g * 64, cap - g * 64 < 64 ? cap - g * 64 : 64, p);
+      l1[g] = p[63];
+    }
+    for (int g = 0; g < n2; ++g) {
+      scan64_host(l1.data() + (size_t)g * 64, 64, p);
+      x2[g] = p[63];
+    }
+  }
+  // target = u x total descends the three levels; the picked leaf is removed
+  // and its two ancestors are summed again, never subtracted from
+  TreePick draw(double u) {
+    double p[64];
+    scan64_host(x2, 64, p);
+    TreePick d{0, 0.0, u * p[63], p[63]};
+    const int j2 = pick64_host(x2, 64, &d.target);
+    const int j1 = pick64_host(l1.data() + (size_t)j2 * 64, 64, &d.target);
+    const int g1 = j2 * 64 + j1;
+    const int n0 = cap - g1 * 64 < 0 ? 0 : cap - g1 * 64 < 64 ? cap - g1 * 64 : 64;
+    const int j0 = pick64_host(leaf.data() + (size_t)g1 * 64, n0, &d.target);
+    d.slot = g1 * 64 + j0 < cap - 1 ? g1 * 64 + j0 : cap - 1;
+    d.w = leaf[d.slot];
+    leaf[d.slot] = 0.0;
+    scan64_host(leaf.data() + (size_t)g1 * 64, n0, p);
+    l1[g1] = p[63];
+    scan64_host(l1.data() + (size_t)j2 * 64, 64, p);
+    x2[j2] = p[63];
+    return d;
+  }
+};
+// the importance weights of B draws from their picked weights, out of a
+// population of n and the total before any removal: (n w / total0)^-beta over
+// the batch's largest
+inline void importance_weights_host(const double* pick_w, int B, double n, double total0, double beta, float* weight) {
+  double vmax = 0.0;
+  for (int b = 0; b < B; ++b) vmax = std::max(vmax, std::pow(n * pick_w[b] / total0, -beta));
+  for (int b = 0; b < B; ++b) weight[b] = (float)(std::pow(n * pick_w[b] / total0, -beta) / vmax);
 }
 
 // mzgo_capi.hip: fill *v from an engine (no checks beyond the null pointer)

@@ -136,6 +136,22 @@ def finish_values(val, factor, has_boot, value):
     return t_val
 
 
+def _draw_args(seed, step, symmetries, beta):
+    """A draw's (seed, step, symmetries, beta) as the library takes them."""
+    return int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, int(bool(symmetries)), float(beta)
+
+
+def _sample_twin(fn, weights, length, dims, head, batch_size, draw):
+    """Both sampler twins' call: ``fn(weights, length, *dims, head, B, *draw,
+    items, index, weight)`` into fresh numpy buffers."""
+    B = int(batch_size)
+    items = np.empty((max(B, 0), 3), np.int32)
+    index = np.empty(max(B, 0), np.int32)
+    weight = np.empty(max(B, 0), np.float32)
+    check(fn(ptr(weights), ptr(length), *dims, int(head), B, *draw, ptr(items), ptr(index), ptr(weight)))
+    return dict(items=items, index=index, weight=weight)
+
+
 def sample_host(prio, length, head, batch_size, *, seed, step, symmetries=False, beta=0.0):
     """The device sampler's host twin (mzgo_replay_sample_host: the kernels'
     own scan, descent and fallback functions run serially; no GPU).  ``prio``
@@ -147,14 +163,8 @@ def sample_host(prio, length, head, batch_size, *, seed, step, symmetries=False,
     length = np.ascontiguousarray(np.asarray(length, dtype=np.int32).reshape(-1))
     if len(prio) != len(length):
         raise ValueError("sample_host: prio and length have one entry per slot")
-    B = int(batch_size)
-    items = np.empty((max(B, 0), 3), np.int32)
-    index = np.empty(max(B, 0), np.int32)
-    weight = np.empty(max(B, 0), np.float32)
-    check(lib.mzgo_replay_sample_host(ptr(prio), ptr(length), len(prio), int(head), B, int(seed) & (2 ** 64 - 1),
-                                      int(step) & 0xFFFFFFFF, int(bool(symmetries)), float(beta), ptr(items),
-                                      ptr(index), ptr(weight)))
-    return dict(items=items, index=index, weight=weight)
+    return _sample_twin(lib.mzgo_replay_sample_host, prio, length, (len(prio),), head, batch_size,
+                        _draw_args(seed, step, symmetries, beta))
 
 
 def sample_positions_host(pprio, length, head, batch_size, *, seed, step, symmetries=False, beta=0.0):
@@ -168,15 +178,8 @@ def sample_positions_host(pprio, length, head, batch_size, *, seed, step, symmet
     length = np.ascontiguousarray(np.asarray(length, dtype=np.int32).reshape(-1))
     if pprio.ndim != 2 or len(pprio) != len(length):
         raise ValueError("sample_positions_host: pprio is [cap, M] and length has one entry per slot")
-    B = int(batch_size)
-    items = np.empty((max(B, 0), 3), np.int32)
-    index = np.empty(max(B, 0), np.int32)
-    weight = np.empty(max(B, 0), np.float32)
-    check(lib.mzgo_replay_sample_positions_host(ptr(pprio), ptr(length), pprio.shape[0], pprio.shape[1], int(head), B,
-                                                int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF,
-                                                int(bool(symmetries)), float(beta), ptr(items), ptr(index),
-                                                ptr(weight)))
-    return dict(items=items, index=index, weight=weight)
+    return _sample_twin(lib.mzgo_replay_sample_positions_host, pprio, length, pprio.shape, head, batch_size,
+                        _draw_args(seed, step, symmetries, beta))
 
 
 def position_priorities_host(rewards, root_values, td_steps, discount, alpha=1.0, floor=None):
@@ -347,6 +350,17 @@ class DeviceReplay:
         gids = np.zeros(self.capacity, np.int32)
         check(lib.mzgo_replay_info(self._h, ctypes.byref(size), None, ptr(lengths), ptr(gids)))
         return lengths[:size.value], gids[:size.value]
+
+    def _slot_order(self):
+        """What the host twins take per ring SLOT: the slots of the games held
+        (logical order), the ``length`` array i32 [capacity] (empty slots 0)
+        and the head."""
+        size, head = ctypes.c_int32(), ctypes.c_int32()
+        check(lib.mzgo_replay_info(self._h, ctypes.byref(size), ctypes.byref(head), None, None))
+        slots = (head.value + np.arange(size.value)) % self.capacity
+        length = np.zeros(self.capacity, np.int32)
+        length[slots] = self._info()[0]
+        return slots, length, head.value
 
     def _pushed(self, n):
         """Enter the last n games the store took into the ledger."""
@@ -561,12 +575,36 @@ class DeviceReplay:
         ``items`` i32 [B,3] (slot, start, symmetry), ``index`` i32 [B]
         (logical, oldest = 0), ``gen`` i32 [B] (the slots' generations, u32
         bits) and ``weight`` f32 [B] (importance weights, all 1 at beta 0)."""
+        return self._sample(False, batch_size, _draw_args(seed, step, symmetries, beta))
+
+    # the three sample calls, for the game sampler and (``positions``) the position sampler
+    def _sample(self, positions, batch_size, draw):
         B = int(batch_size)
         s = self._sample_out(B)
-        check(lib.mzgo_replay_sample(self._h, B, int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, int(bool(symmetries)),
-                                     float(beta), ptr(s["items"]), ptr(s["index"]), ptr(s["gen"]), ptr(s["weight"]),
-                                     stream_of(self.device)))
+        fn = lib.mzgo_replay_sample_positions if positions else lib.mzgo_replay_sample
+        check(fn(self._h, B, *draw, ptr(s["items"]), ptr(s["index"]), ptr(s["gen"]), ptr(s["weight"]),
+                 stream_of(self.device)))
         return s
+
+    def _sample_batch(self, positions, batch_size, unroll_steps, discount, draw):
+        B, K = int(batch_size), int(unroll_steps)
+        out = self._batch_out(B, K)
+        out.update(self._sample_out(B))
+        fn = lib.mzgo_replay_sample_positions_batch if positions else lib.mzgo_replay_sample_batch
+        check(fn(self._h, B, K, float(discount), *draw, ptr(out["items"]), ptr(out["index"]), ptr(out["gen"]),
+                 ptr(out["weight"]), ptr(out["obs0"]), ptr(out["boot_obs"]), ptr(out["acts"]), ptr(out["t_rew"]),
+                 ptr(out["t_pol"]), ptr(out["val"]), ptr(out["factor"]), ptr(out["has_boot"]), stream_of(self.device)))
+        return out
+
+    def _sample_batch_values(self, positions, batch_size, unroll_steps, td_steps, discount, draw):
+        B, K = int(batch_size), int(unroll_steps)
+        out = self._values_out(B, K)
+        out.update(self._sample_out(B))
+        fn = lib.mzgo_replay_sample_positions_batch_values if positions else lib.mzgo_replay_sample_batch_values
+        check(fn(self._h, B, K, int(td_steps), float(discount), *draw, ptr(out["items"]), ptr(out["index"]),
+                 ptr(out["gen"]), ptr(out["weight"]), ptr(out["obs0"]), ptr(out["acts"]), ptr(out["t_rew"]),
+                 ptr(out["t_pol"]), ptr(out["t_val"]), stream_of(self.device)))
+        return out
 
     def sample_batch(self, batch_size, unroll_steps, discount, *, seed, step, symmetries=False, beta=0.0):
         """``sample`` and ``batch`` in one call without the host
@@ -574,16 +612,7 @@ class DeviceReplay:
         start, symmetry) triples plus ``sample``'s ``items``, ``index``,
         ``gen`` and ``weight``.  The draw depends on (seed, step) and the
         device weights only; it is ``sample_host``'s, bit for bit."""
-        B, K = int(batch_size), int(unroll_steps)
-        out = self._batch_out(B, K)
-        out.update(self._sample_out(B))
-        check(lib.mzgo_replay_sample_batch(self._h, B, K, float(discount), int(seed) & (2 ** 64 - 1),
-                                           int(step) & 0xFFFFFFFF, int(bool(symmetries)), float(beta),
-                                           ptr(out["items"]), ptr(out["index"]), ptr(out["gen"]), ptr(out["weight"]),
-                                           ptr(out["obs0"]), ptr(out["boot_obs"]), ptr(out["acts"]), ptr(out["t_rew"]),
-                                           ptr(out["t_pol"]), ptr(out["val"]), ptr(out["factor"]), ptr(out["has_boot"]),
-                                           stream_of(self.device)))
-        return out
+        return self._sample_batch(False, batch_size, unroll_steps, discount, _draw_args(seed, step, symmetries, beta))
 
     def batch_from(self, sample, unroll_steps, discount):
         """``batch``'s dict for a drawn ``sample`` (what ``sample`` returned, or
@@ -605,16 +634,8 @@ class DeviceReplay:
         """``sample`` and ``batch_values`` in one call without the host
         (mzgo_replay_sample_batch_values): ``sample_batch``'s draw, with
         ``batch_values``' five tensors for the sampled triples."""
-        B, K = int(batch_size), int(unroll_steps)
-        out = self._values_out(B, K)
-        out.update(self._sample_out(B))
-        check(lib.mzgo_replay_sample_batch_values(self._h, B, K, int(td_steps), float(discount),
-                                                  int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF,
-                                                  int(bool(symmetries)), float(beta), ptr(out["items"]),
-                                                  ptr(out["index"]), ptr(out["gen"]), ptr(out["weight"]),
-                                                  ptr(out["obs0"]), ptr(out["acts"]), ptr(out["t_rew"]),
-                                                  ptr(out["t_pol"]), ptr(out["t_val"]), stream_of(self.device)))
-        return out
+        return self._sample_batch_values(False, batch_size, unroll_steps, td_steps, discount,
+                                         _draw_args(seed, step, symmetries, beta))
 
     def batch_values_from(self, sample, unroll_steps, td_steps, discount):
         """``batch_values``' dict for a drawn ``sample`` (what ``sample``
@@ -687,15 +708,10 @@ class DeviceReplay:
     def sample_host(self, batch_size, *, seed, step, symmetries=False, beta=0.0):
         """The sampler's host twin on this store's present weights (copied
         back) and lengths: numpy ``items``, ``index``, ``weight``."""
-        size, head = ctypes.c_int32(), ctypes.c_int32()
-        check(lib.mzgo_replay_info(self._h, ctypes.byref(size), ctypes.byref(head), None, None))
-        lengths, _ = self._info()
-        slots = (head.value + np.arange(size.value)) % self.capacity
-        prio, length = np.zeros(self.capacity), np.zeros(self.capacity, np.int32)
+        slots, length, head = self._slot_order()
+        prio = np.zeros(self.capacity)
         prio[slots] = self.device_priorities().cpu().numpy()
-        length[slots] = lengths
-        return sample_host(prio, length, head.value, batch_size, seed=seed, step=step, symmetries=symmetries,
-                           beta=beta)
+        return sample_host(prio, length, head, batch_size, seed=seed, step=step, symmetries=symmetries, beta=beta)
 
     # ---- position-level priorities (opt-in on top of the device ledger) ----
     def enable_position_priorities(self, td_steps, discount, alpha=1.0, floor=None, init="td"):
@@ -722,43 +738,19 @@ class DeviceReplay:
         one uniform picks both.  ``sample``'s tensors; ``items[:, 1]`` is the
         drawn position and ``weight`` the importance weights over positions,
         (n_positions w / total) ** -beta over the batch's largest."""
-        B = int(batch_size)
-        s = self._sample_out(B)
-        check(lib.mzgo_replay_sample_positions(self._h, B, int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF,
-                                               int(bool(symmetries)), float(beta), ptr(s["items"]), ptr(s["index"]),
-                                               ptr(s["gen"]), ptr(s["weight"]), stream_of(self.device)))
-        return s
+        return self._sample(True, batch_size, _draw_args(seed, step, symmetries, beta))
 
     def sample_positions_batch(self, batch_size, unroll_steps, discount, *, seed, step, symmetries=False, beta=0.0):
         """``sample_batch`` with the position sampler's draw
         (mzgo_replay_sample_positions_batch)."""
-        B, K = int(batch_size), int(unroll_steps)
-        out = self._batch_out(B, K)
-        out.update(self._sample_out(B))
-        check(lib.mzgo_replay_sample_positions_batch(self._h, B, K, float(discount), int(seed) & (2 ** 64 - 1),
-                                                     int(step) & 0xFFFFFFFF, int(bool(symmetries)), float(beta),
-                                                     ptr(out["items"]), ptr(out["index"]), ptr(out["gen"]),
-                                                     ptr(out["weight"]), ptr(out["obs0"]), ptr(out["boot_obs"]),
-                                                     ptr(out["acts"]), ptr(out["t_rew"]), ptr(out["t_pol"]),
-                                                     ptr(out["val"]), ptr(out["factor"]), ptr(out["has_boot"]),
-                                                     stream_of(self.device)))
-        return out
+        return self._sample_batch(True, batch_size, unroll_steps, discount, _draw_args(seed, step, symmetries, beta))
 
     def sample_positions_batch_values(self, batch_size, unroll_steps, td_steps, discount, *, seed, step,
                                       symmetries=False, beta=0.0):
         """``sample_batch_values`` with the position sampler's draw
         (mzgo_replay_sample_positions_batch_values)."""
-        B, K = int(batch_size), int(unroll_steps)
-        out = self._values_out(B, K)
-        out.update(self._sample_out(B))
-        check(lib.mzgo_replay_sample_positions_batch_values(self._h, B, K, int(td_steps), float(discount),
-                                                            int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF,
-                                                            int(bool(symmetries)), float(beta), ptr(out["items"]),
-                                                            ptr(out["index"]), ptr(out["gen"]), ptr(out["weight"]),
-                                                            ptr(out["obs0"]), ptr(out["acts"]), ptr(out["t_rew"]),
-                                                            ptr(out["t_pol"]), ptr(out["t_val"]),
-                                                            stream_of(self.device)))
-        return out
+        return self._sample_batch_values(True, batch_size, unroll_steps, td_steps, discount,
+                                         _draw_args(seed, step, symmetries, beta))
 
     def update_position_priorities(self, sample, value, t_val):
         """New position weights for a sampled batch's windows
@@ -800,15 +792,11 @@ class DeviceReplay:
         """The position sampler's host twin on this store's present position
         weights (copied back) and lengths: numpy ``items``, ``index``,
         ``weight``."""
-        size, head = ctypes.c_int32(), ctypes.c_int32()
-        check(lib.mzgo_replay_info(self._h, ctypes.byref(size), ctypes.byref(head), None, None))
-        lengths, _ = self._info()
-        slots = (head.value + np.arange(size.value)) % self.capacity
-        pprio, length = np.zeros((self.capacity, self.max_moves)), np.zeros(self.capacity, np.int32)
+        slots, length, head = self._slot_order()
+        pprio = np.zeros((self.capacity, self.max_moves))
         pprio[slots] = self.position_priorities().cpu().numpy()
-        length[slots] = lengths
-        return sample_positions_host(pprio, length, head.value, batch_size, seed=seed, step=step,
-                                     symmetries=symmetries, beta=beta)
+        return sample_positions_host(pprio, length, head, batch_size, seed=seed, step=step, symmetries=symmetries,
+                                     beta=beta)
 
     # ---- reanalysis in place ----
     def reanalyse(self, reanalyser, games=None):
@@ -855,11 +843,7 @@ class DeviceReplay:
         """``window_items_host`` on this store's lengths (the host mirror's,
         in slot order): numpy i32 [n,2] rows (slot, t).  ``items``: [B,3]
         (slot, start, symmetry), a tensor or an array."""
-        size, head = ctypes.c_int32(), ctypes.c_int32()
-        check(lib.mzgo_replay_info(self._h, ctypes.byref(size), ctypes.byref(head), None, None))
-        lengths, _ = self._info()
-        length = np.zeros(self.capacity, np.int32)
-        length[(head.value + np.arange(size.value)) % self.capacity] = lengths
+        length = self._slot_order()[1]
         if isinstance(items, dict):
             items = items["items"]
         if isinstance(items, torch.Tensor):

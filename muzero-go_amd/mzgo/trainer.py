@@ -901,23 +901,22 @@ class MuZeroTrainer:
         from .replay import finish_values
         c, N, td = self.config, self.net.board_size, self.td_steps
         draw = dict(seed=self.sample_seed, step=self.sample_step, symmetries=c.symmetries, beta=c.importance_beta)
-        sample, sample_batch, sample_batch_values = replay.sample, replay.sample_batch, replay.sample_batch_values
+        sampler = "sample"                  # the store's three sample calls: <sampler>, _batch, _batch_values
         if c.position_priorities:
             # (a no-op after the first step; the store refuses other parameters than it was enabled with)
             replay.enable_position_priorities(td or c.unroll_steps, c.discount, alpha=c.priority_alpha,
                                               floor=c.priority_floor or None)
-            sample, sample_batch, sample_batch_values = (replay.sample_positions, replay.sample_positions_batch,
-                                                         replay.sample_positions_batch_values)
+            sampler = "sample_positions"
         if c.reanalyse_sample and self.sample_step % c.reanalyse_every == 0:
-            s = sample(batch_size, **draw)
+            s = getattr(replay, sampler)(batch_size, **draw)
             self.reanalyser.refresh()
             self.last_searched_device = replay.reanalyse_sample(self.reanalyser, s, c.unroll_steps, td_steps=td)
             s.update(replay.batch_from(s, c.unroll_steps, c.discount) if td is None
                      else replay.batch_values_from(s, c.unroll_steps, td, c.discount))
         elif td is None:
-            s = sample_batch(batch_size, c.unroll_steps, c.discount, **draw)
+            s = getattr(replay, sampler + "_batch")(batch_size, c.unroll_steps, c.discount, **draw)
         else:
-            s = sample_batch_values(batch_size, c.unroll_steps, td, c.discount, **draw)
+            s = getattr(replay, sampler + "_batch_values")(batch_size, c.unroll_steps, td, c.discount, **draw)
         self.sample_step += 1
         if td is None:
             with torch.no_grad():

@@ -112,6 +112,35 @@ def test_kernel_equals_the_twin_at_4097_slots():
     _assert_sampler_equals_twin(4097, False, ((128, True, 0.5),))
 
 
+def test_one_move_games_draw_as_the_game_sampler():
+    """Both samplers' kernels descend one tree: where every game has one move
+    and pprio[game][0] = prio[game], ``sample_positions`` returns ``sample``'s
+    items, index, gen and weight byte for byte (test_replay_positions has the
+    reasons and the host twins' side).  65 slots: two level-1 groups, the second
+    of one slot; the ring wrapped, six games without a move; all the others drawn."""
+    import mzgo
+    cap, head = 65, 20
+    rp = mzgo.DeviceReplay(N, cap, 2, "cuda")
+    rp.enable_position_priorities(1, DISCOUNT, init="uniform")
+    for k in range(cap + head):
+        rp.add(_game(int(k % 11 != 3), k))
+    r = np.random.default_rng(65)
+    prio = 10.0 ** r.uniform(-34.0, 1.0, cap)
+    rp.set_device_priorities(prio)
+    rp.set_position_priorities(np.stack([prio, 10.0 ** r.uniform(-34.0, 1.0, cap)], axis=1))   # (column 1: never read)
+    B = int((np.asarray(rp.lengths) > 0).sum())
+    assert B == cap - 6
+    draw = dict(seed=21, step=7, symmetries=True, beta=0.5)
+    want, got = rp.sample(B, **draw), rp.sample_positions(B, **draw)
+    for k in ("items", "index", "gen", "weight"):
+        assert _np(got[k]).tobytes() == _np(want[k]).tobytes(), k
+    items = _np(want["items"])
+    np.testing.assert_array_equal(items, rp.sample_host(B, **draw)["items"])
+    assert len(set(items[:, 0].tolist())) == B and (items[:, 1] == 0).all() and len(set(items[:, 2].tolist())) > 1
+    assert set(_np(want["gen"]).tolist()) == {1, 2} and 0 < _np(want["weight"]).min() < 1.0
+    rp.close()
+
+
 # ---------------------------------------------------------------------------
 # new games
 # ---------------------------------------------------------------------------

@@ -145,6 +145,33 @@ def test_twin_equals_the_restatement(cap):
     assert sorted(slots.tolist()) == np.flatnonzero(length > 0).tolist()       # B = n_valid: every game once
 
 
+@pytest.mark.parametrize("cap", CAPACITIES + [5000])
+def test_one_move_games_draw_as_the_game_sampler(cap):
+    """Both samplers descend one tree.  Where every game has one move and
+    pprio[slot][0] = prio[slot], the position twin returns the game twin's
+    items, index and weight byte for byte: a one-position game's weight is that
+    position's (adding zeros is exact), n_pos = n_valid, the start drawn below 1
+    is 0 and the two levels inside the game pick entry 0.  Rows of 1 and of 3
+    weights, junk past the one move; B = 1, half and all of the games."""
+    from mzgo.replay import sample_host
+    r = np.random.default_rng(900 + cap)
+    length = (r.random(cap) < 0.85).astype(np.int32)       # some slots empty
+    length[r.integers(cap)] = 1
+    prio = 10.0 ** r.uniform(-34.0, 1.0, cap)
+    n_valid = int(length.sum())
+    for Mx in (1, 3):
+        pprio = 10.0 ** r.uniform(-34.0, 1.0, (cap, Mx))   # (columns past the length: never read)
+        pprio[:, 0] = prio
+        for B in sorted({1, max(1, n_valid // 2), n_valid}):
+            for beta in (0.0, 0.5):
+                draw_ = dict(seed=31, step=cap + B, symmetries=True, beta=beta)
+                want = sample_host(prio, length, cap // 3, B, **draw_)
+                got = _twin(pprio, length, cap // 3, B, **draw_)
+                assert (want["items"][:, 1] == 0).all() and len(set(want["items"][:, 0].tolist())) == B
+                for k in ("items", "index", "weight"):
+                    assert got[k].dtype == want[k].dtype and got[k].tobytes() == want[k].tobytes(), (k, Mx, B, beta)
+
+
 def test_targets_next_to_a_boundary_stay_on_positive_positions():
     """Weights that make every rounding case: 1e-300 next to 1, a zero, then
     1e300 across the chunk edge at 64 (and again at 128, and in a second game

@@ -1,7 +1,8 @@
 // replay_twins_check.cpp -- the replay store's two search-value host twins,
 // mzgo_replay_value_targets_host and mzgo_replay_window_items_values_host, and
 // the position ledger's two, mzgo_replay_sample_positions_host and
-// mzgo_replay_position_priorities_host
+// mzgo_replay_position_priorities_host, and the game sampler's,
+// mzgo_replay_sample_host
 // (csrc/mzgo_replay.hip), called from a stand-alone host program so that the C
 // wrappers themselves -- their vectors, the index clamp, the writes into the
 // caller's buffers -- can run under AddressSanitizer and UBSan on a machine
@@ -202,6 +203,37 @@ int main() {
       CHECK(mzgo_replay_sample_positions_host(w.data(), length.data(), cap, M, 0, valid + 1, 5, 0, 0, 0.0, nullptr,
                                               nullptr, nullptr) == MZGO_EINVAL);
     }
+  // ---- mzgo_replay_sample_host (the same capacities; the tree is the position twin's) ----
+  long game_draws = 0;
+  for (int cap : {1, 63, 64, 65, 130, 4097}) {
+    std::vector<double> w(cap);                            // exactly [cap]
+    std::vector<int32_t> length(cap);
+    int valid = 0;
+    for (int i = 0; i < cap; ++i) {
+      length[i] = lens[rand() % 10];
+      valid += length[i] > 0;
+      w[i] = (rand() % 1000 + 1) * 1e-3;
+    }
+    if (!valid) { length[0] = 1; valid = 1; }
+    for (int B : {1, valid}) {
+      std::vector<int32_t> items((size_t)B * 3, -1), index(B, -1);
+      std::vector<float> weight(B, -1.f);
+      CHECK(mzgo_replay_sample_host(w.data(), length.data(), cap, cap / 3, B, 5, (uint32_t)game_draws, 1, 0.5,
+                                    items.data(), index.data(), weight.data()) == MZGO_OK);
+      std::set<int> seen;
+      for (int b = 0; b < B; ++b) {
+        const int s = items[3 * b], t = items[3 * b + 1];
+        CHECK(s >= 0 && s < cap && length[s] > 0 && t >= 0 && t < length[s]);
+        CHECK(items[3 * b + 2] >= 0 && items[3 * b + 2] < 8 && index[b] == (s - cap / 3 + cap) % cap);
+        CHECK(weight[b] > 0.f && weight[b] <= 1.f && seen.insert(s).second);
+        ++game_draws;
+      }
+    }
+    std::vector<int32_t> items((size_t)(valid + 1) * 3), index(valid + 1);
+    CHECK(mzgo_replay_sample_host(w.data(), length.data(), cap, 0, valid + 1, 5, 0, 0, 0.0, items.data(), index.data(),
+                                  nullptr) == MZGO_EINVAL);
+    CHECK(g_err.find("exceeds") != std::string::npos);
+  }
   for (int L : {0, 1, 2, 54, 4096}) {
     std::vector<double> r(L + 1), nu(L), out(L, -1.0);     // exactly L weights
     for (auto& x : r) x = unit();
@@ -226,6 +258,7 @@ int main() {
     CHECK(mzgo_replay_position_priorities_host(r, nu, 1, 1, 0.99, 0.0, 0.0, out) == MZGO_EINVAL);
     CHECK(mzgo_replay_position_priorities_host(r, nu, 1, 1, 0.99, 1.0, -1.0, out) == MZGO_EINVAL);
   }
-  printf("ok: %ld targets, %ld pairs, %ld draws, %ld weights\n", targets, pairs, draws, weights);
+  printf("ok: %ld targets, %ld pairs, %ld draws, %ld game draws, %ld weights\n", targets, pairs, draws, game_draws,
+         weights);
   return 0;
 }
