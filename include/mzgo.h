@@ -152,6 +152,15 @@ int mzgo_weights_copy(mzgo_engine* dst, const mzgo_engine* src, void* stream);
  * data may be NULL to query; cap in floats.  A test and diagnostic hook: the
  * layout is mzgo_weights.hpp's and depends on (board_size, latent_dim) only. */
 int mzgo_weights_export(mzgo_engine* eng, float* data_host, int64_t cap, int64_t* n_floats, void* stream);
+/* The blob's host twin: the packed blob of a (board_size, latent_dim) engine
+ * from the 22 state_dict tensors in host memory (mzgo_set_weights_device's
+ * table and its checks), by a serial walk of the rules the pack kernel runs --
+ * the same floats bit for bit, without an engine, a device or a HIP call.
+ * *n_floats = the blob's length; blob may be NULL to query; cap in floats.
+ * MZGO_EINVAL for a (board_size, latent_dim) no kernels are built for. */
+int mzgo_weights_pack_host(int board_size, int latent_dim, const char* const* keys, const float* const* data_host,
+                           const int64_t* const* shapes, const int* ndims, int n, float* blob, int64_t cap,
+                           int64_t* n_floats);
 
 /* MuZeroNet protocol, batch B (any B >= 1):
  *   obs f32 [B][6][N][N] -> latent f32 [B][C][N][N], value f32 [B][1], logits f32 [B][N*N+1]  */

@@ -78,117 +78,6 @@ std::vector<Spec> specs(int C, int A) {
   return out;
 }
 
-// conv weight W[cout][cin][3][3] -> MFMA A-fragment order of mzgo_conv.hpp:
-// packed[((s * NCOG + cog) * 64 + lane) * MGP + mi] with k-step s = tap*CQ + c4,
-// cout = (cog*MG + mi)*16 + (lane & 15), cin = c4*4 + (lane >> 4).
-// With cog_major the layout is packed[(frag * 64 + lane) * MGP + mi] with
-// frag = ((cog * ksplit + half) * 9 + tap) * (CQ / ksplit) + c4 % (CQ / ksplit):
-// one contiguous stream per (cout group, k-half) for the per-wave DMA rings
-// of conv3x3_ring (ksplit = Geo::KSPLIT); otherwise frag = s * NCOG + cog
-// (conv3x3_direct).
-std::vector<float> pack_conv(const float* W, int COUT, int CIN, bool cog_major, int ksplit = 1) {
-  const int CINP = (CIN + 3) / 4 * 4, CQ = CINP / 4, KS = 9 * CQ, CQH = CQ / ksplit;
-  const int MT = COUT / 16;
-  const int MG = (MT % 3 == 0) ? 3 : ((MT % 4 == 0 && MT >= 8) ? 4 : 2);
-  const int MGP = MG == 3 ? 4 : MG, NCOG = MT / MG;
-  std::vector<float> out((size_t)KS * NCOG * 64 * MGP, 0.f);
-  for (int s = 0; s < KS; ++s) {
-    const int t = s / CQ, c4 = s % CQ, ky = t / 3, kx = t % 3;
-    for (int cog = 0; cog < NCOG; ++cog)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int mi = 0; mi < MG; ++mi) {
-          const int cout = (cog * MG + mi) * 16 + (lane & 15);
-          const int cin = c4 * 4 + (lane >> 4);
-          const float v = cin < CIN ? W[(((size_t)cout * CIN + cin) * 3 + ky) * 3 + kx] : 0.f;
-          // cog-major streams are further ordered [half][tap][c4 within the half]
-          const int half = c4 / CQH, c4h = c4 % CQH;
-          const size_t frag = cog_major ? (((size_t)cog * ksplit + half) * 9 + t) * CQH + c4h
-                                        : (size_t)s * NCOG + cog;
-          out[(frag * 64 + lane) * MGP + mi] = v;
-        }
-  }
-  return out;
-}
-
-// conv weight W[cout][cin][3][3] -> Winograd U for mzgo_wino.hpp (9x9):
-// U_xi[cout][cin] = (G2 g G3^T)[i][j], g = W[cout][cin], xi = i*5 + j, with
-// G2 of F(2,3) (points 0, 1, -1, inf) on kernel rows and G3 of F(3,3)
-// (points 0, 1, -1, -2, inf) on kernel columns, computed in double and
-// rounded once.  Packed as packed[(((m*2 + h)*L + pos)*64 + lane)*4 + e]
-// = U_xi[16m + (lane & 15)][hh*CIN/2 + 4*(4*s4 + e) + (lane >> 4)] for
-// xi = h*10 + xl, k-position k = hh*S4 + s4 (S4 = CIN/32), and
-// pos = ((xl/XG)*KP + k)*XG + xl%XG (kWinoXG, KP = CIN/16): one contiguous
-// float4 stream per (cout tile m, xi half h) wave, in the order wino_conv
-// consumes it.
-// khalf (one-strip boards, wino_conv's KHALF loop): consumption order is
-// K half, xi group, k-position within the half, xi within the group -- the
-// GEMM runs the first half of CIN for every xi before the second, so the
-// rebuilt input's second channel slab is transformed under the first half's
-// MFMAs (wino_conv_rebuilt)
-std::vector<float> pack_wino(const float* W, int COUT, int CIN, bool khalf) {
-  static const double G2[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  static const double G3[5][3] = {{0.5, 0, 0},
-                                  {1.0 / 6, 1.0 / 6, 1.0 / 6},
-                                  {0.5, -0.5, 0.5},
-                                  {1.0 / 6, -1.0 / 3, 2.0 / 3},
-                                  {0, 0, 1}};
-  const int MT = COUT / 16, CH = CIN / 2, S4 = CH / 16, KP = CIN / 16, L = 10 * KP;
-  std::vector<float> out((size_t)MT * 2 * L * 64 * 4, 0.f);
-  for (int m = 0; m < MT; ++m)
-    for (int h = 0; h < 2; ++h)
-      for (int xl = 0; xl < 10; ++xl)
-        for (int k = 0; k < KP; ++k)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int e = 0; e < 4; ++e) {
-              const int xi = h * 10 + xl, i = xi / 5, j = xi % 5;
-              const int hh = k / S4, s4 = k % S4;
-              const int co = 16 * m + (lane & 15), ci = hh * CH + 4 * (4 * s4 + e) + (lane >> 4);
-              const float* g = W + ((size_t)co * CIN + ci) * 9;
-              double u = 0.0;
-              for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) u += G2[i][a] * (double)g[a * 3 + b] * G3[j][b];
-              const int KH = KP / 2, kh = k / KH, NG = 10 / kWinoXG;
-              const int pos = khalf ? (((kh * NG + xl / kWinoXG) * KH + k % KH) * kWinoXG + xl % kWinoXG)
-                                    : (((xl / kWinoXG) * KP + k) * kWinoXG + xl % kWinoXG);   // consumption order
-              out[((((size_t)m * 2 + h) * L + pos) * 64 + lane) * 4 + e] = (float)u;
-            }
-  return out;
-}
-
-// The action-tap table of the factored expansion (mzgo_expand.hpp):
-// E[a][r][co] = sum over the taps (ky, kx) on the board for a cell of region
-// r = ry*3 + rx (ry, rx in {first, interior, last} row / column) of
-// sum_ci W[co][ci][ky][kx] * emb[a][ci], so that conv3x3(x + emb[a]) =
-// conv3x3(x) + E[a][region] under zero padding.  f64 sums, rounded once.
-std::vector<float> action_taps(const float* W, const float* emb, int C, int A) {
-  std::vector<float> out((size_t)A * 9 * C);
-  std::vector<double> u((size_t)9 * C);
-  for (int a = 0; a < A; ++a) {
-    const float* e = emb + (size_t)a * C;
-    for (int co = 0; co < C; ++co)
-      for (int t = 0; t < 9; ++t) {
-        double s = 0.0;
-        for (int ci = 0; ci < C; ++ci) s += (double)W[((size_t)co * C + ci) * 9 + t] * (double)e[ci];
-        u[(size_t)t * C + co] = s;
-      }
-    for (int r = 0; r < 9; ++r) {
-      const int ry = r / 3, rx = r % 3;
-      for (int co = 0; co < C; ++co) {
-        double s = 0.0;
-        for (int ky = 0; ky < 3; ++ky) {
-          if ((ry == 0 && ky == 0) || (ry == 2 && ky == 2)) continue;   // row y-1 / y+1 off the board
-          for (int kx = 0; kx < 3; ++kx) {
-            if ((rx == 0 && kx == 0) || (rx == 2 && kx == 2)) continue;
-            s += u[(size_t)(ky * 3 + kx) * C + co];
-          }
-        }
-        out[((size_t)a * 9 + r) * C + co] = (float)s;
-      }
-    }
-  }
-  return out;
-}
-
 }  // namespace
 
 // CUs of the current device (one self-play workgroup fills a CU's LDS)
@@ -294,37 +183,15 @@ struct mzgo_engine {
     for (const Spec& s : spec)
       if (!sd.count(s.key)) return fail(MZGO_ENOWEIGHTS, "missing weight '%s'", s.key.c_str());
     if (tower) {
-      HIPCHK(tower->upload(sd, &action_taps));
+      HIPCHK(tower->upload(sd));
       dirty = false;
       return MZGO_OK;
     }
     if (int rc = ensure_blob()) return rc;
-    // the parts in blob order (WeightPart, mzgo_weights.hpp)
-    std::vector<std::vector<float>> parts;
-    parts.push_back(pack_conv(sd["representation.conv1.weight"].data(), 64, 6, false));
-    parts.push_back(sd["representation.conv1.bias"]);
-    auto latent = [&](const char* key, int cout, int cin) {
-      return wl.wino ? pack_wino(sd[key].data(), cout, cin, true)
-                     : pack_conv(sd[key].data(), cout, cin, true, wl.ksplit);
-    };
-    parts.push_back(latent("representation.conv2.weight", 64, 64));
-    parts.push_back(sd["representation.conv2.bias"]);
-    parts.push_back(latent("representation.conv3.weight", C, 64));
-    parts.push_back(sd["representation.conv3.bias"]);
-    parts.push_back(latent("dynamics.conv.weight", C, C));
-    parts.push_back(sd["dynamics.conv.bias"]);
-    parts.push_back(sd["dynamics.action_embedding.weight"]);
-    std::vector<float> hw;
-    for (WeightKey k : kHeadKeys) hw.insert(hw.end(), sd[spec[k].key].begin(), sd[spec[k].key].end());
-    parts.push_back(hw);
-    parts.push_back(action_taps(sd["dynamics.conv.weight"].data(), sd["dynamics.action_embedding.weight"].data(), C, A));
-    for (WeightKey k : kScalarKeys) parts.push_back(sd[spec[k].key]);
-    if ((int)parts.size() != WP_COUNT) return fail(MZGO_EASSERT, "weight blob: %zu parts, layout has %d", parts.size(), (int)WP_COUNT);
-    for (int i = 0; i < WP_COUNT; ++i)
-      if (parts[i].size() != wl.size[i])
-        return fail(MZGO_EASSERT, "weight blob: part %d has %zu floats, layout says %zu", i, parts[i].size(), wl.size[i]);
+    const float* src[WK_COUNT];
+    for (int k = 0; k < WK_COUNT; ++k) src[k] = sd[spec[k].key].data();
     std::vector<float> blob(wl.total, 0.f);
-    for (int i = 0; i < WP_COUNT; ++i) std::memcpy(blob.data() + wl.off[i], parts[i].data(), parts[i].size() * 4);
+    pack_weights_host(wl, src, blob.data());
     HIPCHK(hipMemcpy(d_w, blob.data(), wl.total * 4, hipMemcpyHostToDevice));
     dev_weights = false;
     dirty = false;
@@ -646,29 +513,11 @@ int mzgo_weights_ready(const mzgo_engine* e) {
 
 int mzgo_set_weights_device(mzgo_engine* e, const char* const* keys, const float* const* data_dev,
                             const int64_t* const* shapes, const int* ndims, int n, void* stream) {
-  if (!e || !keys || !data_dev || !shapes || !ndims) return fail(MZGO_EINVAL, "mzgo_set_weights_device: null argument");
+  if (!e) return fail(MZGO_EINVAL, "mzgo_set_weights_device: null argument");
   if (e->C == 0) return fail(MZGO_EINVAL, "mzgo_set_weights_device: board-only engine (latent_dim 0) has no network");
   if (e->tower) return fail(MZGO_EINVAL, "mzgo_set_weights_device: tower engines (tower = 1) are not supported");
-  if ((int)e->spec.size() != WK_COUNT) return fail(MZGO_EASSERT, "mzgo_set_weights_device: %zu specs", e->spec.size());
-  const float* src[WK_COUNT] = {};
-  for (int i = 0; i < n; ++i) {
-    if (!keys[i] || !data_dev[i] || (!shapes[i] && ndims[i] > 0))
-      return fail(MZGO_EINVAL, "mzgo_set_weights_device: null entry %d ('%s')", i, keys[i] ? keys[i] : "?");
-    int k = 0;
-    while (k < WK_COUNT && e->spec[k].key != keys[i]) ++k;
-    if (k == WK_COUNT) return fail(MZGO_EINVAL, "unexpected key '%s' in state_dict", keys[i]);
-    if (src[k]) return fail(MZGO_EINVAL, "duplicate key '%s'", keys[i]);
-    const Spec& s = e->spec[k];
-    if ((int)s.shape.size() != ndims[i])
-      return fail(MZGO_EINVAL, "'%s': expected %zu dims, got %d", keys[i], s.shape.size(), ndims[i]);
-    for (int d = 0; d < ndims[i]; ++d)
-      if (shapes[i][d] != s.shape[d])
-        return fail(MZGO_EINVAL, "'%s': dim %d is %lld, expected %lld", keys[i], d, (long long)shapes[i][d],
-                    (long long)s.shape[d]);
-    src[k] = data_dev[i];
-  }
-  for (int k = 0; k < WK_COUNT; ++k)
-    if (!src[k]) return fail(MZGO_EINVAL, "missing weight '%s'", e->spec[k].key.c_str());
+  const float* src[WK_COUNT];
+  if (int rc = weight_table("mzgo_set_weights_device", keys, data_dev, shapes, ndims, n, e->C, e->A, src)) return rc;
   if (int rc = e->ensure_blob()) return rc;
   HIPCHK(pack_weights_device(e->wl, src, e->d_w, (hipStream_t)stream));
   e->sd.clear();                                      // the host copies are stale

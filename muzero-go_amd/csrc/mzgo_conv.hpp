@@ -6,7 +6,7 @@
 // accumulator's row index:
 //     out[cout][cell] = sum_k W[cout][k] * im2col[k][cell],  k = tap*CINP + cin
 // A operand (16 couts x 4 k)  : pre-packed weights streamed from L2
-//                               (layout written by pack_conv_weights, host side)
+//                               (layout: conv_frag, mzgo_weights.hpp)
 // B operand (4 k x 16 cells)  : the input board staged in LDS as [cin][CPAD],
 //                               gathered per lane with the tap's cell offset
 // Each wave owns jobs of MG cout tiles x NG cell tiles (3x3 tiles of 16x16 at
@@ -241,7 +241,7 @@ __device__ __forceinline__ void conv3x3_direct(const float* __restrict__ lds_in,
 // after its own vmcnt wait).  Both MFMA operands come from LDS.  One wave
 // serves one cout group and JW cell groups, so each A fragment feeds
 // MG x NG x JW MFMAs.  Weights are packed cog-major ([cog][k-step][lane][MGP],
-// pack_conv(..., cog_major=true)) so a wave's stream is contiguous.
+// conv_frag(..., cog_major = 1)) so a wave's stream is contiguous.
 //
 //   wave chunk c (KC k-steps, SLOT bytes) lands in slot c % NSLOT.
 //   iteration c: issue chunk c+NSLOT-1 (into the slot read in iteration c-1)

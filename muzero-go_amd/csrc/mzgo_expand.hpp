@@ -8,8 +8,8 @@
 //     E[a][r][co] = sum over the taps (ky, kx) that stay on the board for a
 //                   cell of region r of  sum_ci W[co][ci][ky][kx] * emb[a][ci]
 // where r = (row class)*3 + (column class), classes {first, interior, last}.
-// E is a per-network table [A][9][C] built once on the host in f64
-// (mzgo_capi.hip: action_taps).
+// E is a per-network table [A][9][C] built once per weight load in f64
+// (mzgo_weights.hpp: taps_column).
 //
 // A search therefore runs the full 3x3 conv only for nodes that become
 // parents (3-11 per 200-400-simulation search in the reference's trees; the

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "mzgo_tower_dispatch.hpp"
+#include "mzgo_weights.hpp"
 
 namespace mzgo {
 
@@ -324,10 +325,10 @@ struct TowerHost {
 
   // pack + upload (host f32 state_dict -> device).  The dynamics' first conv
   // adds the action embedding through the region table of mzgo_expand.hpp
-  // (conv(x + emb[a]) = conv(x) + E[a][region] under zero padding), built from
-  // the bf16-rounded weights the MFMA uses: the GEMM never sees emb.
-  hipError_t upload(std::map<std::string, std::vector<float>>& sd,
-                    std::vector<float> (*taps)(const float*, const float*, int, int)) {
+  // (conv(x + emb[a]) = conv(x) + E[a][region] under zero padding; action_taps,
+  // mzgo_weights.hpp), built from the bf16-rounded weights the MFMA uses: the
+  // GEMM never sees emb.
+  hipError_t upload(std::map<std::string, std::vector<float>>& sd) {
     std::vector<uint16_t> wb;
     std::vector<size_t> woff;
     std::vector<std::string> order;
@@ -358,7 +359,9 @@ struct TowerHost {
     for (const std::string& k : order) boff.push_back(addf(sd[k + ".bias"]));
     std::vector<float> wr = sd["dynamics.conv_in.weight"];
     for (float& x : wr) x = bf16_round(x);
-    const size_t eoff = addf(taps(wr.data(), sd["dynamics.action_embedding.weight"].data(), C, A));
+    std::vector<float> et((size_t)A * 9 * C);
+    action_taps(wr.data(), sd["dynamics.action_embedding.weight"].data(), C, A, et.data());
+    const size_t eoff = addf(et);
     std::vector<float> hw;
     for (const char* k : {"dynamics.reward_conv.weight", "prediction.value_conv.weight",
                           "prediction.policy_conv.weight"})

@@ -9,7 +9,7 @@
 // of 96 x 96 x 16 -- 2880 MFMAs per conv instead of 7776 for the direct
 // implicit GEMM over 96 padded cells.  The device transforms are integer
 // (BT, AT below); the fractions of G live in U, packed by the host
-// (mzgo_capi.hip: pack_wino).  fp32 error is on par with the direct conv
+// (mzgo_weights.hpp: wino_value).  fp32 error is on par with the direct conv
 // (the per-output sums run over 96 inputs instead of 864).
 //
 // Work split: 12 waves (3 per SIMD); wave w owns cout tile m = w / 2 and xi
@@ -29,7 +29,7 @@
 
 
 namespace mzgo {
-constexpr int kWinoXG = 2;   // xi per accumulation group (A stream order, pack_wino)
+constexpr int kWinoXG = 2;   // xi per accumulation group (A stream order, wino_frag)
 }
 
 namespace mzgo {
@@ -414,8 +414,8 @@ __device__ __forceinline__ constexpr float wino_at3(int ox, int j) {
 // alias V); hp: head partials [COUT/16][3][CS]; outs: output staging
 // [COUT][CS] (LDS; red, hp and outs disjoint).  hp is complete on return;
 // the stores to ``out`` are issued but not synchronised.
-// upk: U packed [m][h][pos][lane][4], pos = ((xl/XG)*KP + k)*XG + xl%XG for
-// xi = h*10 + xl and k-position k (pack_wino).  out: [COUT][out_stride]
+// upk: U packed [m][h][pos][lane][4], pos the consumption order of
+// xi = h*10 + xl and k-position k (wino_frag, mzgo_weights.hpp).  out: [COUT][out_stride]
 // global; cells >= out_cells are not stored (pooled rows, stride == out_cells
 // == CS, are stored whole with their zero pad cells).
 //
@@ -425,7 +425,7 @@ __device__ __forceinline__ constexpr float wino_at3(int ox, int j) {
 // output is computed by the same operations as in the whole conv.
 //
 // One-strip boards (KHALF) run the K dimension in two halves, every xi's
-// first half before any second half (pack_wino's khalf order; each xi's
+// first half before any second half (wino_frag's order; each xi's
 // chain still adds k = 0 .. KP-1 in order, so the sums are the same bits):
 // hook(s) runs between the MFMA groups of step s of the first half, and a
 // hook that DEFERS the second half's V (wino_conv_rebuilt: that half is
@@ -469,7 +469,7 @@ __device__ __forceinline__ void wino_conv(const float* V, float* red, float* hp,
   for (int r = 0; r < 4; ++r) bb[r] = active ? bias[m * 16 + kq * 4 + r] : 0.f;
 
   const unsigned long long t_loop = st ? __builtin_amdgcn_s_memtime() : 0ull;
-  constexpr bool KHALF = true;                // (every Winograd board: pack_wino's khalf order)
+  constexpr bool KHALF = true;                // (every Winograd board: wino_frag's order)
   static_assert(!Hook::DEFERS || KHALF, "a deferred second half needs the split K loop");
   if (KHALF && active) {
     // (KHALF) all xi's accumulators live across the two K halves
@@ -556,7 +556,7 @@ __device__ __forceinline__ void wino_conv(const float* V, float* red, float* hp,
   } else if (!KHALF && active) {
     // this wave: xi in [h*XH, h*XH + XH), all CIN (KP float4 k-positions per xi).
     // A stream: positions pos = ((g*KP + k)*XG + q) for local xi g*XG + q, in
-    // consumption order (pack_wino), PF float4 registers ahead
+    // consumption order (no packer), PF float4 registers ahead
     const f32x4* ap = reinterpret_cast<const f32x4*>(upk) + (size_t)(m * 2 + h) * L * 64 + lane;
     const f32x4* bp = reinterpret_cast<const f32x4*>(V) + (size_t)h * XH * KP * 64 + lane;
     auto bidx = [&](int xl, int k) { return (xl * KP + k) * 64; };

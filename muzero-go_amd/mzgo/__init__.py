@@ -39,11 +39,13 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
 * ``DeviceAdam`` -- the optimizer tail (gradient-norm clip, Adam / AdamW, StepLR) of any float32
   module in one stream-ordered HIP call that refuses and counts a non-finite gradient
   (``TrainConfig.device_optimizer``); ``adam_step_host`` is its host twin on numpy arrays
+* ``pack_weights_host`` -- an engine's packed weight blob from a state_dict on the host: the rule
+  both weight paths (``Engine.set_state_dict``, ``Engine.set_parameters_device``) run
 * ``mzgo.play`` -- play.py's interactive human-vs-agent loop (``python -m mzgo.play weights.pth``)
 """
 from ._lib import MzgoError
 from .arena import SelfPlayEvaluator
-from .engine import Engine, EngineConfig, playout_budget_host
+from .engine import Engine, EngineConfig, pack_weights_host, playout_budget_host
 from .env import GoEnv
 from .loss import unroll_loss, unroll_loss_host
 from .net import MuZeroNet
@@ -65,4 +67,4 @@ __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "
            "unroll_loss_host", "unroll", "unroll_heads_host", "bf16_round_host", "window_items_host", "value_targets_host",
            "sample_positions_host", "position_priorities_host", "DeviceAdam", "adam_step_host", "optim_chunk",
            "playout_budget_host", "OwnershipHead", "ownership_loss", "ownership_loss_host", "ownership_host",
-           "ownership_targets_host"]
+           "ownership_targets_host", "pack_weights_host"]

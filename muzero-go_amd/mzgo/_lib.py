@@ -80,6 +80,7 @@ SIGNATURES = {
     "mzgo_set_weights_device": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "mzgo_weights_copy": (_I, [_P, _P, _P]),
     "mzgo_weights_export": (_I, [_P, _P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), _P]),
+    "mzgo_weights_pack_host": (_I, [_I, _I, _P, _P, _P, _P, _I, _P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     "mzgo_initial_inference": (_I, [_P, _P, _I, _P, _P, _P, _P]),
     "mzgo_recurrent_inference": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "mzgo_check_inference_errors": (_I, [_P, _P]),

@@ -76,6 +76,50 @@ def playout_budget_host(seed, key_gid, move, num_simulations, fast_simulations, 
     return out.value
 
 
+def _weight_table(items, A):
+    """(keys, data, shapes, ndims, n, keep) of host float32 tensors for a C
+    call that takes mzgo_set_weights_device's table; the embedding's rows past
+    the A actions stay out (play.py:193).  ``keep`` owns the memory."""
+    items = list(items)
+    n = len(items)
+    keys = (ctypes.c_char_p * n)()
+    data = (ctypes.c_void_p * n)()
+    shapes = (ctypes.POINTER(ctypes.c_int64) * n)()
+    ndims = (ctypes.c_int * n)()
+    keep = []
+    for i, (key, t) in enumerate(items):
+        a = np.ascontiguousarray(torch.as_tensor(t).detach().to("cpu", torch.float32).numpy())
+        if key == "dynamics.action_embedding.weight" and a.ndim == 2 and a.shape[0] > A:
+            a = np.ascontiguousarray(a[:A])
+        shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
+        keep.append((a, shape))
+        keys[i] = key.encode()
+        data[i] = a.ctypes.data
+        shapes[i] = ctypes.cast(shape, ctypes.POINTER(ctypes.c_int64))
+        ndims[i] = a.ndim
+    return keys, data, shapes, ndims, n, keep
+
+
+def pack_weights_host(state_dict, board_size):
+    """The packed weight blob (numpy float32) of a ``board_size`` engine from a
+    reference state_dict (a mapping or (key, tensor) pairs), on the host
+    (mzgo_weights_pack_host): the floats ``Engine.export_weights()`` returns
+    after either load, bit for bit, without an engine or a GPU.  latent_dim is
+    the embedding's width."""
+    items = list(state_dict.items() if hasattr(state_dict, "items") else state_dict)
+    N = int(board_size)
+    widths = [np.shape(t)[-1] for k, t in items if k == "dynamics.action_embedding.weight" and np.ndim(t) == 2]
+    if not widths:
+        raise _lib.MzgoError("mzgo error -1: missing weight 'dynamics.action_embedding.weight'")
+    keys, data, shapes, ndims, n, keep = _weight_table(items, N * N + 1)
+    total = ctypes.c_int64()
+    check(lib.mzgo_weights_pack_host(N, int(widths[0]), keys, data, shapes, ndims, n, None, 0, ctypes.byref(total)))
+    out = np.empty(total.value, np.float32)
+    check(lib.mzgo_weights_pack_host(N, int(widths[0]), keys, data, shapes, ndims, n, ptr(out), out.size,
+                                     ctypes.byref(total)))
+    return out
+
+
 class Engine:
     def __init__(self, config: EngineConfig):
         self.config = config

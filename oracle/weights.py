@@ -69,3 +69,18 @@ def deterministic_state_dict(latent_dim, action_size, seed=0):
         unit = ((u24 - (1 << 23)).astype(np.float32) / np.float32(1 << 23)).astype(np.float32)
         out[key] = (unit * np.float32(bound)).astype(np.float32).reshape(shape)
     return out
+
+
+def scaled_state_dict(latent_dim, action_size, seed=0):
+    """``deterministic_state_dict`` with flat element ``i`` of each tensor
+    scaled by 10**(i % 12 - 8) in float32 and, in tensors of at least 16
+    elements, every 50th element set to -0.0: variety in the packers' f64 ->
+    f32 rounding, from numpy alone (tests/golden/weight_blobs.json)."""
+    scale = np.array([float(f"1e{k}") for k in range(-8, 4)], dtype=np.float32)
+    out = OrderedDict()
+    for key, w in deterministic_state_dict(latent_dim, action_size, seed).items():
+        flat = (w.reshape(-1) * scale[np.arange(w.size) % 12]).astype(np.float32)
+        if flat.size >= 16:
+            flat[::50] = np.float32(-0.0)
+        out[key] = flat.reshape(w.shape)
+    return out

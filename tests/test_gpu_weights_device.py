@@ -6,9 +6,15 @@ mzgo_weights_export; ``Engine.set_parameters_device`` / ``copy_weights_from``,
 
 The device pack must give the host packers' blob: every comparison here is
 byte for byte (``view(np.uint32)``), no tolerance.  Engines are 1 game x 1
-simulation (``compat="fixed"``) so that 19x19 allocates little.
+simulation (``compat="fixed"``) so that 19x19 allocates little.  Both paths
+run one text (csrc/mzgo_weights.hpp), so each is also held to the blobs
+recorded before they did (tests/golden/weight_blobs.json,
+scripts/record_weight_blobs.py).
 """
 import ctypes
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -74,6 +80,26 @@ def test_blob_is_the_host_packers(N, C):
         want, got = host.export_weights(), dev.export_weights()
         assert len(got) == len(want) and len(want) % 64 == 0
         _same_bits(got, want)
+    host.close()
+    dev.close()
+
+
+@pytest.mark.parametrize("N,C", KERNEL_SETS)
+def test_each_path_gives_the_recorded_blob(N, C):
+    from oracle.weights import deterministic_state_dict, scaled_state_dict
+    A = N * N + 1
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "weight_blobs.json")) as f:
+        golden = {c["state_dict"]: c for c in json.load(f)["cases"] if (c["board_size"], c["latent_dim"]) == (N, C)}
+    assert sorted(golden) == ["deterministic_3", "scaled_7"]
+    host, dev = _engine(N, C), _engine(N, C)
+    for name, sd in (("deterministic_3", deterministic_state_dict(C, A, 3)), ("scaled_7", scaled_state_dict(C, A, 7))):
+        sd = {k: torch.from_numpy(v) for k, v in sd.items()}
+        host.set_state_dict(sd)
+        dev.set_parameters_device(_cuda(sd))
+        for path, e in (("set_state_dict", host), ("set_parameters_device", dev)):
+            blob = e.export_weights()
+            assert blob.size == golden[name]["n_floats"], (path, name)
+            assert hashlib.sha256(blob.tobytes()).hexdigest() == golden[name]["sha256"], (path, name)
     host.close()
     dev.close()
 
