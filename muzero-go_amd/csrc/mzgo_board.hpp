@@ -38,14 +38,18 @@ struct BoardLds {
 };
 
 // Who steps a board (the board functions' team parameter T): the whole
-// workgroup.  (One wave alone was tried for self-play's end of move: the
-// label propagation ran slower without the other waves' lanes.)
+// workgroup.  (One wave alone was tried for self-play's end of move inside
+// the 12-wave megakernel: the label propagation ran slower without the other
+// waves' lanes.  The boards launch has teams of its own, mzgo_kernels.hpp.)
+// any(v, phase): whether v is non-zero on any thread, with a barrier; calls
+// that no other barrier separates pass consecutive phases (a team may keep
+// one flag buffer per phase parity).
 template <class G>
 struct BoardWG {
   static constexpr int SIZE = G::THREADS;
   __device__ static int id() { return tid_local(); }
   __device__ static void sync() { __syncthreads(); }
-  __device__ static bool any(int v) { return __syncthreads_or(v) != 0; }
+  __device__ static bool any(int v, int = 0) { return __syncthreads_or(v) != 0; }
   __device__ static bool leader() { return tid_local() == 0; }
 };
 template <class G>
@@ -80,7 +84,7 @@ __device__ __forceinline__ void label_components(int* label, ClassFn cls) {
       m = j < m ? j : m;
       if (m < label[c]) { label[c] = m; changed = 1; }
     }
-    if (!T::any(changed)) break;
+    if (!T::any(changed, it)) break;
   }
 }
 
@@ -140,9 +144,26 @@ __device__ __forceinline__ void compute_invalid(BoardLds<G>& b, int mover, int k
 
 enum : int { BOARD_OK = 0, BOARD_ERR_DONE = 1, BOARD_ERR_INVALID = 2, BOARD_ERR_RANGE = 3 };
 
+// The stone groups' labels and liberties of the board as it stands: what a
+// board_step<G, T, true> expects to find (and leaves behind).
+template <class G, class T>
+__device__ __forceinline__ void board_groups(BoardLds<G>& b) {
+  label_components<G, T>(b.label, [&](int c) { return (int)b.stone[c]; });
+  count_liberties<G, T>(b, false);
+}
+
 // gogame.next_state(state, action, canonical=False) on the LDS board.
 // Returns a BOARD_* status (uniform across the workgroup).
-template <class G, class T = BoardWG<G>>
+// KEEP: b.label / b.libs hold the groups of the board before the move
+// (board_groups, or the previous board_step<.., true>; nothing else wrote
+// them in between), and the step updates them instead of labelling the board
+// from scratch.  The invariant is label_components': a stone's label is the
+// smallest cell index of its group, an empty cell's is -1.  A placement joins
+// the new stone to at most four groups of its colour, whose smallest index is
+// the minimum of their labels and the stone's cell; a capture removes whole
+// groups, which splits none; a pass changes nothing.  So labels, libs, gsize,
+// the order of killed[] and the ko point are the from-scratch step's.
+template <class G, class T = BoardWG<G>, bool KEEP = false>
 __device__ __forceinline__ int board_step(BoardLds<G>& b, BoardMeta& m, int action) {
   if (m.done) return BOARD_ERR_DONE;                 // GoEnv.step: assert not self.done
   if (action < 0 || action > G::CELLS) return BOARD_ERR_RANGE;
@@ -151,11 +172,23 @@ __device__ __forceinline__ int board_step(BoardLds<G>& b, BoardMeta& m, int acti
   if (action == G::CELLS) {                          // pass
     if (m.passed) m.done = 1;
     m.passed = 1;
-    label_components<G, T>(b.label, [&](int c) { return (int)b.stone[c]; });
-    count_liberties<G, T>(b, false);
+    if constexpr (!KEEP) board_groups<G, T>(b);
   } else {
     if (b.invd[action]) return BOARD_ERR_INVALID;    // assert INVD == 0
     m.passed = 0;
+    // KEEP: the labels of the new stone's own-colour neighbour groups, read
+    // before the barrier below, rewritten after it
+    int join[4] = {-2, -2, -2, -2}, lmin = action;    // (-2: no stone's label)
+    if constexpr (KEEP) {
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        int n;
+        if (nbr<G>(action, d, n) && b.stone[n] == player + 1) {
+          join[d] = b.label[n];
+          lmin = join[d] < lmin ? join[d] : lmin;
+        }
+      }
+    }
     if (T::leader()) {
       b.stone[action] = (int8_t)(player + 1);
       bool boxed = true;
@@ -166,7 +199,17 @@ __device__ __forceinline__ int board_step(BoardLds<G>& b, BoardMeta& m, int acti
       b.misc[1] = boxed;
     }
     T::sync();
-    label_components<G, T>(b.label, [&](int c) { return (int)b.stone[c]; });
+    if constexpr (KEEP) {
+      for (int c = T::id(); c < G::CELLS; c += T::SIZE) {
+        if (c == action) { b.label[c] = lmin; continue; }
+        if (b.stone[c] != player + 1) continue;
+        const int l = b.label[c];
+        if (l == join[0] || l == join[1] || l == join[2] || l == join[3]) b.label[c] = lmin;
+      }
+      // (count_liberties' barrier after its zeroing pass orders these writes before its reads)
+    } else {
+      label_components<G, T>(b.label, [&](int c) { return (int)b.stone[c]; });
+    }
     count_liberties<G, T>(b, true);
     // opponent groups adjacent to the new stone with no liberty die
     if (T::leader()) {
@@ -191,7 +234,7 @@ __device__ __forceinline__ int board_step(BoardLds<G>& b, BoardMeta& m, int acti
           const int l = b.label[c];
           bool dead = false;
           for (int i = 0; i < nk; ++i) dead |= b.killed[i] == l;
-          if (dead) b.stone[c] = 0;
+          if (dead) { b.stone[c] = 0; if constexpr (KEEP) b.label[c] = -1; }
         }
       }
       T::sync();
@@ -205,6 +248,8 @@ __device__ __forceinline__ int board_step(BoardLds<G>& b, BoardMeta& m, int acti
 }
 
 // gogame.winning: sign(black_area - white_area - komi), area (Tromp-Taylor).
+// (Overwrites label / libs / gsize with the empty regions': no
+// board_step<.., true> may follow without a board_groups.)
 template <class G, class T = BoardWG<G>>
 __device__ __forceinline__ double board_winning(BoardLds<G>& b, double komi) {
   label_components<G, T>(b.label, [&](int c) { return b.stone[c] == 0 ? 1 : 0; });

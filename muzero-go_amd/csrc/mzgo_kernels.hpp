@@ -1843,22 +1843,60 @@ __global__ void __launch_bounds__((Geo<N, C>::THREADS)) __attribute__((amdgpu_wa
 // ---------------------------------------------------------------------------
 // The move-parallel epoch, first launch: every game's moves without their
 // searches (record, legal mask, action, board step, result).  A game's
-// moves are a serial chain of board steps, each a few label-propagation
-// rounds with a barrier apiece, so the step's latency is
+// moves are a serial chain of board steps, each a dozen passes over the board
+// with a barrier apiece, so the step's latency is
 // the launch's: a workgroup of BoardsGeo::THREADS (one cell per lane, 2 waves
 // at 9x9) with a few KB of LDS instead of k_selfplay_move's 12 waves and 159
-// KB.  The move is mzgo_move.hpp's, with this workgroup as the team.
+// KB.  The move is mzgo_move.hpp's, with this workgroup as the team; what
+// only a launch of several moves can do is done here: the board and its
+// groups stay in LDS and are updated per move (play_action's HELD), and the
+// slot's board and the counters are written once per game.
 // ---------------------------------------------------------------------------
 template <class G>
 struct BoardsGeo {
   static constexpr int THREADS = (G::CELLS + 63) / 64 * 64 < 512 ? (G::CELLS + 63) / 64 * 64 : 512;
+  static constexpr int WAVES = THREADS / 64;
 };
+// The boards launch's team.  Its barriers order LDS only: a wave waits for its
+// own LDS operations (lgkmcnt), never for the move's global stores (the
+// records, the policy row: nothing in the launch reads them back, and the
+// kernel's end publishes them), then joins the workgroup barrier.  (On gfx950
+// __syncthreads compiles to the same wait; the fence says so by name.  What
+// the team saves is in any(): one barrier and a flag per wave, where
+// __syncthreads_or takes two barriers round an LDS reduction -- once per
+// labelling round and per legal mask.)  A team of one wave (up to 64 cells)
+// needs no barrier: its LDS operations complete in order.
 template <class G>
 struct BoardsTeam {
   static constexpr int SIZE = BoardsGeo<G>::THREADS;
+  static constexpr int WAVES = BoardsGeo<G>::WAVES;
   __device__ static int id() { return tid_local(); }
-  __device__ static void sync() { __syncthreads(); }
-  __device__ static bool any(int v) { return __syncthreads_or(v) != 0; }
+  __device__ static void sync() {
+    if constexpr (WAVES == 1) {
+      wave_lds_sync();
+    } else {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    }
+  }
+  // a flag per wave and phase parity: call k + 2 rewrites call k's flags, and
+  // call k + 1's barrier lies between that and every wave's read of them
+  __device__ static bool any(int v, int phase = 0) {
+    const bool mine = __ballot(v != 0) != 0;
+    if constexpr (WAVES == 1) {
+      wave_lds_sync();
+      return mine;
+    } else {
+      __shared__ int flag[2][WAVES];
+      if (lane_id_local() == 0) flag[phase & 1][wave_id()] = mine;
+      sync();
+      int r = 0;
+#pragma unroll
+      for (int w = 0; w < WAVES; ++w) r |= flag[phase & 1][w];
+      return r != 0;
+    }
+  }
   __device__ static bool leader() { return tid_local() == 0; }
 };
 template <class G>
@@ -1888,8 +1926,21 @@ __global__ void __launch_bounds__((BoardsGeo<Geo<N, C>>::THREADS)) k_selfplay_bo
   BoardMeta m;
   board_load<G, T>(sm.stone, sm.invd, E, g, m);
   BoardLds<G> b = make_board_lds<G>(sm.stone, sm.invd, sm.label, sm.libs, sm.gsize, sm.killed, sm.misc);
+  board_groups<G, T>(b);                                 // kept from move to move (play_action's HELD)
+  // MZGO_STAMPS: thread 0's cycles per phase of a move, summed over the launch's moves (slots: below)
+#ifdef MZGO_STAMPS
+  unsigned long long lapc[6] = {}, lapt = __builtin_amdgcn_s_memtime();
+  auto lap = [&](int k) {
+    const unsigned long long now = __builtin_amdgcn_s_memtime();
+    lapc[k] += now - lapt;
+    lapt = now;
+  };
+#else
+  auto lap = [](int) {};
+#endif
   const int mv_first = m.moves;
-  int played = 0;
+  int played = 0, finished = 0;
+  unsigned long long sims = 0;
   const TreeView TV = TreeViewOf<G>::make(E, g);         // (compat "reference" reads no tree)
   for (int step = 0; step < pp.moves; ++step) {
     const int mv = m.moves;
@@ -1897,8 +1948,11 @@ __global__ void __launch_bounds__((BoardsGeo<Geo<N, C>>::THREADS)) k_selfplay_bo
     const uint64_t key = move_key(sp, pp, g, mv);
     const int budget = move_budget<CAPS>(sp, key);       // (k_search_queue derives the same from the same key)
     record_observation<G, T>(E, rec, sm.stone, sm.invd, m, CAPS && budget != sp.num_simulations);
+    lap(0);
     ++played;
+    sims += (unsigned long long)budget;
     build_mask<G, T>(sm.t, sp.pass_epsilon, [&](int a) { return sm.invd[a]; });
+    lap(1);
     if (wave_id() == 0) {
       // (the host launches this schedule for search variant 0 only: choose_move_action's self_play.py arm)
       const int a = choose_action<G>(sm.t, TV, sp.compat, move_temperature(pp, mv), key, E.rec_policy + rec * G::A);
@@ -1907,13 +1961,29 @@ __global__ void __launch_bounds__((BoardsGeo<Geo<N, C>>::THREADS)) k_selfplay_bo
         E.rec_action[rec] = a;
       }
     }
-    __syncthreads();
+    T::sync();
+    lap(move_temperature(pp, mv) != 0.0 ? 2 : 3);
     double w;
-    const int st = play_action<G, T>(E, g, b, m, sm.bc[0], pp.komi, w);
-    if (finish_move<G, T>(E, budget, g, rec, st, m, w)) break;
-    __syncthreads();                               // this move's LDS reads before the next move's writes
+    const int st = play_action<G, T, true>(E, g, b, m, sm.bc[0], pp.komi, w);
+    lap(4);
+    finished += game_finished(E, st, m);
+    if (finish_move<G, T, false>(E, budget, g, rec, st, m, w)) break;
+    T::sync();                                     // this move's LDS reads before the next move's writes
+    lap(5);
   }
+  // the slot's board, the launch's counters and the queue's (first move, moves played): once per game
+  board_store<G, T>(sm.stone, sm.invd, E, g, m);
   if (tid == 0) {
+    count_moves(E, sims, played, finished);
+#ifdef MZGO_STAMPS
+    // 83 record, 84 legal mask, 85 / 86 action choice with / without temperature, 87 board step and
+    // winner, 47 result + the move's last barrier, 45 moves
+    if (E.stamps) {
+      unsigned long long* row = E.stamps + (size_t)g * kStampPhases;
+      row[83] += lapc[0]; row[84] += lapc[1]; row[85] += lapc[2]; row[86] += lapc[3];
+      row[87] += lapc[4]; row[47] += lapc[5]; row[45] += (unsigned long long)played;
+    }
+#endif
     E.mpq[2 * g] = mv_first;
     E.mpq[2 * g + 1] = played;
   }

@@ -344,23 +344,39 @@ __device__ __forceinline__ int choose_action(TreeLds<G>& t, const TreeView& T, i
   wave_lds_sync();
   const double ts = np_pairwise_sum<double, G::A>(t.dbuf);
   wave_lds_sync();
-  for (int a = lane; a < G::A; a += 64) t.dbuf[a] = ts > 0 ? t.dbuf[a] / ts : mask_of<G>(t, a) / msum;
-  wave_lds_sync();
-  if (lane == 0) {
-    double cdf = 0.0;
-    for (int a = 0; a < G::A; ++a) cdf += t.dbuf[a];
-    const double total = cdf;
-    const double u = u01(h);
-    double run = 0.0;
-    int idx = 0;
-    for (int a = 0; a < G::A; ++a) {
-      run += t.dbuf[a];
-      if (run / total <= u) idx = a + 1;
-    }
-    t.bcast = idx;
+  // np.cumsum is a sequential f64 sum over a = 0 .. A-1: every lane runs it on
+  // the probabilities read lane by lane from the registers that hold them
+  // (p[j]: action lane + 64 j), and keeps the prefix of its own actions.  The
+  // test cdf[a] / cdf[-1] <= u is then formed for all actions at once, with
+  // the same division and comparison per entry; the index is one past the
+  // highest action that passes (searchsorted(side="right") on a
+  // non-decreasing cdf).
+  double p[G::AP], pre[G::AP];
+#pragma unroll
+  for (int j = 0; j < G::AP; ++j) {
+    const int a = lane + 64 * j;
+    p[j] = a < G::A ? (ts > 0 ? t.dbuf[a] / ts : mask_of<G>(t, a) / msum) : 0.0;
+    pre[j] = 0.0;
   }
-  wave_lds_sync();
-  return t.bcast;
+  double run = 0.0;
+#pragma unroll
+  for (int j = 0; j < G::AP; ++j) {
+#pragma unroll
+    for (int l = 0; l < 64; ++l) {
+      if (64 * j + l < G::A) {
+        run += dpp::lane(p[j], l);
+        if (lane == l) pre[j] = run;
+      }
+    }
+  }
+  const double total = run, u = u01(h);
+  int idx = 0;
+#pragma unroll
+  for (int j = 0; j < G::AP; ++j) {
+    const uint64_t ok = __ballot(lane + 64 * j < G::A && pre[j] / total <= u);
+    if (ok) idx = 64 * j + 64 - __clzll((long long)ok);
+  }
+  return idx;
 }
 
 // the temperature schedule (self_play.py:471) and the action of move mv by the engine's rule (sp.variant)
@@ -386,13 +402,18 @@ __device__ __forceinline__ double root_value(const TreeView& T) {
 // env.step(action) and env.winner() (self_play.py:479, :502) on the LDS board,
 // stored back to slot g.  Returns the BOARD_* status; w = the winner once the
 // game has ended, else 0.  All of T.
-template <class G, class T = BoardWG<G>>
+// HELD (k_selfplay_boards): the board and its groups stay in LDS from move to
+// move of the launch -- board_groups once after board_load, then every step
+// updates them (board_step's KEEP), and the caller stores the board once, when
+// the game's loop ends.  (board_winning runs only on the game's last move, so
+// no step follows its use of the group arrays.)
+template <class G, class T = BoardWG<G>, bool HELD = false>
 __device__ __forceinline__ int play_action(const EngineArrays& E, int g, BoardLds<G>& b, BoardMeta& m, int action,
                                            double komi, double& w) {
-  const int st = board_step<G, T>(b, m, action);
+  const int st = board_step<G, T, HELD>(b, m, action);
   T::sync();
   w = (st == BOARD_OK && m.done) ? board_winning<G, T>(b, komi) : 0.0;
-  board_store<G, T>(b.stone, b.invd, E, g, m);
+  if constexpr (!HELD) board_store<G, T>(b.stone, b.invd, E, g, m);
   return st;
 }
 
@@ -401,24 +422,40 @@ __device__ __forceinline__ int play_action(const EngineArrays& E, int g, BoardLd
 // length and final reward when the game ends (double pass, max_moves moves or
 // a board error, status 16 + BOARD_*).  All of T call it, the leader writes;
 // returns whether the game is over.
-template <class G, class T = BoardWG<G>>
+// COUNT = false: the caller adds counters 0-2 itself (count_moves), once for
+// all the moves it played in the launch.
+template <class G, class T = BoardWG<G>, bool COUNT = true>
 __device__ __forceinline__ bool finish_move(const EngineArrays& E, int sims, int g, size_t rec, int st,
                                             const BoardMeta& m, double w) {
   const bool ended = m.done || m.moves >= E.max_moves;
   if (T::leader()) {
     E.rec_reward[rec] = w;
-    atomicAdd(&E.counters[0], (unsigned long long)sims);
-    atomicAdd(&E.counters[1], 1ull);
+    if constexpr (COUNT) {
+      atomicAdd(&E.counters[0], (unsigned long long)sims);
+      atomicAdd(&E.counters[1], 1ull);
+    }
     if (st != BOARD_OK) {
       E.status[g] = 16 + st;
     } else if (ended) {
       E.status[g] = 1;
       E.game_len[g] = m.moves;
       E.final_reward[g] = m.done ? w : 0.0;      // env.winner() is 0 unless ended
-      atomicAdd(&E.counters[2], 1ull);
+      if constexpr (COUNT) atomicAdd(&E.counters[2], 1ull);
     }
   }
   return st != BOARD_OK || ended;
+}
+// whether finish_move(st, m) counted a finished game (counter 2)
+__device__ __forceinline__ bool game_finished(const EngineArrays& E, int st, const BoardMeta& m) {
+  return st == BOARD_OK && (m.done || m.moves >= E.max_moves);
+}
+// what finish_move<.., false> left out, for a launch's moves of one game: one thread
+__device__ __forceinline__ void count_moves(const EngineArrays& E, unsigned long long sims, int moves, int finished) {
+  if (moves) {
+    atomicAdd(&E.counters[0], sims);
+    atomicAdd(&E.counters[1], (unsigned long long)moves);
+  }
+  if (finished) atomicAdd(&E.counters[2], (unsigned long long)finished);
 }
 
 }  // namespace mzgo
