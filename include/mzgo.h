@@ -1140,6 +1140,88 @@ int mzgo_ownership_loss_host(const float* latents, const float* w, const float* 
                              float* per, double* total, float* g_x, float* g_latents, float* g_w, float* g_bias);
 
 /* --------------------------------------------------------------------------
+ * The latent consistency loss (EfficientZero's temporal consistency, SimSiam's
+ * form, on MuZero's unrolled latents; not in main.py): the dynamics' k-th
+ * latent s_k is pulled towards the representation's latent of the real board
+ * at start + k, through a head of two 1x1 convs of its own, proj (C -> P) and
+ * pred (P -> P).  The target side carries no gradient.
+ *
+ * The real boards.  mzgo_replay_window_obs / _items write, for sample (slot,
+ * start, symmetry) and k = 1..unroll_steps,
+ *   obs [K][B][6][N*N]   the six planes of position start + k exactly as
+ *                        mzgo_replay_batch writes obs0 for it (the same planes
+ *                        through the same sym_src permutation), STEP-major so
+ *                        that [K B][6][N][N] goes to mzgo_encode as it is and
+ *                        lines up with the unroll's latents 1..K
+ *   window_mask [B][K]   1 where start + k <= L (row L, the final board, is
+ *                        stored and counts), else 0 with all-zero planes; a
+ *                        slot outside the ring gives the same
+ * with mzgo_replay_ownership's arguments and checks: host indices, starts and
+ * symmetries (NULL: identity), or the sampler's DEVICE items [B][3] (nothing
+ * crosses the bus, nothing synchronises).  One launch, a workgroup per sample;
+ * unroll_steps in 0..63, and 0 launches nothing (the outputs may be NULL). */
+int mzgo_replay_window_obs(mzgo_replay* replay, const int32_t* indices_host, const int32_t* starts_host,
+                           const int32_t* symmetries_host, int B, int unroll_steps, float* obs, float* window_mask,
+                           void* stream);
+int mzgo_replay_window_obs_items(mzgo_replay* replay, const int32_t* items, int B, int unroll_steps, float* obs,
+                                 float* window_mask, void* stream);
+
+/* The representation alone: obs f32 [B][6][N][N] -> latents f32 [B][C][N][N] by
+ * mzgo_unroll_forward's three representation convs, under the same parameter
+ * table (any of the net's 22 tensors may be there; the representation's six
+ * must be) and the same checks (C a multiple of 16, N in 2..19, emb_rows >=
+ * N*N + 1).  The bits are those of the step-0 latents of mzgo_unroll_forward on
+ * the same obs; no heads, no saved buffer, no gradient.  ``work``
+ * (mzgo_encode_workspace bytes) holds the two intermediates.  Any B >= 1: past
+ * 65535 boards the convs run in chunks inside the call.  Three launches per
+ * chunk; stream-ordered; nothing allocates or synchronises. */
+int mzgo_encode_workspace(int B, int C, int N, int64_t* work_bytes);
+int mzgo_encode(const char* const* keys, const float* const* params, const int64_t* const* shapes, const int* ndims,
+                int n_params, const float* obs, int B, int C, int N, int emb_rows, float* latents, void* work,
+                int64_t work_bytes, void* stream);
+
+/* The head and the loss on ``latents`` [K+1][B][C][N][N] (mzgo_unroll_latents'
+ * layout, taken whole: step 0 takes no part), ``targets`` [K][B][C][N][N]
+ * (mzgo_encode of mzgo_replay_window_obs's boards) and ``mask`` [B][K], with
+ * proj_w [P][C], proj_b [P], pred_w [P][P], pred_b [P].  For row (k, b),
+ * k = 1..K, over the D = P N N entries:
+ *   u = proj(latents[k][b]),  p = pred(relu(u)),  z = proj(targets[k-1][b])
+ *   cos = <p, z> / (|p| |z|)         (f64 sums; cos := 0 where |p| or |z| < 1e-8,
+ *                                     and such a row's gradient is exactly 0)
+ *   per[b] = weight sum_k mask[b][k-1] (1 - cos)
+ * z is a constant of the backward (the stop-gradient): nothing flows to
+ * ``targets`` nor, along z, to proj.  The convs are f32 fmaf chains
+ * (v_mfma_f32_16x16x4_f32).  C a multiple of 16 up to 256; P one of 16, 32,
+ * 48, 64; K >= 1; N in 2..19.
+ * mzgo_consistency_loss writes per f32 [B] and *total (f64, the samples' sum)
+ * and leaves in ``work`` what the backward reads (u, p, z and four scalars per
+ * row): two launches.  mzgo_consistency_loss_backward takes the incoming g_per
+ * [B] and the SAME ``work``, and writes g_latents [K+1][B][C][N][N] (step 0:
+ * zeros), g_proj_w, g_proj_b, g_pred_w, g_pred_b: two launches; it reads
+ * ``latents`` again and never ``targets``.  The parameter gradients' partial
+ * sums are one set per chunk of rows walked in order by one workgroup, at most
+ * 512 chunks and 32 MB whatever the shapes, summed over the chunks in order in
+ * f64; no atomics, so repeats are bit-identical.  A row whose mask is 0 is not
+ * read and contributes exact zeros.  All pointers are device pointers; nothing
+ * allocates or synchronises.
+ * mzgo_consistency_loss_host is both on HOST arrays with serial sums in index
+ * order (csrc/mzgo_consistency.hpp's functions): no device work. */
+int mzgo_consistency_loss_workspace(int B, int K, int C, int P, int N, int64_t* work_bytes);
+int mzgo_consistency_loss(const float* latents, const float* targets, const float* mask, const float* proj_w,
+                          const float* proj_b, const float* pred_w, const float* pred_b, int B, int K, int C, int P,
+                          int N, float weight, float* per, double* total, void* work, int64_t work_bytes,
+                          void* stream);
+int mzgo_consistency_loss_backward(const float* latents, const float* mask, const float* g_per, const float* proj_w,
+                                   const float* pred_w, int B, int K, int C, int P, int N, float weight,
+                                   float* g_latents, float* g_proj_w, float* g_proj_b, float* g_pred_w,
+                                   float* g_pred_b, void* work, int64_t work_bytes, void* stream);
+int mzgo_consistency_loss_host(const float* latents, const float* targets, const float* mask, const float* proj_w,
+                               const float* proj_b, const float* pred_w, const float* pred_b, const float* g_per,
+                               int B, int K, int C, int P, int N, float weight, float* per, double* total,
+                               float* g_latents, float* g_proj_w, float* g_proj_b, float* g_pred_w,
+                               float* g_pred_b);
+
+/* --------------------------------------------------------------------------
  * The trainer's optimizer tail in one call (main.py:481-484 and :379:
  * clip_grad_norm_, torch.optim.Adam.step and StepLR.step over the parameter
  * tensors, some two dozen small torch launches; this call replaces that

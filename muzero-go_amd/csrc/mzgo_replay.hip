@@ -19,7 +19,9 @@
 // k_replay_possample_draw), with the
 // positions' weights written back from the step's value errors.  Next to the
 // batch assembly, one more launch on the same items turns the games' final
-// boards into the ownership head's targets (k_replay_ownership).
+// boards into the ownership head's targets (k_replay_ownership), and another
+// gives the real boards of the windows' steps 1..K for the consistency loss
+// (k_replay_window_obs).
 //
 // Kernels here use plain vector loads and stores only (and one vector atomic,
 // the count of refused priority updates); workgroups never communicate.  Compiled with -ffp-contract=off like every unit: the value
@@ -221,6 +223,54 @@ __global__ void __launch_bounds__(kThreads) k_replay_ownership(Store R, const in
     float v = 0.f;
     if (own_row_valid(at, L, final_flags)) v = own_target(owner[perm[c]], 1 + (R.flags[pos + at] & 1));
     out[e] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The real boards of a sampled window (the consistency loss's targets' inputs):
+// one workgroup per sample (slot, start, symmetry).  obs[k-1][b] is the six
+// planes of position start + k, k = 1..K, exactly as k_replay_batch writes obs0
+// for that position (the same planes through the same cell permutation),
+// step-major [K][B][6][CELLS]; window_mask[b][k-1] = start + k <= L (row L, the
+// final board, is stored and counts).  Past the final board and for a slot
+// outside the ring: zeros and mask 0.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kThreads) k_replay_window_obs(Store R, const int* items, int B, int K,
+                                                                float* __restrict__ obs,
+                                                                float* __restrict__ window_mask) {
+  __shared__ int perm[kMaxBoard * kMaxBoard];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int slot = items[3 * b], start = items[3 * b + 1], sym = items[3 * b + 2] & 7;
+  const int CELLS = R.CELLS, N = R.N;
+  const bool held = slot >= 0 && slot < R.cap;
+  int L = held ? R.length[slot] : 0;
+  L = L < 0 ? 0 : L > R.M ? R.M : L;
+  const size_t pos = held ? (size_t)slot * (R.M + 1) : 0;
+  for (int c = tid; c < CELLS; c += kThreads) perm[c] = sym_src(N, sym, c);
+  if (tid < K) {
+    const long long at = (long long)start + tid + 1;
+    window_mask[(size_t)b * K + tid] = held && at >= 0 && at <= L ? 1.f : 0.f;
+  }
+  __syncthreads();
+  const int plane = 6 * CELLS;
+  for (int e = tid; e < K * plane; e += kThreads) {
+    const int k = e / plane, rem = e - k * plane;
+    const int p = rem / CELLS, c = rem - p * CELLS;
+    const long long at = (long long)start + k + 1;
+    float v = 0.f;
+    if (held && at >= 0 && at <= L) {
+      const size_t q = pos + (size_t)at;
+      const int fl = R.flags[q];
+      switch (p) {
+        case 0: v = R.stones[q * CELLS + perm[c]] == 1; break;
+        case 1: v = R.stones[q * CELLS + perm[c]] == 2; break;
+        case 2: v = fl & 1; break;
+        case 3: v = R.invd[q * CELLS + perm[c]]; break;
+        case 4: v = (fl >> 1) & 1; break;
+        default: v = (fl >> 2) & 1; break;
+      }
+    }
+    obs[((size_t)k * B + b) * plane + rem] = v;
   }
 }
 
@@ -1222,6 +1272,46 @@ int mzgo_replay_ownership_items(mzgo_replay* r, const int32_t* items, int B, int
   if (int rc = ownership_check(r, who, B, unroll_steps, t_own, own_mask)) return rc;
   if (!items) return set_error(MZGO_EINVAL, "%s: null items", who);
   return ownership_launch(r, items, B, unroll_steps, t_own, own_mask, (hipStream_t)stream);
+}
+
+// the checks the two window-observation assemblies share, and their launch (none at K = 0)
+static int window_obs_check(const mzgo_replay* r, const char* who, int B, int unroll_steps, const float* obs,
+                            const float* window_mask) {
+  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
+  if (unroll_steps < 0 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (0..%d)", who, unroll_steps, kMaxUnroll);
+  if (unroll_steps > 0 && (!obs || !window_mask))
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !obs ? "obs" : "window_mask");
+  return MZGO_OK;
+}
+static int window_obs_launch(mzgo_replay* r, const int* items, int B, int unroll_steps, float* obs, float* window_mask,
+                             hipStream_t s) {
+  if (unroll_steps == 0) return MZGO_OK;
+  hipLaunchKernelGGL(k_replay_window_obs, dim3(B), dim3(kThreads), 0, s, r->R, items, B, unroll_steps, obs,
+                     window_mask);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
+}
+
+int mzgo_replay_window_obs(mzgo_replay* r, const int32_t* indices_host, const int32_t* starts_host,
+                           const int32_t* symmetries_host, int B, int unroll_steps, float* obs, float* window_mask,
+                           void* stream) {
+  const char* who = "mzgo_replay_window_obs";
+  if (int rc = window_obs_check(r, who, B, unroll_steps, obs, window_mask)) return rc;
+  if (!indices_host || !starts_host)
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !indices_host ? "indices" : "starts");
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = upload_samples(r, who, indices_host, starts_host, symmetries_host, B, s)) return rc;
+  return window_obs_launch(r, r->d_items, B, unroll_steps, obs, window_mask, s);
+}
+
+int mzgo_replay_window_obs_items(mzgo_replay* r, const int32_t* items, int B, int unroll_steps, float* obs,
+                                 float* window_mask, void* stream) {
+  const char* who = "mzgo_replay_window_obs_items";
+  if (int rc = window_obs_check(r, who, B, unroll_steps, obs, window_mask)) return rc;
+  if (!items) return set_error(MZGO_EINVAL, "%s: null items", who);
+  return window_obs_launch(r, items, B, unroll_steps, obs, window_mask, (hipStream_t)stream);
 }
 
 int mzgo_ownership_host(const int8_t* stones, int board_size, int8_t* owner) {

@@ -526,6 +526,56 @@ int mzgo_unroll_forward_p(const char* const* keys, const float* const* params, c
   return MZGO_OK;
 }
 
+// The representation alone (the consistency loss's targets): the forward's three
+// convs without the staging copy, the heads and the saved buffer.  A batch past
+// the convs' grid limit goes through in chunks of kConvMaxBatch boards; a
+// board's conv does not depend on its neighbours, so the bits are the unroll's.
+static int encode_check(const char* fn, int B, int C, int N, int emb_rows) {
+  if (int rc = check_dims(fn, 1, 0, C, N, emb_rows)) return rc;
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", fn, B);
+  return MZGO_OK;
+}
+static size_t encode_work_floats(int B, int N) {
+  return 2 * (size_t)std::min(B, kConvMaxBatch) * kRepC * N * N;
+}
+
+int mzgo_encode_workspace(int B, int C, int N, int64_t* work_bytes) {
+  if (int rc = encode_check("mzgo_encode_workspace", B, C, N, N * N + 1)) return rc;
+  if (!work_bytes) return set_error(MZGO_EINVAL, "mzgo_encode_workspace: null work_bytes");
+  *work_bytes = (int64_t)(encode_work_floats(B, N) * sizeof(float));
+  return MZGO_OK;
+}
+
+int mzgo_encode(const char* const* keys, const float* const* params, const int64_t* const* shapes, const int* ndims,
+                int n_params, const float* obs, int B, int C, int N, int emb_rows, float* latents, void* work,
+                int64_t work_bytes, void* stream) {
+  const char* fn = "mzgo_encode";
+  if (int rc = encode_check(fn, B, C, N, emb_rows)) return rc;
+  const char* null = !obs ? "obs" : !latents ? "latents" : !work ? "work" : nullptr;
+  if (null) return set_error(MZGO_EINVAL, "%s: null %s", fn, null);
+  const float* P[WK_COUNT];
+  constexpr unsigned kRepSet = bit(WK_CONV1_W) | bit(WK_CONV1_B) | bit(WK_CONV2_W) | bit(WK_CONV2_B) |
+                               bit(WK_CONV3_W) | bit(WK_CONV3_B);
+  if (int rc = resolve(fn, keys, params, shapes, ndims, nullptr, n_params, C, emb_rows, kAllSet, kRepSet, 0, P, nullptr))
+    return rc;
+  if (work_bytes < (int64_t)(encode_work_floats(B, N) * sizeof(float)))
+    return set_error(MZGO_EINVAL, "%s: work too small: %lld < %lld bytes", fn, (long long)work_bytes,
+                     (long long)(encode_work_floats(B, N) * sizeof(float)));
+  hipStream_t s = (hipStream_t)stream;
+  const int CELLS = N * N;
+  float* x1 = static_cast<float*>(work);
+  float* x2 = x1 + (size_t)std::min(B, kConvMaxBatch) * kRepC * CELLS;
+  for (int b0 = 0; b0 < B; b0 += kConvMaxBatch) {
+    const int cb = std::min(B - b0, kConvMaxBatch);
+    MZGO_HIPCHK(conv_forward(obs + (size_t)b0 * 6 * CELLS, nullptr, nullptr, P[WK_CONV1_W], P[WK_CONV1_B], cb, 6, kRepC,
+                             N, x1, s));
+    MZGO_HIPCHK(conv_forward(x1, nullptr, nullptr, P[WK_CONV2_W], P[WK_CONV2_B], cb, kRepC, kRepC, N, x2, s));
+    MZGO_HIPCHK(conv_forward(x2, nullptr, nullptr, P[WK_CONV3_W], P[WK_CONV3_B], cb, kRepC, C, N,
+                             latents + (size_t)b0 * C * CELLS, s));
+  }
+  return MZGO_OK;
+}
+
 int mzgo_unroll_backward(const char* const* keys, const float* const* params, const int64_t* const* shapes,
                          const int* ndims, float* const* grads, int n_params, const void* saved, int64_t saved_bytes,
                          const float* g_logits, const float* g_value, const float* g_reward, int B, int K, int C, int N,

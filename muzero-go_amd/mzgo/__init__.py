@@ -36,6 +36,12 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
   from the store's final boards (``DeviceReplay.ownership``;
   ``TrainConfig.ownership_loss_weight``); ``ownership_host``, ``ownership_targets_host`` and
   ``ownership_loss_host`` are the rules on host arrays
+* ``ConsistencyHead``, ``consistency_loss``, ``encode`` -- the latent consistency loss
+  (EfficientZero's, in SimSiam's form): the unrolled latents ``s_1..s_K`` are pulled towards the
+  representation's latents (``encode``: the representation alone, no gradient) of the real boards
+  the store holds for the window (``DeviceReplay.window_obs``), through a head of two 1x1 convs
+  on f32 MFMA kernels, two launches each way (``TrainConfig.consistency_loss_weight``);
+  ``consistency_loss_host`` is the rule on host arrays
 * ``DeviceAdam`` -- the optimizer tail (gradient-norm clip, Adam / AdamW, StepLR) of any float32
   module in one stream-ordered HIP call that refuses and counts a non-finite gradient
   (``TrainConfig.device_optimizer``); ``adam_step_host`` is its host twin on numpy arrays
@@ -46,6 +52,7 @@ self_play.py), all executed by libmzgo.so's HIP kernels:
 from ._lib import MzgoError
 from .arena import SelfPlayEvaluator
 from .engine import Engine, EngineConfig, pack_weights_host, playout_budget_host
+from .consistency import ConsistencyHead, consistency_loss, consistency_loss_host
 from .env import GoEnv
 from .loss import unroll_loss, unroll_loss_host
 from .net import MuZeroNet
@@ -57,7 +64,7 @@ from .replay import (DeviceReplay, ownership_host, ownership_targets_host, posit
 from .resnet import ResMuZeroNet
 from .search import MCTS, MainMCTS, MuZeroAgent
 from .selfplay import GameHistory, SelfPlay, history_from_device, save_batches
-from .unroll import bf16_round_host, unroll, unroll_heads_host
+from .unroll import bf16_round_host, encode, unroll, unroll_heads_host
 from .weights import deterministic_res_state_dict, deterministic_state_dict
 
 __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "MuZeroAgent", "SelfPlay",
@@ -67,4 +74,5 @@ __all__ = ["Engine", "EngineConfig", "GoEnv", "MuZeroNet", "MCTS", "MainMCTS", "
            "unroll_loss_host", "unroll", "unroll_heads_host", "bf16_round_host", "window_items_host", "value_targets_host",
            "sample_positions_host", "position_priorities_host", "DeviceAdam", "adam_step_host", "optim_chunk",
            "playout_budget_host", "OwnershipHead", "ownership_loss", "ownership_loss_host", "ownership_host",
-           "ownership_targets_host", "pack_weights_host"]
+           "ownership_targets_host", "pack_weights_host", "ConsistencyHead", "consistency_loss",
+           "consistency_loss_host", "encode"]

@@ -183,6 +183,14 @@ SIGNATURES = {
     "mzgo_ownership_loss": (_I, [_P] * 5 + [_I] * 4 + [ctypes.c_float] + [_P] * 4 + [ctypes.c_int64, _P]),
     "mzgo_ownership_loss_backward": (_I, [_P] * 5 + [_I] * 4 + [_P] * 4 + [ctypes.c_int64, _P]),
     "mzgo_ownership_loss_host": (_I, [_P] * 6 + [_I] * 4 + [ctypes.c_float] + [_P] * 6),
+    "mzgo_replay_window_obs": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),
+    "mzgo_replay_window_obs_items": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "mzgo_encode_workspace": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
+    "mzgo_encode": (_I, [_P] * 4 + [_I] + [_P] + [_I] * 4 + [_P, _P, ctypes.c_int64, _P]),
+    "mzgo_consistency_loss_workspace": (_I, [_I] * 5 + [ctypes.POINTER(ctypes.c_int64)]),
+    "mzgo_consistency_loss": (_I, [_P] * 7 + [_I] * 5 + [ctypes.c_float] + [_P] * 3 + [ctypes.c_int64, _P]),
+    "mzgo_consistency_loss_backward": (_I, [_P] * 5 + [_I] * 5 + [ctypes.c_float] + [_P] * 6 + [ctypes.c_int64, _P]),
+    "mzgo_consistency_loss_host": (_I, [_P] * 8 + [_I] * 5 + [ctypes.c_float] + [_P] * 7),
     "mzgo_optim_chunk": (_I, []),
     "mzgo_optim_create": (_I, [_I, _P, _I, ctypes.POINTER(_P)]),
     "mzgo_optim_destroy": (None, [_P]),

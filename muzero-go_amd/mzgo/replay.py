@@ -545,6 +545,47 @@ class DeviceReplay:
         K1 = max(K, 0) + 1
         return (torch.empty(B, K1, self.N * self.N, device=self.device), torch.empty(B, K1, device=self.device))
 
+    # ---- the real boards of a window (the consistency loss's targets) ----
+    def window_obs(self, indices, starts, unroll_steps, symmetries=None):
+        """The real boards of B sampled windows in one launch
+        (mzgo_replay_window_obs; ``batch``'s indices, starts and symmetries):
+        ``(obs f32 [K, B, 6, N, N], mask f32 [B, K])`` on the device.
+        ``obs[k-1, b]`` is the observation of position start + k of sample b's
+        game under the sample's symmetry, k = 1..K -- the six planes ``batch``
+        writes as ``obs0`` for that position -- step-major, so that
+        ``obs.view(K * B, 6, N, N)`` goes to ``mzgo.encode`` without a copy and
+        lines up with the unroll's ``latents[1:]``.  ``mask[b, k-1]`` is 1 where
+        start + k <= the game's length (the final board counts); past it the
+        planes are zeros and the mask 0.  At K = 0: empty tensors, no launch."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int32).reshape(-1))
+        B, K = len(idx), int(unroll_steps)
+        st = np.ascontiguousarray(np.asarray(starts, dtype=np.int32).reshape(-1))
+        sy = None if symmetries is None else np.ascontiguousarray(np.asarray(symmetries, dtype=np.int32).reshape(-1))
+        if len(st) != B or (sy is not None and len(sy) != B):
+            raise ValueError("window_obs: indices, starts and symmetries must have one entry per sample")
+        obs, mask = self._window_obs_out(B, K)
+        if K > 0:
+            check(lib.mzgo_replay_window_obs(self._h, ptr(idx), ptr(st), ptr(sy), B, K, ptr(obs), ptr(mask),
+                                             stream_of(self.device)))
+        return obs, mask
+
+    def window_obs_from(self, sample, unroll_steps):
+        """``window_obs`` for a drawn ``sample`` (what ``sample`` / ``sample_batch``
+        returned, or its ``items`` tensor), from the device items
+        (mzgo_replay_window_obs_items): nothing crosses the bus, nothing
+        synchronises."""
+        items = self._items_of(sample)
+        B, K = items.shape[0], int(unroll_steps)
+        obs, mask = self._window_obs_out(B, K)
+        if K > 0:
+            check(lib.mzgo_replay_window_obs_items(self._h, ptr(items), B, K, ptr(obs), ptr(mask),
+                                                   stream_of(self.device)))
+        return obs, mask
+
+    def _window_obs_out(self, B, K):
+        K = max(K, 0)
+        return (torch.empty(K, B, 6, self.N, self.N, device=self.device), torch.empty(B, K, device=self.device))
+
     # ---- the device ledger and sampler ----
     # Independent of ``ledger`` above: the host ledger (``priorities``,
     # ``sample_indices``, ``update_priorities``) is main.py's np.random path and

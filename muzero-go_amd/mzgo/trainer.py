@@ -130,6 +130,21 @@ on the device, every game of a batch at once) and trains on it:
   ``training_loss`` and the three totals keep their meaning (without
   ownership); ``last["ownership_loss"]`` reports the ownership total.
 
+  ``TrainConfig.consistency_loss_weight`` (default 0 = off; the ownership
+  option's requirements, and ``unroll_steps`` >= 1) trains EfficientZero's
+  temporal consistency loss on the same latents: ``s_k`` is pulled towards
+  the representation's latent of the real board at start + k, through a head
+  of two 1x1 convs of its own (``mzgo.ConsistencyHead``,
+  ``trainer.consistency_head``, ``consistency_proj_dim`` wide; four parameters
+  next to the net's 22) and with no gradient on the target side.  The store
+  gives the windows' real boards for the step's items
+  (``DeviceReplay.window_obs`` / ``window_obs_from``, one small launch),
+  ``mzgo.encode`` their latents under the current weights (three launches),
+  ``mzgo.consistency_loss`` the per-sample losses, added to ``per`` under the
+  same importance weights.  It runs together with the ownership option: both
+  gradients arrive on the one ``latents`` output.  ``last["consistency_loss"]``
+  reports its total; the other totals keep their meaning.
+
 ``initial_inference_torch`` / ``recurrent_inference_torch`` restate
 main.py:72-144 with torch ops on the module's own parameters (reference
 mode, and the CPU).  Replay buffers restate main.py:158-244.
@@ -180,6 +195,8 @@ class TrainConfig:
     position_priorities: bool = False  # device_sampling: sample positions by |value - target| (MuZero, App. G)
     priority_floor: float = 0.0       # position_priorities: the smallest value error a weight is formed from; 0 = FLT_MIN
     ownership_loss_weight: float = 0.0  # > 0: the ownership head's loss on the fused unroll's latents (DeviceReplay)
+    consistency_loss_weight: float = 0.0  # > 0: the latent consistency loss on the fused unroll's latents (DeviceReplay)
+    consistency_proj_dim: int = 32    # consistency_loss_weight: the head's projection width (16, 32, 48 or 64)
 
 
 def reward_value_transform(x, epsilon=0.001):
@@ -530,7 +547,7 @@ class MuZeroTrainer:
     trained on, under either ``value_target``; held until the next step)."""
 
     def __init__(self, net: MuZeroNet, config: TrainConfig = None, mode="reference", start_index=None,
-                 hip_forward=None, sample_seed=0, reanalyser=None, ownership_head=None):
+                 hip_forward=None, sample_seed=0, reanalyser=None, ownership_head=None, consistency_head=None):
         if mode not in ("reference", "batched"):
             raise ValueError(f"mode must be 'reference' or 'batched', not {mode!r}")
         self.net = net
@@ -589,6 +606,44 @@ class MuZeroTrainer:
         # the ownership head (None: off): a module of its own -- the net keeps the reference's 22 tensors, and the
         # engines, the weight packers and the search never see the head; its two parameters join the optimizer's
         self.ownership_head = ownership_head
+        if not (0.0 <= c.consistency_loss_weight < float("inf")):
+            raise ValueError(f"consistency_loss_weight must be finite and >= 0 (0 = off), got "
+                             f"{c.consistency_loss_weight}")
+        if c.consistency_loss_weight > 0:
+            if mode != "batched":
+                raise ValueError("consistency_loss_weight needs mode='batched' with fused_unroll and fused_loss: "
+                                 "mode='reference' is main.py's per-trajectory step, which has no consistency head")
+            if not c.fused_unroll:
+                raise ValueError("consistency_loss_weight needs fused_unroll=True: the consistency head reads the "
+                                 "latents mzgo.unroll returns (return_latents=True)")
+            if not c.fused_loss:
+                raise ValueError("consistency_loss_weight needs fused_loss=True: the consistency loss joins the "
+                                 "per-sample losses of mzgo.unroll_loss")
+            if int(c.unroll_steps) < 1:
+                raise ValueError(f"consistency_loss_weight needs unroll_steps >= 1 (the loss is on the latents of "
+                                 f"steps 1..K), got {c.unroll_steps}")
+            from .consistency import MAX_LATENT_DIM, ConsistencyHead
+            if net.latent_dim > MAX_LATENT_DIM:
+                raise ValueError(f"consistency_loss_weight needs latent_dim <= {MAX_LATENT_DIM} (the kernels stage "
+                                 f"the projection's weights in LDS), got {net.latent_dim}")
+            if consistency_head is not None and (not isinstance(consistency_head, ConsistencyHead)
+                                                 or consistency_head.latent_dim != net.latent_dim):
+                raise ValueError(f"consistency_head must be a ConsistencyHead({net.latent_dim}, proj_dim) (the net's "
+                                 "latent_dim)")
+            if next(net.parameters()).device.type != "cuda":
+                raise ValueError("consistency_loss_weight needs the net on the GPU (net.to('cuda')): "
+                                 "mzgo.consistency_loss has no eager fall-back")
+            if consistency_head is None:       # (a proj_dim outside 16, 32, 48, 64 is the head's ValueError)
+                consistency_head = ConsistencyHead(net.latent_dim, c.consistency_proj_dim).to(
+                    next(net.parameters()).device)
+            if consistency_head.proj.weight.device != next(net.parameters()).device:
+                raise ValueError("consistency_head must be on the net's device")
+        elif consistency_head is not None or c.consistency_proj_dim != 32:
+            raise ValueError("consistency_head and consistency_proj_dim belong to consistency_loss_weight > 0 "
+                             "(TrainConfig.consistency_loss_weight)")
+        # the consistency head (None: off): a module of its own like the ownership head; its four parameters join
+        # the optimizer's
+        self.consistency_head = consistency_head
         if c.unroll_precision not in ("fp32", "bf16"):
             raise ValueError(f"unroll_precision must be 'fp32' or 'bf16', not {c.unroll_precision!r}")
         if c.unroll_precision == "bf16":
@@ -682,10 +737,13 @@ class MuZeroTrainer:
         return next(self.net.parameters()).device
 
     def _parameters(self):
-        """What the optimizer steps and one clip norm covers: the net's 22 tensors, then the ownership head's two."""
+        """What the optimizer steps and one clip norm covers: the net's 22 tensors, then the ownership head's two
+        and the consistency head's four."""
         params = list(self.net.parameters())
         if self.ownership_head is not None:
             params += list(self.ownership_head.parameters())
+        if self.consistency_head is not None:
+            params += list(self.consistency_head.parameters())
         return params
 
     # -- targets ------------------------------------------------------------
@@ -763,6 +821,9 @@ class MuZeroTrainer:
         if self.ownership_head is not None:
             raise ValueError("ownership_loss_weight needs a DeviceReplay: the ownership targets come from the final "
                              "boards the store keeps (host trajectories are out of scope)")
+        if self.consistency_head is not None:
+            raise ValueError("consistency_loss_weight needs a DeviceReplay: the targets are the real boards the store "
+                             "keeps for the window (host trajectories are out of scope)")
         batch, indices = replay_buffer.sample(batch_size)
         if not batch or len(batch) < batch_size:
             return None
@@ -868,7 +929,10 @@ class MuZeroTrainer:
         syms = [self.symmetry_index() for _ in indices] if self.config.symmetries else None
         own = (replay.ownership(indices, starts, self.config.unroll_steps, syms)
                if self.ownership_head is not None else None)
-        avg = self._unroll_step(*self.device_targets(replay, indices, starts, syms), device_totals=True, ownership=own)
+        cons = (replay.window_obs(indices, starts, self.config.unroll_steps, syms)
+                if self.consistency_head is not None else None)
+        avg = self._unroll_step(*self.device_targets(replay, indices, starts, syms), device_totals=True, ownership=own,
+                                consistency=cons)
         replay.update_priorities(indices, self._priorities(avg, len(indices)))
         self._scheduler_step()
         return avg
@@ -927,18 +991,21 @@ class MuZeroTrainer:
         self.last_t_val_device = t_val
         # the ownership targets of the same items: one more small launch, nothing on the host
         own = replay.ownership_from(s, c.unroll_steps) if self.ownership_head is not None else None
+        # the real boards of the same items' windows (the consistency loss's targets): one more small launch
+        cons = replay.window_obs_from(s, c.unroll_steps) if self.consistency_head is not None else None
         avg = self._unroll_step(s["obs0"], s["acts"], t_val, s["t_rew"], s["t_pol"], device_totals=True,
-                                device_sample=(replay, s), ownership=own)
+                                device_sample=(replay, s), ownership=own, consistency=cons)
         self._scheduler_step()
         return avg
 
-    def _finish_device(self, device_sample, per, totals, B, lr, value=None, t_val=None, own_total=None):
+    def _finish_device(self, device_sample, per, totals, B, lr, value=None, t_val=None, own_total=None,
+                       cons_total=None):
         """The tail of a device-sampled step: the priorities from ``per`` (f32
         [B], unweighted) or the batch mean -- with ``position_priorities`` the
         sampled windows' position weights from ``value`` and ``t_val`` (f32
         [B, K+1]: the raw value outputs and targets) instead -- and the totals
-        (f64 [4], unweighted; ``own_total`` f64 [1]: the ownership loss's, apart) left on the device for
-        ``read_stats``."""
+        (f64 [4], unweighted; ``own_total`` and ``cons_total`` f64 [1]: the ownership and the consistency
+        loss's, apart) left on the device for ``read_stats``."""
         replay, sample = device_sample
         c = self.config
         if c.position_priorities:
@@ -949,7 +1016,7 @@ class MuZeroTrainer:
             replay.update_device_priorities(sample, alpha=c.priority_alpha, mean=totals[:1] / B)
         self.last_per_sample = None
         self.last_per_sample_device = per if c.sample_priorities else None
-        self._pending = (totals, B, lr, own_total)
+        self._pending = (totals, B, lr, own_total, cons_total)
         if c.deferred_stats:
             self.last = {}
             return totals[0] / B
@@ -959,15 +1026,18 @@ class MuZeroTrainer:
         """``last`` of the latest step; with ``deferred_stats`` this is where the
         totals are copied from the device (one synchronising copy)."""
         if self._pending is not None:
-            totals, B, lr, own_total = self._pending
+            totals, B, lr, own_total, cons_total = self._pending
             self._pending = None
-            if own_total is not None:                   # (still one copy)
-                totals = torch.cat([totals, own_total])
-            total, tot_v, tot_p, tot_r, *own = totals.tolist()
+            aux = [t for t in (own_total, cons_total) if t is not None]
+            if aux:                                     # (still one copy)
+                totals = torch.cat([totals, *aux])
+            total, tot_v, tot_p, tot_r, *aux = totals.tolist()
             self.last = dict(training_loss=total / B, value_loss=tot_v / B, policy_loss=tot_p / B,
                              reward_loss=tot_r / B, lr=lr)
-            if own:
-                self.last["ownership_loss"] = own[0] / B
+            if own_total is not None:
+                self.last["ownership_loss"] = aux.pop(0) / B
+            if cons_total is not None:
+                self.last["consistency_loss"] = aux.pop(0) / B
         return self.last
 
     def device_targets(self, replay, indices, starts, symmetries=None):
@@ -1049,7 +1119,8 @@ class MuZeroTrainer:
         obs0 = np.stack([np.asarray(tr["observations"][s]) for tr, s in zip(batch, starts)])
         return obs0, acts, t_val, t_rew, t_pol
 
-    def _unroll_step(self, obs0, acts, t_val, t_rew, t_pol, device_totals=False, device_sample=None, ownership=None):
+    def _unroll_step(self, obs0, acts, t_val, t_rew, t_pol, device_totals=False, device_sample=None, ownership=None,
+                     consistency=None):
         """One optimizer step on the summed losses of B samples unrolled K
         steps, from targets on the device (obs0 f32 [B,6,N,N], acts i64 [B,K],
         t_val f32 [B,K+1], t_rew f32 [B,K], t_pol f32 [B,K+1,A]); returns the
@@ -1067,7 +1138,7 @@ class MuZeroTrainer:
         c, net = self.config, self.net
         B, K = acts.shape
         if c.fused_loss:
-            return self._unroll_step_fused(obs0, acts, t_val, t_rew, t_pol, device_sample, ownership)
+            return self._unroll_step_fused(obs0, acts, t_val, t_rew, t_pol, device_sample, ownership, consistency)
         tot = (lambda x: x.detach().sum().double()) if device_totals else (lambda x: x.sum().item())
         self.optimizer.zero_grad()
         steps = self._head_outputs(obs0, acts)
@@ -1140,7 +1211,8 @@ class MuZeroTrainer:
         priorities and the reported totals stay unweighted)."""
         return device_sample is not None and self.config.importance_beta > 0
 
-    def _unroll_step_fused(self, obs0, acts, t_val, t_rew, t_pol, device_sample=None, ownership=None):
+    def _unroll_step_fused(self, obs0, acts, t_val, t_rew, t_pol, device_sample=None, ownership=None,
+                           consistency=None):
         """``_unroll_step`` with the loss on the HIP kernel: the K + 1 steps'
         head outputs are collected and stacked once (``fused_unroll``:
         they come stacked from ``mzgo.unroll``), ``mzgo.unroll_loss`` gives
@@ -1154,18 +1226,36 @@ class MuZeroTrainer:
         under the same importance weights, and the gradient that reaches the
         latents goes back into the unroll's backward.  The priorities,
         ``training_loss`` and the three totals stay those of ``per`` without
-        ownership; the ownership total is ``last["ownership_loss"]``."""
+        ownership; the ownership total is ``last["ownership_loss"]``.
+
+        With ``consistency`` = (obs, mask) (``consistency_loss_weight`` > 0:
+        the real boards of the windows' steps 1..K, ``DeviceReplay.window_obs``)
+        ``mzgo.encode`` gives the boards' latents under the current weights,
+        and ``mzgo.consistency_loss`` on the unroll's latents joins ``per`` in
+        the same way; its total is ``last["consistency_loss"]``.  Both
+        auxiliary losses hang on the one ``latents`` output: autograd adds
+        their gradients before the unroll's backward."""
         from .loss import unroll_loss
         c, net = self.config, self.net
         B, K = acts.shape
         self.optimizer.zero_grad()
-        per_own = own_total = None
-        if ownership is not None:
-            from .ownership import ownership_loss
+        per_own = own_total = per_cons = cons_total = None
+        if ownership is not None or consistency is not None:
             from .unroll import unroll
+            if consistency is not None:
+                from .consistency import consistency_loss
+                from .unroll import encode
+                obs_k, cons_mask = consistency
+                N = net.board_size
+                targets = encode(net, obs_k.view(K * B, 6, N, N)).view(K, B, net.latent_dim, N, N)
             lgs, vals, rews, latents = unroll(net, obs0, acts, c.unroll_precision, return_latents=True)
-            per_own, own_total = ownership_loss(latents, self.ownership_head, *ownership,
-                                                weight=c.ownership_loss_weight)
+            if ownership is not None:
+                from .ownership import ownership_loss
+                per_own, own_total = ownership_loss(latents, self.ownership_head, *ownership,
+                                                    weight=c.ownership_loss_weight)
+            if consistency is not None:
+                per_cons, cons_total = consistency_loss(latents, targets, cons_mask, self.consistency_head,
+                                                        weight=c.consistency_loss_weight)
         elif c.fused_unroll:
             from .unroll import unroll
             lgs, vals, rews = unroll(net, obs0, acts, c.unroll_precision)   # stacked as they come
@@ -1181,15 +1271,18 @@ class MuZeroTrainer:
                                   policy_loss_weight=c.policy_loss_weight, reward_loss_weight=c.reward_loss_weight,
                                   value_transform=c.use_value_transform)
         trained = per if per_own is None else per + per_own
+        if per_cons is not None:
+            trained = trained + per_cons
         loss = trained.sum() if not self._weighted(device_sample) else (trained * device_sample[1]["weight"]).sum()
         loss.backward()
         lr = self._optimizer_step()
         self.last_per_sample = None
         if device_sample is not None:
             value = vals.detach().t().contiguous() if c.position_priorities else None    # [K+1, B] -> [B, K+1]
-            return self._finish_device(device_sample, per.detach(), totals, B, lr, value, t_val, own_total)
-        if own_total is not None:                       # (still one copy; the per-sample losses follow from index 5)
-            totals = torch.cat([totals, own_total])
+            return self._finish_device(device_sample, per.detach(), totals, B, lr, value, t_val, own_total, cons_total)
+        aux = [t for t in (own_total, cons_total) if t is not None]
+        if aux:                                         # (still one copy; the per-sample losses follow the totals)
+            totals = torch.cat([totals, *aux])
         n = totals.numel()
         if c.sample_priorities:
             back = torch.cat([totals, per.detach().double()]).tolist()
@@ -1201,4 +1294,6 @@ class MuZeroTrainer:
                          reward_loss=tot_r / B, lr=lr)
         if own_total is not None:
             self.last["ownership_loss"] = back[4] / B
+        if cons_total is not None:
+            self.last["consistency_loss"] = back[n - 1] / B
         return total / B

@@ -8,7 +8,9 @@ unroll step with their autograd nodes.
 ``unroll`` is differentiable in the net's 22 parameters only (there is no
 observation gradient); with ``return_latents`` it also returns the K + 1
 latents and takes a gradient with respect to them, which is how an auxiliary
-loss (``mzgo.ownership``) attaches to the fused step; ``unroll_heads_host``
+loss (``mzgo.ownership``, ``mzgo.consistency``) attaches to the fused step;
+``encode`` is the representation alone, without a gradient (the consistency
+loss's targets); ``unroll_heads_host``
 runs the heads' scalar functions serially on host arrays (the formulas' CPU
 check).
 """
@@ -245,6 +247,56 @@ def unroll(net, obs0, acts, precision="fp32", return_latents=False):
                         *params)
     heads = (out[0], out[1], out[2] if K > 0 else None)
     return heads + (out[-1],) if return_latents else heads
+
+
+_encode_work = {}    # (B, C, N) -> mzgo_encode_workspace bytes
+
+
+def encode(net, obs):
+    """The representation alone: ``obs`` f32 [B', 6, N, N] -> latents f32 [B',
+    C, N, N] by the fused unroll's three representation convs
+    (``mzgo_encode``): the bits of ``unroll(net, obs, None,
+    return_latents=True)``'s latents, without the heads and the saved buffer
+    that call carries.  Not differentiable: the result never requires grad,
+    whatever the grad mode (the consistency loss's targets carry no gradient).
+    Any B' >= 1 (past the convs' grid limit of 65535 boards the call runs them
+    in chunks).  ``unroll``'s checks: a ``MuZeroNet`` on the GPU, ``latent_dim``
+    a multiple of 16.  Stream-ordered; device tensors only."""
+    from .resnet import ResMuZeroNet
+    if isinstance(net, ResMuZeroNet):
+        raise TypeError("mzgo.encode runs the reference network (MuZeroNet) only: ResMuZeroNet's residual tower has "
+                        "no fused unroll kernels")
+    if not isinstance(net, MuZeroNet):
+        raise TypeError(f"mzgo.encode needs a MuZeroNet, got {type(net).__name__}")
+    params = list(net.parameters())
+    dev = params[0].device
+    if dev.type != "cuda":
+        raise ValueError("mzgo.encode runs on the GPU: call net.to('cuda') first")
+    N, C = net.board_size, net.latent_dim
+    if C < 16 or C % 16:
+        raise ValueError(f"mzgo.encode needs latent_dim to be a multiple of 16, got {C}")
+    if not isinstance(obs, torch.Tensor) or obs.device != dev:
+        raise ValueError(f"mzgo.encode: obs must be a tensor on {dev} (the net's device)")
+    if obs.ndim != 4 or tuple(obs.shape[1:]) != (6, N, N) or obs.shape[0] < 1:
+        raise ValueError(f"obs must be [B >= 1, 6, {N}, {N}], got {tuple(obs.shape)}")
+    for k, p in net.named_parameters():
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise ValueError(f"mzgo.encode: parameter '{k}' must be contiguous float32")
+    B = obs.shape[0]
+    if (B, C, N) not in _encode_work:
+        n = ctypes.c_int64()
+        check(lib.mzgo_encode_workspace(B, C, N, ctypes.byref(n)))
+        _encode_work[(B, C, N)] = n.value
+    nbytes = _encode_work[(B, C, N)]
+    table, _ = _net_table(net)
+    obs = obs.detach().to(torch.float32).contiguous()
+    latents = torch.empty(B, C, N, N, device=dev)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.mzgo_encode(table.keys, table.pointers([p.detach() for p in params]), table.shapes, table.ndims,
+                              table.n, ptr(obs), B, C, N, net.max_action_size, ptr(latents), ptr(work), nbytes,
+                              stream_of(dev)))
+    return latents
 
 
 def unroll_heads_host(params, latents, g_logits, g_value, g_reward):
