@@ -522,10 +522,24 @@ int mzgo_replay_add(mzgo_replay* replay, int length, const int8_t* stones_host, 
 int mzgo_replay_export(mzgo_replay* replay, int i, int32_t* length_host, int32_t* key_gid_host, int8_t* stones_host,
                        uint8_t* invd_host, uint8_t* flags_host, int32_t* action_host, double* policy_host,
                        double* reward_host, double* root_value_host, void* stream);
+/* The item list of B samples given on the HOST: sample b is logical game
+ * indices_host[b] from move starts_host[b] under symmetry symmetries_host[b]
+ * (0..7; NULL = identity).  The triples are checked against the host mirror and
+ * written as (slot, start, symmetry) through pinned staging words into
+ * ``items`` (device i32 [B][3]), the form every assembly below takes and the
+ * samplers write: one check and one upload serve any number of assemblies of
+ * the same samples.  The call waits until the staging words' previous upload
+ * has been read; it does not wait for this one.
+ * MZGO_EINVAL: null replay, indices, starts or items; B < 1; an index outside
+ * 0..size-1; a start outside 0..L-1 of its game; a symmetry outside 0..7. */
+int mzgo_replay_items(mzgo_replay* replay, const int32_t* indices_host, const int32_t* starts_host,
+                      const int32_t* symmetries_host, int B, int32_t* items, void* stream);
 /* Batch assembly, one launch (k_replay_batch, a workgroup per sample): the
  * trainer's targets (mzgo.trainer batch_targets; main.py:395-470, :503-515)
- * for B samples (logical game, start move, symmetry) given on the HOST, with
- * K = unroll_steps.  Device outputs:
+ * for the B samples of a device item list (i32 [B][3]: slot, start, symmetry,
+ * as mzgo_replay_items or a sampler wrote them), with K = unroll_steps, so that
+ * a reanalysis of the sampled windows can run between the draw and the
+ * assembly.  Device outputs:
  *   obs0 f32 [B][6][N][N]          the observation at ``start``
  *   boot_obs f32 [B][K+1][6][N][N] the observation at start+k+K where the value
  *                                  target of unroll step k has a bootstrap
@@ -542,20 +556,21 @@ int mzgo_replay_export(mzgo_replay* replay, int i, int32_t* length_host, int32_t
  *                                  factor *= discount, in that order in f64,
  *                                  stopping at the rewards' end
  *   has_boot u8 [B][K+1]
- * Symmetry s (0..7; symmetries_host NULL = identity) gives the sample as if
- * its whole trajectory had been transformed: every plane and the first N*N
- * policy entries as [N][N] become np.rot90(x, s & 3), then np.flip(axis=-1)
- * if s & 4; an action below N*N moves where its one-hot would; the pass entry
- * and the pass action stay.
+ * Symmetry s gives the sample as if its whole trajectory had been transformed:
+ * every plane and the first N*N policy entries as [N][N] become np.rot90(x,
+ * s & 3), then np.flip(axis=-1) if s & 4; an action below N*N moves where its
+ * one-hot would; the pass entry and the pass action stay.
  * The value targets are finished with mzgo_initial_inference over boot_obs's
  * B*(K+1) rows and mzgo_replay_finish_values.
- * MZGO_EINVAL: null replay or any required pointer; B < 1; unroll_steps
- * outside 1..63; an index outside 0..size-1; a start outside 0..L-1 of its
- * game; a symmetry outside 0..7. */
-int mzgo_replay_batch(mzgo_replay* replay, const int32_t* indices_host, const int32_t* starts_host,
-                      const int32_t* symmetries_host, int B, int unroll_steps, double discount, float* obs0,
-                      float* boot_obs, int64_t* acts, float* t_rew, float* t_pol, double* val, double* factor,
-                      uint8_t* has_boot, void* stream);
+ * The items are not checked against the host mirror, and the kernel reads no
+ * row outside the store whatever they hold: a slot outside 0..capacity-1 gives
+ * an empty game's outputs (zero planes, pass actions, rewards 0, uniform policy
+ * rows, val 0, factor 1, has_boot 0), and so does every row before a game's
+ * first.  No host staging, no synchronisation.  MZGO_EINVAL: null replay, items
+ * or outputs; B < 1; unroll_steps outside 1..63. */
+int mzgo_replay_batch_items(mzgo_replay* replay, const int32_t* items, int B, int unroll_steps, double discount,
+                            float* obs0, float* boot_obs, int64_t* acts, float* t_rew, float* t_pol, double* val,
+                            double* factor, uint8_t* has_boot, void* stream);
 /* t_val[i] = (float)(val[i] + factor[i] * (double)value[i]) where has_boot[i],
  * (float)val[i] elsewhere, for n entries (device pointers; value f32 [n]: the
  * network's values of the boot_obs rows).  MZGO_EINVAL: a null pointer; n < 1. */
@@ -615,23 +630,6 @@ int mzgo_replay_symmetry_table(int board_size, int symmetry, int32_t* src_host, 
  * negative or not finite. */
 int mzgo_replay_sample(mzgo_replay* replay, int B, uint64_t seed, uint32_t step, int symmetries, double beta,
                        int32_t* items, int32_t* index, uint32_t* gen, float* weight, void* stream);
-/* mzgo_replay_sample, then k_replay_batch on the sampler's device items: the
- * eight output tensors of mzgo_replay_batch for the sampled (game, start,
- * symmetry) triples.  No host staging, no synchronisation.  MZGO_EINVAL as
- * mzgo_replay_sample, plus unroll_steps outside 1..63 and null outputs. */
-int mzgo_replay_sample_batch(mzgo_replay* replay, int B, int unroll_steps, double discount, uint64_t seed,
-                             uint32_t step, int symmetries, double beta, int32_t* items, int32_t* index,
-                             uint32_t* gen, float* weight, float* obs0, float* boot_obs, int64_t* acts, float* t_rew,
-                             float* t_pol, double* val, double* factor, uint8_t* has_boot, void* stream);
-/* k_replay_batch on device items the caller holds (i32 [B][3]: slot, start,
- * symmetry, as mzgo_replay_sample wrote them): the second half of
- * mzgo_replay_sample_batch, so that a reanalysis of the sampled windows can
- * run between the draw and the assembly.  The items are not checked (they
- * are the sampler's).  No host staging, no synchronisation.  MZGO_EINVAL:
- * null replay, items or outputs; B < 1; unroll_steps outside 1..63. */
-int mzgo_replay_batch_items(mzgo_replay* replay, const int32_t* items, int B, int unroll_steps, double discount,
-                            float* obs0, float* boot_obs, int64_t* acts, float* t_rew, float* t_pol, double* val,
-                            double* factor, uint8_t* has_boot, void* stream);
 /* Reanalysis of a sampled batch's windows, in place and without the host.  A
  * sample (slot, start, symmetry) with K = unroll_steps on a game of L moves
  * reads the stored policy rows t = start .. min(start + K, L - 1) (rows past
@@ -676,29 +674,21 @@ int mzgo_replay_window_items_host(const int32_t* length, int cap, const int32_t*
  * function, search_value_target in csrc/mzgo_replay.hpp, which the kernel and
  * the host twin both run).  The i + n == L case is deliberate: the final board
  * is never searched, so nothing is stored for it, and r[L] is the exact
- * remainder of the return from there; network targets (mzgo_replay_batch)
+ * remainder of the return from there; network targets (mzgo_replay_batch_items)
  * evaluate the final board at that index instead, so the two kinds of target
  * differ there even when nu holds the network's values.  td_steps is
  * independent of unroll_steps.
  *
- * mzgo_replay_batch_values / _batch_items_values / _sample_batch_values are
- * mzgo_replay_batch / _batch_items / _sample_batch with one launch of
- * k_replay_batch<true>: obs0, acts, t_rew and t_pol as those write them (the
+ * mzgo_replay_batch_items_values is mzgo_replay_batch_items with one launch of
+ * k_replay_batch<true>: obs0, acts, t_rew and t_pol as that writes them (the
  * same symmetry gather), and t_val f32 [B][K+1], entry k the target of index
- * start + k; no boot_obs, val, factor or has_boot, and nothing to finish.
- * The same promises on staging and synchronisation as their counterparts.
- * MZGO_EINVAL as for the counterparts (for the five outputs they take), plus
- * td_steps < 1. */
-int mzgo_replay_batch_values(mzgo_replay* replay, const int32_t* indices_host, const int32_t* starts_host,
-                             const int32_t* symmetries_host, int B, int unroll_steps, int td_steps, double discount,
-                             float* obs0, int64_t* acts, float* t_rew, float* t_pol, float* t_val, void* stream);
+ * start + k (0 where mzgo_replay_batch_items gives an empty game's outputs); no
+ * boot_obs, val, factor or has_boot, and nothing to finish.  The same promises
+ * on staging and synchronisation.  MZGO_EINVAL as mzgo_replay_batch_items (for
+ * the five outputs it takes), plus td_steps < 1. */
 int mzgo_replay_batch_items_values(mzgo_replay* replay, const int32_t* items, int B, int unroll_steps, int td_steps,
                                    double discount, float* obs0, int64_t* acts, float* t_rew, float* t_pol,
                                    float* t_val, void* stream);
-int mzgo_replay_sample_batch_values(mzgo_replay* replay, int B, int unroll_steps, int td_steps, double discount,
-                                    uint64_t seed, uint32_t step, int symmetries, double beta, int32_t* items,
-                                    int32_t* index, uint32_t* gen, float* weight, float* obs0, int64_t* acts,
-                                    float* t_rew, float* t_pol, float* t_val, void* stream);
 /* mzgo_replay_reanalyse_sample over every stored row a search-value batch
  * reads: a sample's window t = start .. min(start + K, L - 1) (its policy
  * rows) together with its value rows t = start + n .. min(start + K + n, L - 1),
@@ -794,22 +784,10 @@ int mzgo_replay_enable_positions(mzgo_replay* replay, int td_steps, double disco
  * batch's largest, w the picked position's weight, total the sum before any
  * removal.  The items feed mzgo_replay_batch_items, _batch_items_values and
  * mzgo_replay_reanalyse_sample(_values) unchanged.  MZGO_EINVAL as
- * mzgo_replay_sample.  The _batch and _batch_values forms mirror
- * mzgo_replay_sample_batch and mzgo_replay_sample_batch_values launch for
- * launch (build, draw, the unchanged k_replay_batch). */
+ * mzgo_replay_sample. */
 int mzgo_replay_sample_positions(mzgo_replay* replay, int B, uint64_t seed, uint32_t step, int symmetries,
                                  double beta, int32_t* items, int32_t* index, uint32_t* gen, float* weight,
                                  void* stream);
-int mzgo_replay_sample_positions_batch(mzgo_replay* replay, int B, int unroll_steps, double discount, uint64_t seed,
-                                       uint32_t step, int symmetries, double beta, int32_t* items, int32_t* index,
-                                       uint32_t* gen, float* weight, float* obs0, float* boot_obs, int64_t* acts,
-                                       float* t_rew, float* t_pol, double* val, double* factor, uint8_t* has_boot,
-                                       void* stream);
-int mzgo_replay_sample_positions_batch_values(mzgo_replay* replay, int B, int unroll_steps, int td_steps,
-                                              double discount, uint64_t seed, uint32_t step, int symmetries,
-                                              double beta, int32_t* items, int32_t* index, uint32_t* gen,
-                                              float* weight, float* obs0, int64_t* acts, float* t_rew, float* t_pol,
-                                              float* t_val, void* stream);
 /* New weights for a sampled batch's windows (k_replay_update_position_priorities,
  * a thread per (sample b, unroll step k); device pointers; no synchronisation):
  * position t = items[b][1] + k of slot items[b][0] gets the weight of err =
@@ -855,7 +833,7 @@ int mzgo_replay_position_priorities_host(const double* reward, const double* roo
  *   logits [K+1][B][A], value [K+1][B], reward [K][B]   the heads' outputs,
  *                              step-major (the unroll's outputs stacked)
  *   t_pol [B][K+1][A], t_val [B][K+1], t_rew [B][K]     the targets,
- *                              sample-major (mzgo_replay_batch's layout)
+ *                              sample-major (mzgo_replay_batch_items' layout)
  * Per row (b, k), with m = max_a logits, s = sum_a exp(logits - m),
  * logp = logits - m - log s, p = exp(logits - m) / s and T = sum_a t_pol:
  *   policy  w_policy * sum_a (xlogy(t, t) - t logp_a); an entry t == 0 adds
@@ -922,7 +900,7 @@ int mzgo_unroll_loss_host(const float* logits, const float* value, const float* 
  * latents' gradients, the conv weight partials, the heads' partial sums).
  *
  * mzgo_unroll_forward: obs0 [B][6][N][N], acts i64 [B][K] (the action taken
- * before step k, sample-major as mzgo_replay_batch returns them; values
+ * before step k, sample-major as mzgo_replay_batch_items returns them; values
  * 0 <= a < emb_rows are the caller's contract, as in mzgo_dyn_conv_backward).
  *   latent_0 = representation(obs0); latent_k = relu(conv(latent_{k-1} +
  *   emb[acts[:, k-1]]) + bias)
@@ -1091,18 +1069,13 @@ int mzgo_unroll_backward_l(const char* const* keys, const float* const* params, 
  *                        of row L's flags: the condition under which reward[L]
  *                        is the winner), else 0 with an all-zero row -- a game
  *                        cut off by the move cap has no ownership target
- * mzgo_replay_ownership takes host indices, starts and symmetries (NULL:
- * identity) as mzgo_replay_batch does, with its checks;
- * mzgo_replay_ownership_items takes the sampler's DEVICE items [B][3]: nothing
- * crosses the bus and nothing synchronises.  One launch, a workgroup per
- * sample, next to the batch assembly (which is unchanged).  unroll_steps in
+ * mzgo_replay_ownership_items takes DEVICE items [B][3] (mzgo_replay_items' or
+ * a sampler's): nothing crosses the bus and nothing synchronises.  One launch,
+ * a workgroup per sample, next to the batch assembly.  unroll_steps in
  * 0..63.  mzgo_ownership_host is the owner map alone on HOST arrays (stones
  * int8 [N*N] -> owner int8 [N*N]: 0, 1, 2) and mzgo_ownership_targets_host one
  * sample's rows from the final board's stones and the game's flags [L + 1]:
  * the kernel's own functions (csrc/mzgo_replay.hpp), no device work. */
-int mzgo_replay_ownership(mzgo_replay* replay, const int32_t* indices_host, const int32_t* starts_host,
-                          const int32_t* symmetries_host, int B, int unroll_steps, float* t_own, float* own_mask,
-                          void* stream);
 int mzgo_replay_ownership_items(mzgo_replay* replay, const int32_t* items, int B, int unroll_steps, float* t_own,
                                 float* own_mask, void* stream);
 int mzgo_ownership_host(const int8_t* stones, int board_size, int8_t* owner);
@@ -1146,23 +1119,19 @@ int mzgo_ownership_loss_host(const float* latents, const float* w, const float* 
  * at start + k, through a head of two 1x1 convs of its own, proj (C -> P) and
  * pred (P -> P).  The target side carries no gradient.
  *
- * The real boards.  mzgo_replay_window_obs / _items write, for sample (slot,
+ * The real boards.  mzgo_replay_window_obs_items writes, for sample (slot,
  * start, symmetry) and k = 1..unroll_steps,
  *   obs [K][B][6][N*N]   the six planes of position start + k exactly as
- *                        mzgo_replay_batch writes obs0 for it (the same planes
+ *                        mzgo_replay_batch_items writes obs0 for it (the same planes
  *                        through the same sym_src permutation), STEP-major so
  *                        that [K B][6][N][N] goes to mzgo_encode as it is and
  *                        lines up with the unroll's latents 1..K
  *   window_mask [B][K]   1 where start + k <= L (row L, the final board, is
  *                        stored and counts), else 0 with all-zero planes; a
  *                        slot outside the ring gives the same
- * with mzgo_replay_ownership's arguments and checks: host indices, starts and
- * symmetries (NULL: identity), or the sampler's DEVICE items [B][3] (nothing
- * crosses the bus, nothing synchronises).  One launch, a workgroup per sample;
+ * with mzgo_replay_ownership_items' arguments and checks: DEVICE items [B][3]
+ * (nothing crosses the bus, nothing synchronises).  One launch, a workgroup per sample;
  * unroll_steps in 0..63, and 0 launches nothing (the outputs may be NULL). */
-int mzgo_replay_window_obs(mzgo_replay* replay, const int32_t* indices_host, const int32_t* starts_host,
-                           const int32_t* symmetries_host, int B, int unroll_steps, float* obs, float* window_mask,
-                           void* stream);
 int mzgo_replay_window_obs_items(mzgo_replay* replay, const int32_t* items, int B, int unroll_steps, float* obs,
                                  float* window_mask, void* stream);
 
@@ -1182,7 +1151,7 @@ int mzgo_encode(const char* const* keys, const float* const* params, const int64
 
 /* The head and the loss on ``latents`` [K+1][B][C][N][N] (mzgo_unroll_latents'
  * layout, taken whole: step 0 takes no part), ``targets`` [K][B][C][N][N]
- * (mzgo_encode of mzgo_replay_window_obs's boards) and ``mask`` [B][K], with
+ * (mzgo_encode of mzgo_replay_window_obs_items' boards) and ``mask`` [B][K], with
  * proj_w [P][C], proj_b [P], pred_w [P][P], pred_b [P].  For row (k, b),
  * k = 1..K, over the D = P N N entries:
  *   u = proj(latents[k][b]),  p = pred(relu(u)),  z = proj(targets[k-1][b])

@@ -4,7 +4,7 @@
 //
 // The head is one 1x1 conv (C -> 1) on each of the (K+1) B latents
 // mzgo_unroll_latents hands out, step-major [K+1][B][C][CELLS]; the targets
-// come sample-major from mzgo_replay_ownership, t_own [B][K+1][CELLS] in
+// come sample-major from mzgo_replay_ownership_items, t_own [B][K+1][CELLS] in
 // {-1, 0, +1} with own_mask [B][K+1].  The scalar formulas are
 // mzgo_ownership.hpp's.
 //

@@ -46,7 +46,8 @@ using namespace mzgo;
 
 namespace {
 
-constexpr int kThreads = 256;      // k_replay_batch / k_replay_ingest workgroup
+constexpr int kThreads = 256;      // the workgroup of the ingest and of every kernel that takes a sample of an item
+                                   // list (mzgo_replay.hpp: "An item list") per workgroup
 constexpr int kMaxBoard = 19;
 constexpr int kMaxUnroll = 63;     // wave 0 of k_replay_batch holds the K + 1 value targets
 
@@ -61,7 +62,9 @@ __global__ void __launch_bounds__(kThreads) k_replay_ingest(Store R, ReplayEngin
 }
 
 // ---------------------------------------------------------------------------
-// Batch assembly: one workgroup per sample (slot, start, symmetry).
+// Batch assembly: one workgroup per sample of the item list (mzgo_replay.hpp:
+// sample_window decodes it, window_position / window_move say which rows of the
+// store may be read; a row that may not is the row past a game's end).
 //   wave 0     the K + 1 value targets, a thread each (_discounted's loop: at
 //              most K multiply-adds in f64, in its order)
 //   wave 1     the K actions and rewards
@@ -69,10 +72,14 @@ __global__ void __launch_bounds__(kThreads) k_replay_ingest(Store R, ReplayEngin
 //              of the sample's output on thread e % 256: every store is
 //              contiguous across the workgroup; the symmetry is a gather
 //              through the cell permutation in LDS
-// SEARCH (search-value targets, mzgo_replay_batch_values): wave 0 writes t_val
-// itself from the stored root values (search_value_target, mzgo_replay.hpp: at
-// most ``td`` multiply-adds), the plane loop covers the start position alone
-// and boot_obs, val, factor and has_boot are not written (null).
+// SEARCH (search-value targets, mzgo_replay_batch_items_values): wave 0 writes
+// t_val itself from the stored root values (search_value_target,
+// mzgo_replay.hpp: at most ``td`` multiply-adds), the plane loop covers the
+// start position alone and boot_obs, val, factor and has_boot are not written
+// (null).
+// A sample whose slot is not the ring's comes out as an empty game's: zero
+// planes, pass actions, rewards 0, uniform policy rows, val 0, factor 1,
+// has_boot 0, t_val 0; so does a row before a game's first (start + k < 0).
 // ---------------------------------------------------------------------------
 struct BatchOut {
   float* obs0;        // [B][6][CELLS]
@@ -91,34 +98,35 @@ __global__ void __launch_bounds__(kThreads) k_replay_batch(Store R, const int* i
                                                            BatchOut O) {
   __shared__ int perm[kMaxBoard * kMaxBoard];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int slot = items[3 * b], start = items[3 * b + 1], sym = items[3 * b + 2];
-  const int CELLS = R.CELLS, A = R.A, N = R.N;
-  const int L = R.length[slot];
-  const int T = L + 1;                                     // rewards
-  const size_t pos = (size_t)slot * (R.M + 1), mv = (size_t)slot * R.M;
-  for (int c = tid; c < CELLS; c += kThreads) perm[c] = sym_src(N, sym, c);
+  const SampleWindow w = sample_window(R, items, b);
+  const int CELLS = R.CELLS, A = R.A, N = R.N, L = w.L;
+  const long long start = w.start;
+  const size_t pos = w.pos, mv = w.mv;
+  for (int c = tid; c < CELLS; c += kThreads) perm[c] = sym_src(N, w.sym, c);
 
   if (SEARCH && tid <= K) {                               // wave 0 (K <= 63)
+    const long long i = start + tid;                       // (every index past L has the target 0)
     O.t_val[(size_t)b * (K + 1) + tid] =
-        search_value_target(R.reward + pos, R.root_value + mv, L, start + tid, td, discount);
+        window_position(w, i) ? search_value_target(R.reward + pos, R.root_value + mv, L, (int)i, td, discount) : 0.f;
   } else if (tid <= K) {
-    const int index = start + tid;
+    const long long index = start + tid;
     double target = 0.0, factor = 1.0;
     for (int k = 0; k < K; ++k) {
-      const int j = index + k;
-      if (j >= T) break;
+      const long long j = index + k;
+      if (!window_position(w, j)) break;
       target += factor * R.reward[pos + j];
       factor *= discount;
     }
     const size_t o = (size_t)b * (K + 1) + tid;
     O.val[o] = target;
     O.factor[o] = factor;
-    O.has_boot[o] = index + K < T;
+    O.has_boot[o] = window_position(w, index + K);
   } else if (tid >= 64 && tid - 64 < K) {                  // wave 1
-    const int k = tid - 64, j = start + k;
+    const int k = tid - 64;
+    const long long j = start + k;
     const size_t o = (size_t)b * K + k;
-    O.acts[o] = j < L ? sym_dst(N, sym, R.action[mv + j]) : A - 1;     // pass past the end
-    O.t_rew[o] = j < T ? (float)R.reward[pos + j] : 0.f;
+    O.acts[o] = window_move(w, j) ? sym_dst(N, w.sym, R.action[mv + j]) : A - 1;     // pass past the end
+    O.t_rew[o] = window_position(w, j) ? (float)R.reward[pos + j] : 0.f;
   }
   __syncthreads();
 
@@ -127,19 +135,11 @@ __global__ void __launch_bounds__(kThreads) k_replay_batch(Store R, const int* i
     const int row = e / plane, rem = e - row * plane;
     const int p = rem / CELLS, c = rem - p * CELLS;
     // row 0: the start position; row k + 1: the bootstrap position of unroll step k
-    const int at = row == 0 ? start : start + row - 1 + K;
+    const long long at = row == 0 ? start : start + row - 1 + K;
     float v = 0.f;
-    if (at <= L) {
-      const size_t q = pos + at;
-      const int fl = R.flags[q];
-      switch (p) {
-        case 0: v = R.stones[q * CELLS + perm[c]] == 1; break;
-        case 1: v = R.stones[q * CELLS + perm[c]] == 2; break;
-        case 2: v = fl & 1; break;
-        case 3: v = R.invd[q * CELLS + perm[c]]; break;
-        case 4: v = (fl >> 1) & 1; break;
-        default: v = (fl >> 2) & 1; break;
-      }
+    if (window_position(w, at)) {
+      const size_t q = pos + (size_t)at;
+      v = observation_plane(R.stones + q * CELLS, R.invd + q * CELLS, R.flags[q], p, perm[c]);
     }
     if (row == 0) O.obs0[(size_t)b * plane + rem] = v;
     else O.boot_obs[((size_t)b * (K + 1) + row - 1) * plane + rem] = v;
@@ -147,11 +147,13 @@ __global__ void __launch_bounds__(kThreads) k_replay_batch(Store R, const int* i
 
   const float uniform = (float)(1.0 / A);
   for (int e = tid; e < (K + 1) * A; e += kThreads) {
-    const int k = e / A, a = e - k * A, i = start + k;
+    const int k = e / A, a = e - k * A;
+    const long long i = start + k;
     float v = uniform;
     // a position searched with the fast budget (kFlagFast) is no policy target: an all-zero row,
     // on which the loss and its gradient are exactly 0
-    if (i < L) v = (R.flags[pos + i] & kFlagFast) ? 0.f : (float)R.policy[(mv + i) * A + (a < CELLS ? perm[a] : a)];
+    if (window_move(w, i))
+      v = (R.flags[pos + i] & kFlagFast) ? 0.f : (float)R.policy[(mv + i) * A + (a < CELLS ? perm[a] : a)];
     O.t_pol[(size_t)b * (K + 1) * A + e] = v;
   }
 }
@@ -166,7 +168,7 @@ __global__ void __launch_bounds__(kThreads) k_replay_finish(const double* val, c
 }
 
 // ---------------------------------------------------------------------------
-// Ownership targets: one workgroup per sample (slot, start, symmetry).  The
+// Ownership targets: one workgroup per sample of the item list.  The
 // final board (row L) goes to LDS; the reached-colour masks of its empty cells
 // are iterated to their fixed point in two LDS buffers, a pass reading one and
 // writing the other, with the barrier that also ORs the threads' "changed"
@@ -183,13 +185,10 @@ __global__ void __launch_bounds__(kThreads) k_replay_ownership(Store R, const in
   __shared__ uint8_t reach[2][kMaxBoard * kMaxBoard];
   __shared__ int perm[kMaxBoard * kMaxBoard];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int slot = items[3 * b], start = items[3 * b + 1], sym = items[3 * b + 2] & 7;
-  const int CELLS = R.CELLS, N = R.N;
-  const bool held = slot >= 0 && slot < R.cap;
-  int L = held ? R.length[slot] : 0;
-  L = L < 0 ? 0 : L > R.M ? R.M : L;
-  const size_t pos = held ? (size_t)slot * (R.M + 1) : 0;
-  const int final_flags = held ? R.flags[pos + L] : 0;
+  const SampleWindow w = sample_window(R, items, b);
+  const int CELLS = R.CELLS, N = R.N, start = w.start, sym = w.sym, L = w.L;
+  const size_t pos = w.pos;
+  const int final_flags = window_position(w, L) ? R.flags[pos + L] : 0;
   float* out = t_own + (size_t)b * (K + 1) * CELLS;
   if (tid <= K) own_mask[(size_t)b * (K + 1) + tid] = own_row_valid((long long)start + tid, L, final_flags) ? 1.f : 0.f;
   if (!own_row_valid(start < 0 ? 0 : start, L, final_flags)) {    // (block-uniform) no row of the sample has a target
@@ -228,7 +227,7 @@ __global__ void __launch_bounds__(kThreads) k_replay_ownership(Store R, const in
 
 // ---------------------------------------------------------------------------
 // The real boards of a sampled window (the consistency loss's targets' inputs):
-// one workgroup per sample (slot, start, symmetry).  obs[k-1][b] is the six
+// one workgroup per sample of the item list.  obs[k-1][b] is the six
 // planes of position start + k, k = 1..K, exactly as k_replay_batch writes obs0
 // for that position (the same planes through the same cell permutation),
 // step-major [K][B][6][CELLS]; window_mask[b][k-1] = start + k <= L (row L, the
@@ -240,35 +239,21 @@ __global__ void __launch_bounds__(kThreads) k_replay_window_obs(Store R, const i
                                                                 float* __restrict__ window_mask) {
   __shared__ int perm[kMaxBoard * kMaxBoard];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int slot = items[3 * b], start = items[3 * b + 1], sym = items[3 * b + 2] & 7;
+  const SampleWindow w = sample_window(R, items, b);
   const int CELLS = R.CELLS, N = R.N;
-  const bool held = slot >= 0 && slot < R.cap;
-  int L = held ? R.length[slot] : 0;
-  L = L < 0 ? 0 : L > R.M ? R.M : L;
-  const size_t pos = held ? (size_t)slot * (R.M + 1) : 0;
-  for (int c = tid; c < CELLS; c += kThreads) perm[c] = sym_src(N, sym, c);
-  if (tid < K) {
-    const long long at = (long long)start + tid + 1;
-    window_mask[(size_t)b * K + tid] = held && at >= 0 && at <= L ? 1.f : 0.f;
-  }
+  const long long start = w.start;
+  for (int c = tid; c < CELLS; c += kThreads) perm[c] = sym_src(N, w.sym, c);
+  if (tid < K) window_mask[(size_t)b * K + tid] = window_position(w, start + tid + 1) ? 1.f : 0.f;
   __syncthreads();
   const int plane = 6 * CELLS;
   for (int e = tid; e < K * plane; e += kThreads) {
     const int k = e / plane, rem = e - k * plane;
     const int p = rem / CELLS, c = rem - p * CELLS;
-    const long long at = (long long)start + k + 1;
+    const long long at = start + k + 1;
     float v = 0.f;
-    if (held && at >= 0 && at <= L) {
-      const size_t q = pos + (size_t)at;
-      const int fl = R.flags[q];
-      switch (p) {
-        case 0: v = R.stones[q * CELLS + perm[c]] == 1; break;
-        case 1: v = R.stones[q * CELLS + perm[c]] == 2; break;
-        case 2: v = fl & 1; break;
-        case 3: v = R.invd[q * CELLS + perm[c]]; break;
-        case 4: v = (fl >> 1) & 1; break;
-        default: v = (fl >> 2) & 1; break;
-      }
+    if (window_position(w, at)) {
+      const size_t q = w.pos + (size_t)at;
+      v = observation_plane(R.stones + q * CELLS, R.invd + q * CELLS, R.flags[q], p, perm[c]);
     }
     obs[((size_t)k * B + b) * plane + rem] = v;
   }
@@ -659,7 +644,7 @@ struct mzgo_replay {
   int head = 0, size = 0;                 // logical game i lives in slot (head + i) % cap
   std::vector<int> len, gid;              // per SLOT: host mirrors of R.length / R.key_gid
   std::vector<void*> allocs;
-  // batch / reanalysis index staging: pinned host words -> device words
+  // index staging: pinned host words -> device words (mzgo_replay_items: the caller's; the reanalysis: d_items)
   int* h_items = nullptr;
   int* d_items = nullptr;
   size_t items_cap = 0;
@@ -733,8 +718,8 @@ struct mzgo_replay {
     items_cap = cap;
     return MZGO_OK;
   }
-  int items_upload(size_t n, hipStream_t s) {
-    RHIPCHK(hipMemcpyAsync(d_items, h_items, n * sizeof(int), hipMemcpyHostToDevice, s));
+  int items_upload(int* dst, size_t n, hipStream_t s) {
+    RHIPCHK(hipMemcpyAsync(dst, h_items, n * sizeof(int), hipMemcpyHostToDevice, s));
     RHIPCHK(hipEventRecord(items_read, s));
     return MZGO_OK;
   }
@@ -952,10 +937,13 @@ int mzgo_replay_export(mzgo_replay* r, int i, int32_t* length_host, int32_t* key
   return MZGO_OK;
 }
 
-// the host samples of mzgo_replay_batch / _batch_values checked against the
-// mirror and uploaded as device items (``who``: the entry point's name)
-static int upload_samples(mzgo_replay* r, const char* who, const int32_t* indices_host, const int32_t* starts_host,
-                          const int32_t* symmetries_host, int B, hipStream_t s) {
+int mzgo_replay_items(mzgo_replay* r, const int32_t* indices_host, const int32_t* starts_host,
+                      const int32_t* symmetries_host, int B, int32_t* items, void* stream) {
+  const char* who = "mzgo_replay_items";
+  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
+  if (!indices_host || !starts_host || !items)
+    return set_error(MZGO_EINVAL, "%s: null %s", who, !indices_host ? "indices" : !starts_host ? "starts" : "items");
   for (int b = 0; b < B; ++b) {
     const int i = indices_host[b];
     if (i < 0 || i >= r->size)
@@ -966,79 +954,33 @@ static int upload_samples(mzgo_replay* r, const char* who, const int32_t* indice
     if (symmetries_host && (symmetries_host[b] < 0 || symmetries_host[b] > 7))
       return set_error(MZGO_EINVAL, "%s: sample %d: symmetry %d (0..7)", who, b, symmetries_host[b]);
   }
+  hipStream_t s = (hipStream_t)stream;
   if (int rc = r->items_room((size_t)B * 3, s)) return rc;
   for (int b = 0; b < B; ++b) {
     r->h_items[3 * b] = r->slot_of(indices_host[b]);
     r->h_items[3 * b + 1] = starts_host[b];
     r->h_items[3 * b + 2] = symmetries_host ? symmetries_host[b] : 0;
   }
-  return r->items_upload((size_t)B * 3, s);
-}
-
-// the checks the three search-value assemblies share, and their launch
-static int values_check(const mzgo_replay* r, const char* who, int B, int unroll_steps, int td_steps, const float* obs0,
-                        const int64_t* acts, const float* t_rew, const float* t_pol, const float* t_val) {
-  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
-  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
-  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
-    return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (1..%d)", who, unroll_steps, kMaxUnroll);
-  if (td_steps < 1) return set_error(MZGO_EINVAL, "%s: td_steps must be >= 1, got %d", who, td_steps);
-  if (!obs0 || !acts || !t_rew || !t_pol || !t_val)
-    return set_error(MZGO_EINVAL, "%s: null %s", who,
-                     !obs0 ? "obs0" : !acts ? "acts" : !t_rew ? "t_rew" : !t_pol ? "t_pol" : "t_val");
-  return MZGO_OK;
-}
-static int values_launch(mzgo_replay* r, const int* items, int B, int unroll_steps, int td_steps, double discount,
-                         float* obs0, int64_t* acts, float* t_rew, float* t_pol, float* t_val, hipStream_t s) {
-  const BatchOut O{obs0, nullptr, acts, t_rew, t_pol, nullptr, nullptr, nullptr, t_val};
-  hipLaunchKernelGGL(k_replay_batch<true>, dim3(B), dim3(kThreads), 0, s, r->R, items, unroll_steps, td_steps,
-                     discount, O);
-  RHIPCHK(hipGetLastError());
-  return MZGO_OK;
-}
-
-int mzgo_replay_batch(mzgo_replay* r, const int32_t* indices_host, const int32_t* starts_host,
-                      const int32_t* symmetries_host, int B, int unroll_steps, double discount, float* obs0,
-                      float* boot_obs, int64_t* acts, float* t_rew, float* t_pol, double* val, double* factor,
-                      uint8_t* has_boot, void* stream) {
-  if (!r) return set_error(MZGO_EINVAL, "mzgo_replay_batch: null replay");
-  if (B < 1) return set_error(MZGO_EINVAL, "mzgo_replay_batch: B must be >= 1, got %d", B);
-  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
-    return set_error(MZGO_EINVAL, "mzgo_replay_batch: unroll_steps %d out of range (1..%d)", unroll_steps, kMaxUnroll);
-  if (!indices_host || !starts_host || !obs0 || !boot_obs || !acts || !t_rew || !t_pol || !val || !factor || !has_boot)
-    return set_error(MZGO_EINVAL, "mzgo_replay_batch: null %s",
-                     !indices_host ? "indices" : !starts_host ? "starts" : !obs0 ? "obs0" : !boot_obs ? "boot_obs"
-                     : !acts ? "acts" : !t_rew ? "t_rew" : !t_pol ? "t_pol" : !val ? "val" : !factor ? "factor"
-                     : "has_boot");
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = upload_samples(r, "mzgo_replay_batch", indices_host, starts_host, symmetries_host, B, s)) return rc;
-  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot, nullptr};
-  hipLaunchKernelGGL(k_replay_batch<false>, dim3(B), dim3(kThreads), 0, s, r->R, r->d_items, unroll_steps, 0, discount,
-                     O);
-  RHIPCHK(hipGetLastError());
-  return MZGO_OK;
-}
-
-int mzgo_replay_batch_values(mzgo_replay* r, const int32_t* indices_host, const int32_t* starts_host,
-                             const int32_t* symmetries_host, int B, int unroll_steps, int td_steps, double discount,
-                             float* obs0, int64_t* acts, float* t_rew, float* t_pol, float* t_val, void* stream) {
-  const char* who = "mzgo_replay_batch_values";
-  if (int rc = values_check(r, who, B, unroll_steps, td_steps, obs0, acts, t_rew, t_pol, t_val)) return rc;
-  if (!indices_host || !starts_host)
-    return set_error(MZGO_EINVAL, "%s: null %s", who, !indices_host ? "indices" : "starts");
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = upload_samples(r, who, indices_host, starts_host, symmetries_host, B, s)) return rc;
-  return values_launch(r, r->d_items, B, unroll_steps, td_steps, discount, obs0, acts, t_rew, t_pol, t_val, s);
+  return r->items_upload(items, (size_t)B * 3, s);
 }
 
 int mzgo_replay_batch_items_values(mzgo_replay* r, const int32_t* items, int B, int unroll_steps, int td_steps,
                                    double discount, float* obs0, int64_t* acts, float* t_rew, float* t_pol,
                                    float* t_val, void* stream) {
   const char* who = "mzgo_replay_batch_items_values";
-  if (int rc = values_check(r, who, B, unroll_steps, td_steps, obs0, acts, t_rew, t_pol, t_val)) return rc;
-  if (!items) return set_error(MZGO_EINVAL, "%s: null items", who);
-  return values_launch(r, items, B, unroll_steps, td_steps, discount, obs0, acts, t_rew, t_pol, t_val,
-                       (hipStream_t)stream);
+  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
+  if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
+  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
+    return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (1..%d)", who, unroll_steps, kMaxUnroll);
+  if (td_steps < 1) return set_error(MZGO_EINVAL, "%s: td_steps must be >= 1, got %d", who, td_steps);
+  if (!items || !obs0 || !acts || !t_rew || !t_pol || !t_val)
+    return set_error(MZGO_EINVAL, "%s: null %s", who,
+                     !items ? "items" : !obs0 ? "obs0" : !acts ? "acts" : !t_rew ? "t_rew" : !t_pol ? "t_pol" : "t_val");
+  const BatchOut O{obs0, nullptr, acts, t_rew, t_pol, nullptr, nullptr, nullptr, t_val};
+  hipLaunchKernelGGL(k_replay_batch<true>, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, r->R, items, unroll_steps,
+                     td_steps, discount, O);
+  RHIPCHK(hipGetLastError());
+  return MZGO_OK;
 }
 
 int mzgo_replay_value_targets_host(const double* reward, const double* root_value, int L, int start, int unroll_steps,
@@ -1098,7 +1040,7 @@ int mzgo_replay_reanalyse(mzgo_replay* r, mzgo_engine* eng, const int32_t* games
     r->h_items[2 * i] = items[2 * order[i]];
     r->h_items[2 * i + 1] = items[2 * order[i] + 1];
   }
-  if (int rc = r->items_upload(2 * n, s)) return rc;
+  if (int rc = r->items_upload(r->d_items, 2 * n, s)) return rc;
   // staging, each field on a 256-byte boundary
   const size_t C = r->R.CELLS, A = r->R.A;
   const size_t sizes[] = {n * C, n * C, n, n * 2 * 4, n * A * 4, n * 8, n * A * 8};
@@ -1237,81 +1179,36 @@ int mzgo_replay_batch_items(mzgo_replay* r, const int32_t* items, int B, int unr
   return MZGO_OK;
 }
 
-// the checks the two ownership assemblies share, and their launch
-static int ownership_check(const mzgo_replay* r, const char* who, int B, int unroll_steps, const float* t_own,
-                           const float* own_mask) {
+int mzgo_replay_ownership_items(mzgo_replay* r, const int32_t* items, int B, int unroll_steps, float* t_own,
+                                float* own_mask, void* stream) {
+  const char* who = "mzgo_replay_ownership_items";
   if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
   if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
   if (unroll_steps < 0 || unroll_steps > kMaxUnroll)
     return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (0..%d)", who, unroll_steps, kMaxUnroll);
   if (!t_own || !own_mask) return set_error(MZGO_EINVAL, "%s: null %s", who, !t_own ? "t_own" : "own_mask");
-  return MZGO_OK;
-}
-static int ownership_launch(mzgo_replay* r, const int* items, int B, int unroll_steps, float* t_own, float* own_mask,
-                            hipStream_t s) {
-  hipLaunchKernelGGL(k_replay_ownership, dim3(B), dim3(kThreads), 0, s, r->R, items, unroll_steps, t_own, own_mask);
+  if (!items) return set_error(MZGO_EINVAL, "%s: null items", who);
+  hipLaunchKernelGGL(k_replay_ownership, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, r->R, items, unroll_steps,
+                     t_own, own_mask);
   RHIPCHK(hipGetLastError());
   return MZGO_OK;
 }
 
-int mzgo_replay_ownership(mzgo_replay* r, const int32_t* indices_host, const int32_t* starts_host,
-                          const int32_t* symmetries_host, int B, int unroll_steps, float* t_own, float* own_mask,
-                          void* stream) {
-  const char* who = "mzgo_replay_ownership";
-  if (int rc = ownership_check(r, who, B, unroll_steps, t_own, own_mask)) return rc;
-  if (!indices_host || !starts_host)
-    return set_error(MZGO_EINVAL, "%s: null %s", who, !indices_host ? "indices" : "starts");
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = upload_samples(r, who, indices_host, starts_host, symmetries_host, B, s)) return rc;
-  return ownership_launch(r, r->d_items, B, unroll_steps, t_own, own_mask, s);
-}
-
-int mzgo_replay_ownership_items(mzgo_replay* r, const int32_t* items, int B, int unroll_steps, float* t_own,
-                                float* own_mask, void* stream) {
-  const char* who = "mzgo_replay_ownership_items";
-  if (int rc = ownership_check(r, who, B, unroll_steps, t_own, own_mask)) return rc;
-  if (!items) return set_error(MZGO_EINVAL, "%s: null items", who);
-  return ownership_launch(r, items, B, unroll_steps, t_own, own_mask, (hipStream_t)stream);
-}
-
-// the checks the two window-observation assemblies share, and their launch (none at K = 0)
-static int window_obs_check(const mzgo_replay* r, const char* who, int B, int unroll_steps, const float* obs,
-                            const float* window_mask) {
+int mzgo_replay_window_obs_items(mzgo_replay* r, const int32_t* items, int B, int unroll_steps, float* obs,
+                                 float* window_mask, void* stream) {
+  const char* who = "mzgo_replay_window_obs_items";
   if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
   if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
   if (unroll_steps < 0 || unroll_steps > kMaxUnroll)
     return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (0..%d)", who, unroll_steps, kMaxUnroll);
   if (unroll_steps > 0 && (!obs || !window_mask))
     return set_error(MZGO_EINVAL, "%s: null %s", who, !obs ? "obs" : "window_mask");
-  return MZGO_OK;
-}
-static int window_obs_launch(mzgo_replay* r, const int* items, int B, int unroll_steps, float* obs, float* window_mask,
-                             hipStream_t s) {
-  if (unroll_steps == 0) return MZGO_OK;
-  hipLaunchKernelGGL(k_replay_window_obs, dim3(B), dim3(kThreads), 0, s, r->R, items, B, unroll_steps, obs,
-                     window_mask);
+  if (!items) return set_error(MZGO_EINVAL, "%s: null items", who);
+  if (unroll_steps == 0) return MZGO_OK;                    // (no rows: no launch)
+  hipLaunchKernelGGL(k_replay_window_obs, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, r->R, items, B,
+                     unroll_steps, obs, window_mask);
   RHIPCHK(hipGetLastError());
   return MZGO_OK;
-}
-
-int mzgo_replay_window_obs(mzgo_replay* r, const int32_t* indices_host, const int32_t* starts_host,
-                           const int32_t* symmetries_host, int B, int unroll_steps, float* obs, float* window_mask,
-                           void* stream) {
-  const char* who = "mzgo_replay_window_obs";
-  if (int rc = window_obs_check(r, who, B, unroll_steps, obs, window_mask)) return rc;
-  if (!indices_host || !starts_host)
-    return set_error(MZGO_EINVAL, "%s: null %s", who, !indices_host ? "indices" : "starts");
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = upload_samples(r, who, indices_host, starts_host, symmetries_host, B, s)) return rc;
-  return window_obs_launch(r, r->d_items, B, unroll_steps, obs, window_mask, s);
-}
-
-int mzgo_replay_window_obs_items(mzgo_replay* r, const int32_t* items, int B, int unroll_steps, float* obs,
-                                 float* window_mask, void* stream) {
-  const char* who = "mzgo_replay_window_obs_items";
-  if (int rc = window_obs_check(r, who, B, unroll_steps, obs, window_mask)) return rc;
-  if (!items) return set_error(MZGO_EINVAL, "%s: null items", who);
-  return window_obs_launch(r, items, B, unroll_steps, obs, window_mask, (hipStream_t)stream);
 }
 
 int mzgo_ownership_host(const int8_t* stones, int board_size, int8_t* owner) {
@@ -1362,7 +1259,7 @@ static int positions_check(const mzgo_replay* r, const char* who) {
 static int sample_launch(mzgo_replay* r, const char* who, bool positions, int B, uint64_t seed, uint32_t step,
                          int symmetries, double beta, int32_t* items, int32_t* index, uint32_t* gen, float* weight,
                          hipStream_t s) {
-  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);    // (every sampling entry point's)
+  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
   if (positions)
     if (int rc = positions_check(r, who)) return rc;
   if (B < 1) return set_error(MZGO_EINVAL, "%s: B must be >= 1, got %d", who, B);
@@ -1394,83 +1291,16 @@ static int sample_launch(mzgo_replay* r, const char* who, bool positions, int B,
   return MZGO_OK;
 }
 
-// the three sample calls, for the game sampler and (``positions``) the position sampler
-static int sample_batch(mzgo_replay* r, const char* who, bool positions, int B, int unroll_steps, double discount,
-                        uint64_t seed, uint32_t step, int symmetries, double beta, int32_t* items, int32_t* index,
-                        uint32_t* gen, float* weight, float* obs0, float* boot_obs, int64_t* acts, float* t_rew,
-                        float* t_pol, double* val, double* factor, uint8_t* has_boot, hipStream_t s) {
-  if (!r) return set_error(MZGO_EINVAL, "%s: null replay", who);
-  if (unroll_steps < 1 || unroll_steps > kMaxUnroll)
-    return set_error(MZGO_EINVAL, "%s: unroll_steps %d out of range (1..%d)", who, unroll_steps, kMaxUnroll);
-  if (!obs0 || !boot_obs || !acts || !t_rew || !t_pol || !val || !factor || !has_boot)
-    return set_error(MZGO_EINVAL, "%s: null %s", who,
-                     !obs0 ? "obs0" : !boot_obs ? "boot_obs" : !acts ? "acts" : !t_rew ? "t_rew" : !t_pol ? "t_pol"
-                     : !val ? "val" : !factor ? "factor" : "has_boot");
-  if (int rc = sample_launch(r, who, positions, B, seed, step, symmetries, beta, items, index, gen, weight, s))
-    return rc;
-  const BatchOut O{obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot, nullptr};
-  hipLaunchKernelGGL(k_replay_batch<false>, dim3(B), dim3(kThreads), 0, s, r->R, items, unroll_steps, 0, discount, O);
-  RHIPCHK(hipGetLastError());
-  return MZGO_OK;
-}
-static int sample_batch_values(mzgo_replay* r, const char* who, bool positions, int B, int unroll_steps, int td_steps,
-                               double discount, uint64_t seed, uint32_t step, int symmetries, double beta,
-                               int32_t* items, int32_t* index, uint32_t* gen, float* weight, float* obs0,
-                               int64_t* acts, float* t_rew, float* t_pol, float* t_val, hipStream_t s) {
-  if (int rc = values_check(r, who, B, unroll_steps, td_steps, obs0, acts, t_rew, t_pol, t_val)) return rc;
-  if (int rc = sample_launch(r, who, positions, B, seed, step, symmetries, beta, items, index, gen, weight, s))
-    return rc;
-  return values_launch(r, items, B, unroll_steps, td_steps, discount, obs0, acts, t_rew, t_pol, t_val, s);
-}
-
 int mzgo_replay_sample(mzgo_replay* r, int B, uint64_t seed, uint32_t step, int symmetries, double beta,
                        int32_t* items, int32_t* index, uint32_t* gen, float* weight, void* stream) {
   return sample_launch(r, "mzgo_replay_sample", false, B, seed, step, symmetries, beta, items, index, gen, weight,
                        (hipStream_t)stream);
 }
 
-int mzgo_replay_sample_batch(mzgo_replay* r, int B, int unroll_steps, double discount, uint64_t seed, uint32_t step,
-                             int symmetries, double beta, int32_t* items, int32_t* index, uint32_t* gen,
-                             float* weight, float* obs0, float* boot_obs, int64_t* acts, float* t_rew, float* t_pol,
-                             double* val, double* factor, uint8_t* has_boot, void* stream) {
-  return sample_batch(r, "mzgo_replay_sample_batch", false, B, unroll_steps, discount, seed, step, symmetries, beta,
-                      items, index, gen, weight, obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot,
-                      (hipStream_t)stream);
-}
-
-int mzgo_replay_sample_batch_values(mzgo_replay* r, int B, int unroll_steps, int td_steps, double discount,
-                                    uint64_t seed, uint32_t step, int symmetries, double beta, int32_t* items,
-                                    int32_t* index, uint32_t* gen, float* weight, float* obs0, int64_t* acts,
-                                    float* t_rew, float* t_pol, float* t_val, void* stream) {
-  return sample_batch_values(r, "mzgo_replay_sample_batch_values", false, B, unroll_steps, td_steps, discount, seed,
-                             step, symmetries, beta, items, index, gen, weight, obs0, acts, t_rew, t_pol, t_val,
-                             (hipStream_t)stream);
-}
-
 int mzgo_replay_sample_positions(mzgo_replay* r, int B, uint64_t seed, uint32_t step, int symmetries, double beta,
                                  int32_t* items, int32_t* index, uint32_t* gen, float* weight, void* stream) {
   return sample_launch(r, "mzgo_replay_sample_positions", true, B, seed, step, symmetries, beta, items, index, gen,
                        weight, (hipStream_t)stream);
-}
-
-int mzgo_replay_sample_positions_batch(mzgo_replay* r, int B, int unroll_steps, double discount, uint64_t seed,
-                                       uint32_t step, int symmetries, double beta, int32_t* items, int32_t* index,
-                                       uint32_t* gen, float* weight, float* obs0, float* boot_obs, int64_t* acts,
-                                       float* t_rew, float* t_pol, double* val, double* factor, uint8_t* has_boot,
-                                       void* stream) {
-  return sample_batch(r, "mzgo_replay_sample_positions_batch", true, B, unroll_steps, discount, seed, step, symmetries,
-                      beta, items, index, gen, weight, obs0, boot_obs, acts, t_rew, t_pol, val, factor, has_boot,
-                      (hipStream_t)stream);
-}
-
-int mzgo_replay_sample_positions_batch_values(mzgo_replay* r, int B, int unroll_steps, int td_steps, double discount,
-                                              uint64_t seed, uint32_t step, int symmetries, double beta,
-                                              int32_t* items, int32_t* index, uint32_t* gen, float* weight,
-                                              float* obs0, int64_t* acts, float* t_rew, float* t_pol, float* t_val,
-                                              void* stream) {
-  return sample_batch_values(r, "mzgo_replay_sample_positions_batch_values", true, B, unroll_steps, td_steps, discount,
-                             seed, step, symmetries, beta, items, index, gen, weight, obs0, acts, t_rew, t_pol, t_val,
-                             (hipStream_t)stream);
 }
 
 // the two sampler twins' common argument checks (``wname``: what the weights

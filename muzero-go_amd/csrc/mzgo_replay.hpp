@@ -7,7 +7,9 @@
 // order of additions, descent rule and fallback, host and device; its host
 // serial form -- build, one draw with the leaf's removal, importance weights
 // -- which both samplers' host twins run), the position
-// ledger and its weight rules (host and device likewise), the window
+// ledger and its weight rules (host and device likewise), the item list the
+// assembly kernels take with its one decode, its two row predicates and the
+// plane rule of a stored row (host and device likewise), the window
 // of a sample and the item list of a batch's windows (host and device
 // likewise) with the in-place reanalysis queue's arguments, the search-value
 // target rule and the value rows it reads (host and device), the ownership
@@ -146,6 +148,61 @@ struct GamesArgs {
 };
 
 // ---------------------------------------------------------------------------
+// An item list: i32 [B][3] on the device, sample b = (slot, start, symmetry) --
+// a ring slot, the move the sample starts from and one of the eight symmetries
+// above.  mzgo_replay_items writes one from host (game, start, symmetry) triples
+// it has checked against the host mirror, the samplers write one from their
+// draws; the three assembly kernels (k_replay_batch, k_replay_ownership,
+// k_replay_window_obs) and the priority updates read one, a workgroup per
+// sample.  The kernels check nothing else: sample_window is their one decode,
+// and a row of the store is read only where one of the two predicates below
+// holds, whatever the list holds.  Host and device: tools/replay_twins_check.cpp
+// runs them on a store image in host memory.
+// ---------------------------------------------------------------------------
+struct SampleWindow {
+  int slot, start, sym;  // the triple; sym & 7
+  bool held;             // the slot is one of the ring's
+  int L;                 // the game's moves, 0..M (0 when not held)
+  size_t pos, mv;        // the game's first position row and first move row (0 when not held)
+};
+__host__ __device__ __forceinline__ SampleWindow sample_window(const Store& R, const int* items, int b) {
+  SampleWindow w;
+  w.slot = items[3 * b];
+  w.start = items[3 * b + 1];
+  w.sym = items[3 * b + 2] & 7;
+  w.held = w.slot >= 0 && w.slot < R.cap;
+  const int L = w.held ? R.length[w.slot] : 0;
+  w.L = L < 0 ? 0 : L > R.M ? R.M : L;
+  w.pos = w.held ? (size_t)w.slot * (R.M + 1) : 0;
+  w.mv = w.held ? (size_t)w.slot * R.M : 0;
+  return w;
+}
+// position row ``at`` (stones, invd, flags, reward: rows 0..L, the final board last) may be read
+__host__ __device__ __forceinline__ bool window_position(const SampleWindow& w, long long at) {
+  return w.held && at >= 0 && at <= w.L;
+}
+// move row ``j`` (action, policy, root_value: rows 0..L-1) may be read
+__host__ __device__ __forceinline__ bool window_move(const SampleWindow& w, long long j) {
+  return w.held && j >= 0 && j < w.L;
+}
+
+// Plane p (0..5: black, white, turn, invalid, passed, done) of the observation
+// of a stored position, at the row's cell ``src``: ``stones`` and ``invd`` are
+// the row's [CELLS], ``flags`` its byte.  mzgo.reanalyse.observation_planes is
+// the same rule on the host.
+__host__ __device__ __forceinline__ float observation_plane(const int8_t* stones, const uint8_t* invd, int flags, int p,
+                                                            int src) {
+  switch (p) {
+    case 0: return stones[src] == 1;
+    case 1: return stones[src] == 2;
+    case 2: return flags & 1;
+    case 3: return invd[src];
+    case 4: return (flags >> 1) & 1;
+    default: return (flags >> 2) & 1;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // The window of a sample (slot, start, symmetry) under K unroll steps: the
 // stored policy rows k_replay_batch reads for it, t = start .. min(start + K,
 // L - 1) with L = length[slot] (rows past the game's end are the uniform row
@@ -170,7 +227,7 @@ __host__ __device__ __forceinline__ bool window_has(int start, int rows, int t) 
 }
 
 // ---------------------------------------------------------------------------
-// Search-value targets (mzgo.h: mzgo_replay_batch_values): the n-step return of
+// Search-value targets (mzgo.h: mzgo_replay_batch_items_values): the n-step return of
 // trajectory index i >= 0 of a game of L moves, bootstrapped from the stored
 // root value of the position n = td_steps >= 1 moves on.  reward [L + 1] (the
 // winner last), root_value [L].  f64, one multiply and one add per step in
@@ -217,7 +274,7 @@ __host__ __device__ __forceinline__ bool sample_has(int start, int rows, int vfi
 }
 
 // ---------------------------------------------------------------------------
-// Ownership targets (mzgo.h: mzgo_replay_ownership): who owns each point of a
+// Ownership targets (mzgo.h: mzgo_replay_ownership_items): who owns each point of a
 // game's final board under the area rule (oracle/gogame.py: areas, cell by
 // cell).  A stone is owned by its colour (1 black, 2 white); an empty point by
 // the one colour its empty region touches, by nobody (0) when the region

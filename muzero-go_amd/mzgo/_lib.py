@@ -120,20 +120,15 @@ SIGNATURES = {
     "mzgo_replay_play_games": (_I, [_P, _P, _I, _I, _P]),
     "mzgo_replay_add": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int32, _P]),
     "mzgo_replay_export": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "mzgo_replay_batch": (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mzgo_replay_items": (_I, [_P, _P, _P, _P, _I, _P, _P]),
     "mzgo_replay_finish_values": (_I, [_P, _P, _P, _P, _I, _P, _P]),
     "mzgo_replay_reanalyse": (_I, [_P, _P, _P, _I, _P]),
     "mzgo_replay_symmetry_table": (_I, [_I, _I, _P, _P]),
     "mzgo_replay_sample": (_I, [_P, _I, ctypes.c_uint64, ctypes.c_uint32, _I, ctypes.c_double, _P, _P, _P, _P, _P]),
-    "mzgo_replay_sample_batch": (_I, [_P, _I, _I, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _I,
-                                      ctypes.c_double] + [_P] * 13),
     "mzgo_replay_batch_items": (_I, [_P, _P, _I, _I, ctypes.c_double] + [_P] * 9),
     "mzgo_replay_reanalyse_sample": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "mzgo_replay_window_items_host": (_I, [_P, _I, _P, _I, _I, _P, _P]),
-    "mzgo_replay_batch_values": (_I, [_P, _P, _P, _P, _I, _I, _I, ctypes.c_double] + [_P] * 6),
     "mzgo_replay_batch_items_values": (_I, [_P, _P, _I, _I, _I, ctypes.c_double] + [_P] * 6),
-    "mzgo_replay_sample_batch_values": (_I, [_P, _I, _I, _I, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _I,
-                                             ctypes.c_double] + [_P] * 10),
     "mzgo_replay_reanalyse_sample_values": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "mzgo_replay_value_targets_host": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_double, _P]),
     "mzgo_replay_window_items_values_host": (_I, [_P, _I, _P, _I, _I, _I, _P, _P]),
@@ -146,10 +141,6 @@ SIGNATURES = {
     "mzgo_replay_enable_positions": (_I, [_P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P]),
     "mzgo_replay_sample_positions": (_I, [_P, _I, ctypes.c_uint64, ctypes.c_uint32, _I, ctypes.c_double, _P, _P, _P,
                                           _P, _P]),
-    "mzgo_replay_sample_positions_batch": (_I, [_P, _I, _I, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _I,
-                                                ctypes.c_double] + [_P] * 13),
-    "mzgo_replay_sample_positions_batch_values": (_I, [_P, _I, _I, _I, ctypes.c_double, ctypes.c_uint64,
-                                                       ctypes.c_uint32, _I, ctypes.c_double] + [_P] * 10),
     "mzgo_replay_update_position_priorities": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
     "mzgo_replay_position_priorities": (_I, [_P, _P, _P]),
     "mzgo_replay_set_position_priorities": (_I, [_P, _P, _I, _P]),
@@ -175,7 +166,6 @@ SIGNATURES = {
     "mzgo_unroll_latents": (_I, [_I] * 6 + [ctypes.POINTER(ctypes.c_int64)] * 2),
     "mzgo_unroll_backward_l": (_I, [_P] * 5 + [_I] + [_P, ctypes.c_int64] + [_P] * 4 + [_I] * 5
                                + [_P, ctypes.c_int64, _I, _P]),
-    "mzgo_replay_ownership": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "mzgo_replay_ownership_items": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "mzgo_ownership_host": (_I, [_P, _I, _P]),
     "mzgo_ownership_targets_host": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
@@ -183,7 +173,6 @@ SIGNATURES = {
     "mzgo_ownership_loss": (_I, [_P] * 5 + [_I] * 4 + [ctypes.c_float] + [_P] * 4 + [ctypes.c_int64, _P]),
     "mzgo_ownership_loss_backward": (_I, [_P] * 5 + [_I] * 4 + [_P] * 4 + [ctypes.c_int64, _P]),
     "mzgo_ownership_loss_host": (_I, [_P] * 6 + [_I] * 4 + [ctypes.c_float] + [_P] * 6),
-    "mzgo_replay_window_obs": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "mzgo_replay_window_obs_items": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "mzgo_encode_workspace": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
     "mzgo_encode": (_I, [_P] * 4 + [_I] + [_P] + [_I] * 4 + [_P, _P, ctypes.c_int64, _P]),

@@ -9,7 +9,8 @@ until none is left) and comes back as root child visit counts, root values and
 visit-count policy targets.
 
 * ``positions_from_planes`` / ``record_ids`` -- observations and RNG keys in
-  the engine's record format; ``latest_first`` -- the order to queue them in;
+  the engine's record format (``observation_planes``: a record back to its
+  observation); ``latest_first`` -- the order to queue them in;
 * ``SelfPlay.reanalyse()`` (mzgo.selfplay) -- every recorded move of the
   current games, with the records' own keys;
 * ``Reanalyser`` -- main.py-format trajectories in, trajectories with fresh
@@ -30,7 +31,7 @@ def positions_from_planes(obs):
     """GoEnv observations [n, 6, N, N] (black, white, turn, invalid, passed,
     done) -> (stones int8 [n, N*N]: 0 / 1 black / 2 white, invd uint8
     [n, N*N], flags uint8 [n]: bit0 turn, bit1 passed, bit2 done): the
-    engine's record format, the inverse of ``trainer._planes``.  Takes a
+    engine's record format, the inverse of ``observation_planes``.  Takes a
     tensor, an array or a sequence of [6, N, N] arrays; returns torch tensors
     on the input's device (the CPU unless ``obs`` is a CUDA tensor)."""
     if not isinstance(obs, torch.Tensor):
@@ -44,6 +45,23 @@ def positions_from_planes(obs):
     bit = [on[:, c].reshape(n, -1).any(dim=1).to(torch.uint8) for c in (2, 4, 5)]
     flags = bit[0] | (bit[1] << 1) | (bit[2] << 2)
     return stones.contiguous(), invd.contiguous(), flags.contiguous()
+
+
+def observation_planes(stones, invd, flags, N):
+    """One stored position (stones [N*N]: 0 / 1 black / 2 white, invd [N*N],
+    flags: bit0 turn, bit1 passed, bit2 done) -> its GoEnv observation, float64
+    [6, N, N]: the inverse of ``positions_from_planes`` and the host form of
+    the store's plane rule (csrc/mzgo_replay.hpp ``observation_plane``)."""
+    flags = int(flags)
+    o = np.zeros((6, N, N))
+    s = np.asarray(stones).reshape(N, N)
+    o[0] = s == 1
+    o[1] = s == 2
+    o[2] = flags & 1
+    o[3] = np.asarray(invd).reshape(N, N)
+    o[4] = (flags >> 1) & 1
+    o[5] = (flags >> 2) & 1
+    return o
 
 
 def record_ids(game_base, g, epoch, moves):

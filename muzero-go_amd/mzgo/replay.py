@@ -9,7 +9,9 @@ flags u8: 2 N^2 + 1 bytes per position against 48 N^2 for the f64 planes),
 and serves both consumers of stored games from there:
 
 * ``batch``     -- one launch (k_replay_batch) writes the trainer's targets for
-  B (game, start, symmetry) samples; ``finish_values`` adds the bootstrap;
+  B (game, start, symmetry) samples (``items`` checks and uploads them once,
+  ``batch_from`` and the other ``*_from`` assemblies take the device items);
+  ``finish_values`` adds the bootstrap;
   ``batch_values`` -- the same with search-value targets: n-step returns
   bootstrapped from the stored root values, no bootstrap inference
   (``TrainConfig.value_target="search"``; ``value_targets_host`` is the rule);
@@ -59,7 +61,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib, ptr, stream_of
-from .reanalyse import FLAG_FAST, positions_from_planes
+from .reanalyse import FLAG_FAST, observation_planes, positions_from_planes
 
 
 def symmetry_tables(board_size, symmetry):
@@ -421,7 +423,6 @@ class DeviceReplay:
         actions, T policies, T+1 rewards, plus ``root_values`` and ``key_gid``
         -- and ``fast_search`` (T bools) when at least one move's row is a
         fast-budget search that no reanalysis has rewritten."""
-        from .trainer import _planes
         M, C, A, N = self.max_moves, self.N * self.N, self.A, self.N
         length, gid = ctypes.c_int32(), ctypes.c_int32()
         stones = np.empty((M + 1, C), np.int8)
@@ -436,7 +437,7 @@ class DeviceReplay:
                                      ptr(stones), ptr(invd), ptr(flags), ptr(action), ptr(policy), ptr(reward),
                                      ptr(rv), stream_of(self.device)))
         T = length.value
-        obs = [_planes(stones[t], invd[t], int(flags[t]), N) for t in range(T + 1)]
+        obs = [observation_planes(stones[t], invd[t], flags[t], N) for t in range(T + 1)]
         out = {
             "observations": obs + [obs[-1].copy()],
             "actions": [int(a) for a in action[:T]],
@@ -451,34 +452,33 @@ class DeviceReplay:
         return out
 
     # ---- the trainer's batch ----
-    def batch(self, indices, starts, unroll_steps, discount, symmetries=None):
-        """The trainer's targets for B samples in one launch (mzgo_replay_batch):
-        sample b is game ``indices[b]`` from move ``starts[b]`` under symmetry
-        ``symmetries[b]`` (0..7; None = identity).  Returns a dict of CUDA
-        tensors: ``obs0`` f32 [B,6,N,N], ``boot_obs`` f32 [B,K+1,6,N,N],
-        ``acts`` i64 [B,K], ``t_rew`` f32 [B,K], ``t_pol`` f32 [B,K+1,A],
-        ``val`` / ``factor`` f64 [B,K+1] and ``has_boot`` u8 [B,K+1]
-        (``finish_values`` turns the last three and the network's values of
-        ``boot_obs`` into ``t_val``)."""
+    def items(self, indices, starts, symmetries=None):
+        """The device item list of B samples given on the host
+        (mzgo_replay_items): sample b is game ``indices[b]`` (0 = oldest) from
+        move ``starts[b]`` under symmetry ``symmetries[b]`` (0..7; None =
+        identity), checked against the store's lengths.  Returns a CUDA i32
+        tensor [B,3] of (slot, start, symmetry) rows, what ``sample`` returns as
+        ``items``: one check and one upload for every ``*_from`` assembly of
+        the same samples."""
         idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int32).reshape(-1))
-        B, K, N, A, dev = len(idx), int(unroll_steps), self.N, self.A, self.device
         st = np.ascontiguousarray(np.asarray(starts, dtype=np.int32).reshape(-1))
         sy = None if symmetries is None else np.ascontiguousarray(np.asarray(symmetries, dtype=np.int32).reshape(-1))
-        if len(st) != B or (sy is not None and len(sy) != B):
-            raise ValueError("batch: indices, starts and symmetries must have one entry per sample")
-        K1 = max(K, 0) + 1
-        out = dict(obs0=torch.empty(B, 6, N, N, device=dev),
-                   boot_obs=torch.empty(B, K1, 6, N, N, device=dev),
-                   acts=torch.empty(B, max(K, 0), dtype=torch.int64, device=dev),
-                   t_rew=torch.empty(B, max(K, 0), device=dev),
-                   t_pol=torch.empty(B, K1, A, device=dev),
-                   val=torch.empty(B, K1, dtype=torch.float64, device=dev),
-                   factor=torch.empty(B, K1, dtype=torch.float64, device=dev),
-                   has_boot=torch.empty(B, K1, dtype=torch.uint8, device=dev))
-        check(lib.mzgo_replay_batch(self._h, ptr(idx), ptr(st), ptr(sy), B, K, float(discount), ptr(out["obs0"]),
-                                    ptr(out["boot_obs"]), ptr(out["acts"]), ptr(out["t_rew"]), ptr(out["t_pol"]),
-                                    ptr(out["val"]), ptr(out["factor"]), ptr(out["has_boot"]), stream_of(dev)))
-        return out
+        if len(st) != len(idx) or (sy is not None and len(sy) != len(idx)):
+            raise ValueError("indices, starts and symmetries must have one entry per sample")
+        items = torch.empty(len(idx), 3, dtype=torch.int32, device=self.device)
+        check(lib.mzgo_replay_items(self._h, ptr(idx), ptr(st), ptr(sy), len(idx), ptr(items), stream_of(self.device)))
+        return items
+
+    def batch(self, indices, starts, unroll_steps, discount, symmetries=None):
+        """The trainer's targets for B samples in one launch (``items``, then
+        ``batch_from``): sample b is game ``indices[b]`` from move ``starts[b]``
+        under symmetry ``symmetries[b]`` (0..7; None = identity).  Returns a
+        dict of CUDA tensors: ``obs0`` f32 [B,6,N,N], ``boot_obs`` f32
+        [B,K+1,6,N,N], ``acts`` i64 [B,K], ``t_rew`` f32 [B,K], ``t_pol`` f32
+        [B,K+1,A], ``val`` / ``factor`` f64 [B,K+1] and ``has_boot`` u8 [B,K+1]
+        (``finish_values`` turns the last three and the network's values of
+        ``boot_obs`` into ``t_val``)."""
+        return self.batch_from(self.items(indices, starts, symmetries), unroll_steps, discount)
 
     def _values_out(self, B, K):
         N, A, dev, K1 = self.N, self.A, self.device, max(K, 0) + 1
@@ -489,28 +489,18 @@ class DeviceReplay:
                     t_val=torch.empty(B, K1, device=dev))
 
     def batch_values(self, indices, starts, unroll_steps, td_steps, discount, symmetries=None):
-        """``batch`` with search-value targets (mzgo_replay_batch_values, one
-        launch, nothing to finish): ``obs0``, ``acts``, ``t_rew`` and ``t_pol``
-        as ``batch`` gives them, and ``t_val`` f32 [B,K+1] -- the n-step returns
-        (n = ``td_steps`` >= 1, independent of K) bootstrapped from the stored
-        root values, ``value_targets_host``'s bits.  No ``boot_obs``, ``val``,
-        ``factor`` or ``has_boot``."""
-        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int32).reshape(-1))
-        B, K = len(idx), int(unroll_steps)
-        st = np.ascontiguousarray(np.asarray(starts, dtype=np.int32).reshape(-1))
-        sy = None if symmetries is None else np.ascontiguousarray(np.asarray(symmetries, dtype=np.int32).reshape(-1))
-        if len(st) != B or (sy is not None and len(sy) != B):
-            raise ValueError("batch_values: indices, starts and symmetries must have one entry per sample")
-        out = self._values_out(B, K)
-        check(lib.mzgo_replay_batch_values(self._h, ptr(idx), ptr(st), ptr(sy), B, K, int(td_steps), float(discount),
-                                           ptr(out["obs0"]), ptr(out["acts"]), ptr(out["t_rew"]), ptr(out["t_pol"]),
-                                           ptr(out["t_val"]), stream_of(self.device)))
-        return out
+        """``batch`` with search-value targets (``items``, then
+        ``batch_values_from``: one launch, nothing to finish): ``obs0``,
+        ``acts``, ``t_rew`` and ``t_pol`` as ``batch`` gives them, and ``t_val``
+        f32 [B,K+1] -- the n-step returns (n = ``td_steps`` >= 1, independent of
+        K) bootstrapped from the stored root values, ``value_targets_host``'s
+        bits.  No ``boot_obs``, ``val``, ``factor`` or ``has_boot``."""
+        return self.batch_values_from(self.items(indices, starts, symmetries), unroll_steps, td_steps, discount)
 
     # ---- ownership targets ----
     def ownership(self, indices, starts, unroll_steps, symmetries=None):
-        """The ownership targets of B samples in one launch
-        (mzgo_replay_ownership; ``batch``'s indices, starts and symmetries):
+        """The ownership targets of B samples in one launch (``items``, then
+        ``ownership_from``; ``batch``'s indices, starts and symmetries):
         ``(t_own f32 [B, K+1, N*N], own_mask f32 [B, K+1])`` on the device.
         Row (b, k) is the final board of sample b's game seen by the colour to
         move at position start + k under the sample's symmetry: +1 the mover
@@ -518,16 +508,7 @@ class DeviceReplay:
         mask 0 past the final board and for a game that did not end (a game cut
         off by the move cap has no winner and no ownership).
         ``ownership_targets_host`` is the rule; the batch assembly is untouched."""
-        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int32).reshape(-1))
-        B, K = len(idx), int(unroll_steps)
-        st = np.ascontiguousarray(np.asarray(starts, dtype=np.int32).reshape(-1))
-        sy = None if symmetries is None else np.ascontiguousarray(np.asarray(symmetries, dtype=np.int32).reshape(-1))
-        if len(st) != B or (sy is not None and len(sy) != B):
-            raise ValueError("ownership: indices, starts and symmetries must have one entry per sample")
-        t_own, mask = self._ownership_out(B, K)
-        check(lib.mzgo_replay_ownership(self._h, ptr(idx), ptr(st), ptr(sy), B, K, ptr(t_own), ptr(mask),
-                                        stream_of(self.device)))
-        return t_own, mask
+        return self.ownership_from(self.items(indices, starts, symmetries), unroll_steps)
 
     def ownership_from(self, sample, unroll_steps):
         """``ownership`` for a drawn ``sample`` (what ``sample`` / ``sample_batch``
@@ -547,8 +528,8 @@ class DeviceReplay:
 
     # ---- the real boards of a window (the consistency loss's targets) ----
     def window_obs(self, indices, starts, unroll_steps, symmetries=None):
-        """The real boards of B sampled windows in one launch
-        (mzgo_replay_window_obs; ``batch``'s indices, starts and symmetries):
+        """The real boards of B sampled windows in one launch (``items``, then
+        ``window_obs_from``; ``batch``'s indices, starts and symmetries):
         ``(obs f32 [K, B, 6, N, N], mask f32 [B, K])`` on the device.
         ``obs[k-1, b]`` is the observation of position start + k of sample b's
         game under the sample's symmetry, k = 1..K -- the six planes ``batch``
@@ -557,17 +538,7 @@ class DeviceReplay:
         lines up with the unroll's ``latents[1:]``.  ``mask[b, k-1]`` is 1 where
         start + k <= the game's length (the final board counts); past it the
         planes are zeros and the mask 0.  At K = 0: empty tensors, no launch."""
-        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int32).reshape(-1))
-        B, K = len(idx), int(unroll_steps)
-        st = np.ascontiguousarray(np.asarray(starts, dtype=np.int32).reshape(-1))
-        sy = None if symmetries is None else np.ascontiguousarray(np.asarray(symmetries, dtype=np.int32).reshape(-1))
-        if len(st) != B or (sy is not None and len(sy) != B):
-            raise ValueError("window_obs: indices, starts and symmetries must have one entry per sample")
-        obs, mask = self._window_obs_out(B, K)
-        if K > 0:
-            check(lib.mzgo_replay_window_obs(self._h, ptr(idx), ptr(st), ptr(sy), B, K, ptr(obs), ptr(mask),
-                                             stream_of(self.device)))
-        return obs, mask
+        return self.window_obs_from(self.items(indices, starts, symmetries), unroll_steps)
 
     def window_obs_from(self, sample, unroll_steps):
         """``window_obs`` for a drawn ``sample`` (what ``sample`` / ``sample_batch``
@@ -618,7 +589,7 @@ class DeviceReplay:
         bits) and ``weight`` f32 [B] (importance weights, all 1 at beta 0)."""
         return self._sample(False, batch_size, _draw_args(seed, step, symmetries, beta))
 
-    # the three sample calls, for the game sampler and (``positions``) the position sampler
+    # the draw, and the draw followed by either assembly, for the game sampler and (``positions``) the position sampler
     def _sample(self, positions, batch_size, draw):
         B = int(batch_size)
         s = self._sample_out(B)
@@ -628,30 +599,17 @@ class DeviceReplay:
         return s
 
     def _sample_batch(self, positions, batch_size, unroll_steps, discount, draw):
-        B, K = int(batch_size), int(unroll_steps)
-        out = self._batch_out(B, K)
-        out.update(self._sample_out(B))
-        fn = lib.mzgo_replay_sample_positions_batch if positions else lib.mzgo_replay_sample_batch
-        check(fn(self._h, B, K, float(discount), *draw, ptr(out["items"]), ptr(out["index"]), ptr(out["gen"]),
-                 ptr(out["weight"]), ptr(out["obs0"]), ptr(out["boot_obs"]), ptr(out["acts"]), ptr(out["t_rew"]),
-                 ptr(out["t_pol"]), ptr(out["val"]), ptr(out["factor"]), ptr(out["has_boot"]), stream_of(self.device)))
-        return out
+        s = self._sample(positions, batch_size, draw)
+        return {**self.batch_from(s, unroll_steps, discount), **s}
 
     def _sample_batch_values(self, positions, batch_size, unroll_steps, td_steps, discount, draw):
-        B, K = int(batch_size), int(unroll_steps)
-        out = self._values_out(B, K)
-        out.update(self._sample_out(B))
-        fn = lib.mzgo_replay_sample_positions_batch_values if positions else lib.mzgo_replay_sample_batch_values
-        check(fn(self._h, B, K, int(td_steps), float(discount), *draw, ptr(out["items"]), ptr(out["index"]),
-                 ptr(out["gen"]), ptr(out["weight"]), ptr(out["obs0"]), ptr(out["acts"]), ptr(out["t_rew"]),
-                 ptr(out["t_pol"]), ptr(out["t_val"]), stream_of(self.device)))
-        return out
+        s = self._sample(positions, batch_size, draw)
+        return {**self.batch_values_from(s, unroll_steps, td_steps, discount), **s}
 
     def sample_batch(self, batch_size, unroll_steps, discount, *, seed, step, symmetries=False, beta=0.0):
-        """``sample`` and ``batch`` in one call without the host
-        (mzgo_replay_sample_batch): ``batch``'s dict for the sampled (game,
-        start, symmetry) triples plus ``sample``'s ``items``, ``index``,
-        ``gen`` and ``weight``.  The draw depends on (seed, step) and the
+        """``sample`` and ``batch_from`` in one call without the host:
+        ``batch``'s dict for the sampled (game, start, symmetry) triples plus
+        ``sample``'s ``items``, ``index``, ``gen`` and ``weight``.  The draw depends on (seed, step) and the
         device weights only; it is ``sample_host``'s, bit for bit."""
         return self._sample_batch(False, batch_size, unroll_steps, discount, _draw_args(seed, step, symmetries, beta))
 
@@ -672,9 +630,9 @@ class DeviceReplay:
 
     def sample_batch_values(self, batch_size, unroll_steps, td_steps, discount, *, seed, step, symmetries=False,
                             beta=0.0):
-        """``sample`` and ``batch_values`` in one call without the host
-        (mzgo_replay_sample_batch_values): ``sample_batch``'s draw, with
-        ``batch_values``' five tensors for the sampled triples."""
+        """``sample`` and ``batch_values_from`` in one call without the host:
+        ``sample_batch``'s draw, with ``batch_values``' five tensors for the
+        sampled triples."""
         return self._sample_batch_values(False, batch_size, unroll_steps, td_steps, discount,
                                          _draw_args(seed, step, symmetries, beta))
 
@@ -782,14 +740,12 @@ class DeviceReplay:
         return self._sample(True, batch_size, _draw_args(seed, step, symmetries, beta))
 
     def sample_positions_batch(self, batch_size, unroll_steps, discount, *, seed, step, symmetries=False, beta=0.0):
-        """``sample_batch`` with the position sampler's draw
-        (mzgo_replay_sample_positions_batch)."""
+        """``sample_batch`` with the position sampler's draw."""
         return self._sample_batch(True, batch_size, unroll_steps, discount, _draw_args(seed, step, symmetries, beta))
 
     def sample_positions_batch_values(self, batch_size, unroll_steps, td_steps, discount, *, seed, step,
                                       symmetries=False, beta=0.0):
-        """``sample_batch_values`` with the position sampler's draw
-        (mzgo_replay_sample_positions_batch_values)."""
+        """``sample_batch_values`` with the position sampler's draw."""
         return self._sample_batch_values(True, batch_size, unroll_steps, td_steps, discount,
                                          _draw_args(seed, step, symmetries, beta))
 

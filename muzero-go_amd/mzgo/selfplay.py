@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .net import MuZeroNet
-from .reanalyse import FLAG_FAST
+from .reanalyse import FLAG_FAST, observation_planes
 from .weights import deterministic_state_dict
 
 
@@ -78,17 +78,9 @@ def history_from_device(rec, board_size, discount):
     acts = [int(a) for a in rec["action"]]
     ended = L >= 2 and acts[-1] == pass_a and acts[-2] == pass_a
     for t in range(L):
-        o = np.zeros((6, N, N))
-        s = rec["stones"][t].reshape(N, N)
         f = int(rec["flags"][t])
-        o[0] = s == 1
-        o[1] = s == 2
-        o[2] = f & 1
-        o[3] = rec["invd"][t].reshape(N, N)
-        o[4] = (f >> 1) & 1
-        o[5] = (f >> 2) & 1
         last = t == L - 1
-        h.observations.append(o)
+        h.observations.append(observation_planes(rec["stones"][t], rec["invd"][t], f, N))
         h.actions.append(acts[t])
         h.policies.append(np.array(rec["policy"][t], dtype=np.float64))
         h.values.append(float(rec["value"][t]))

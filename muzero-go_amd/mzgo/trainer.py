@@ -158,7 +158,7 @@ import torch
 import torch.nn.functional as F
 
 from .net import MuZeroNet
-from .reanalyse import FLAG_FAST
+from .reanalyse import FLAG_FAST, observation_planes
 from .selfplay import SelfPlay
 
 
@@ -435,16 +435,7 @@ class MultiVersionReplayBuffer:
 # ---------------------------------------------------------------------------
 # trajectories in main.py's format
 # ---------------------------------------------------------------------------
-def _planes(stones, invd, flags, N):
-    o = np.zeros((6, N, N))
-    s = np.asarray(stones).reshape(N, N)
-    o[0] = s == 1
-    o[1] = s == 2
-    o[2] = flags & 1
-    o[3] = np.asarray(invd).reshape(N, N)
-    o[4] = (flags >> 1) & 1
-    o[5] = (flags >> 2) & 1
-    return o
+_planes = observation_planes             # (the name tests import)
 
 
 def trajectory_from_record(rec, final_obs, board_size, max_moves):
@@ -927,11 +918,11 @@ class MuZeroTrainer:
         indices = replay.sample_indices(batch_size)
         starts = [self.start_index(replay.lengths[i]) for i in indices]
         syms = [self.symmetry_index() for _ in indices] if self.config.symmetries else None
-        own = (replay.ownership(indices, starts, self.config.unroll_steps, syms)
-               if self.ownership_head is not None else None)
-        cons = (replay.window_obs(indices, starts, self.config.unroll_steps, syms)
-                if self.consistency_head is not None else None)
-        avg = self._unroll_step(*self.device_targets(replay, indices, starts, syms), device_totals=True, ownership=own,
+        # one check and one upload of the samples for every assembly of the step
+        items, K = replay.items(indices, starts, syms), self.config.unroll_steps
+        own = replay.ownership_from(items, K) if self.ownership_head is not None else None
+        cons = replay.window_obs_from(items, K) if self.consistency_head is not None else None
+        avg = self._unroll_step(*self._targets_from(replay, items), device_totals=True, ownership=own,
                                 consistency=cons)
         replay.update_priorities(indices, self._priorities(avg, len(indices)))
         self._scheduler_step()
@@ -947,9 +938,10 @@ class MuZeroTrainer:
         step, with one blocking copy per tensor, unless ``device_weights`` is
         set: only then is a ``deferred_stats`` step free of synchronisation.
 
-        With ``reanalyse_sample`` the step is sample -> ``reanalyser.refresh()``
-        -> ``reanalyse_sample`` -> ``batch_from`` (on the steps with
-        ``sample_step % reanalyse_every == 0``; ``sample_batch`` on the others):
+        Every step is draw -> assemble (``sample`` or ``sample_positions``, then
+        ``_targets_from``); with ``reanalyse_sample``, ``reanalyser.refresh()``
+        and ``reanalyse_sample`` run between the two (on the steps with
+        ``sample_step % reanalyse_every == 0``):
         the policy rows the batch is about to read are searched under the
         current weights, in the store, before the targets are assembled.  The
         refresh goes through the host (one blocking copy per tensor) without
@@ -957,44 +949,32 @@ class MuZeroTrainer:
         assembly never synchronise.
 
         With ``value_target="search"`` the assembly writes ``t_val`` itself from
-        the stored root values (``sample_batch_values``; with
-        ``reanalyse_sample``: ``reanalyse_sample(td_steps=...)``, which also
-        searches the rows the value targets read, then ``batch_values_from``):
+        the stored root values (``batch_values_from``; with
+        ``reanalyse_sample``: after ``reanalyse_sample(td_steps=...)``, which also
+        searches the rows the value targets read):
         no bootstrap rows, no ``initial_inference``, no ``finish_values``, and
         so no weight reload on the step's own account."""
-        from .replay import finish_values
-        c, N, td = self.config, self.net.board_size, self.td_steps
+        c, td = self.config, self.td_steps
         draw = dict(seed=self.sample_seed, step=self.sample_step, symmetries=c.symmetries, beta=c.importance_beta)
-        sampler = "sample"                  # the store's three sample calls: <sampler>, _batch, _batch_values
+        sample = replay.sample
         if c.position_priorities:
             # (a no-op after the first step; the store refuses other parameters than it was enabled with)
             replay.enable_position_priorities(td or c.unroll_steps, c.discount, alpha=c.priority_alpha,
                                               floor=c.priority_floor or None)
-            sampler = "sample_positions"
+            sample = replay.sample_positions
+        s = sample(batch_size, **draw)
         if c.reanalyse_sample and self.sample_step % c.reanalyse_every == 0:
-            s = getattr(replay, sampler)(batch_size, **draw)
             self.reanalyser.refresh()
             self.last_searched_device = replay.reanalyse_sample(self.reanalyser, s, c.unroll_steps, td_steps=td)
-            s.update(replay.batch_from(s, c.unroll_steps, c.discount) if td is None
-                     else replay.batch_values_from(s, c.unroll_steps, td, c.discount))
-        elif td is None:
-            s = getattr(replay, sampler + "_batch")(batch_size, c.unroll_steps, c.discount, **draw)
-        else:
-            s = getattr(replay, sampler + "_batch_values")(batch_size, c.unroll_steps, td, c.discount, **draw)
         self.sample_step += 1
-        if td is None:
-            with torch.no_grad():
-                _, v, _ = self.net.initial_inference(s["boot_obs"].view(-1, 6, N, N))
-            t_val = finish_values(s["val"], s["factor"], s["has_boot"], v)
-        else:                               # value_target="search": the assembly wrote the targets
-            t_val = s["t_val"]
+        obs0, acts, t_val, t_rew, t_pol = self._targets_from(replay, s)
         self.last_t_val_device = t_val
         # the ownership targets of the same items: one more small launch, nothing on the host
         own = replay.ownership_from(s, c.unroll_steps) if self.ownership_head is not None else None
         # the real boards of the same items' windows (the consistency loss's targets): one more small launch
         cons = replay.window_obs_from(s, c.unroll_steps) if self.consistency_head is not None else None
-        avg = self._unroll_step(s["obs0"], s["acts"], t_val, s["t_rew"], s["t_pol"], device_totals=True,
-                                device_sample=(replay, s), ownership=own, consistency=cons)
+        avg = self._unroll_step(obs0, acts, t_val, t_rew, t_pol, device_totals=True, device_sample=(replay, s),
+                                ownership=own, consistency=cons)
         self._scheduler_step()
         return avg
 
@@ -1045,12 +1025,18 @@ class MuZeroTrainer:
         one ``initial_inference`` over all B (K+1) bootstrap rows (a workgroup
         per row, so a row's value does not depend on its neighbours), one
         finishing launch.  Nothing comes back to the host."""
+        return self._targets_from(replay, replay.items(indices, starts, symmetries))
+
+    def _targets_from(self, replay, sample):
+        """(obs0, acts, t_val, t_rew, t_pol) for a sample's device items: the
+        assembly and, for network value targets, the bootstrap inference and
+        the finishing launch."""
         from .replay import finish_values
         c, N = self.config, self.net.board_size
         if self.td_steps is not None:       # value_target="search": one launch, no inference, nothing to finish
-            bt = replay.batch_values(indices, starts, c.unroll_steps, self.td_steps, c.discount, symmetries)
+            bt = replay.batch_values_from(sample, c.unroll_steps, self.td_steps, c.discount)
             return bt["obs0"], bt["acts"], bt["t_val"], bt["t_rew"], bt["t_pol"]
-        bt = replay.batch(indices, starts, c.unroll_steps, c.discount, symmetries)
+        bt = replay.batch_from(sample, c.unroll_steps, c.discount)
         with torch.no_grad():
             _, v, _ = self.net.initial_inference(bt["boot_obs"].view(-1, 6, N, N))
         t_val = finish_values(bt["val"], bt["factor"], bt["has_boot"], v)
@@ -1131,7 +1117,7 @@ class MuZeroTrainer:
         loss, the totals and the heads' gradients from ``mzgo.unroll_loss``
         instead (``_unroll_step_fused``); ``sample_priorities`` keeps the
         per-sample losses in ``last_per_sample`` (in that same copy).  With
-        ``device_sample`` = (the store, what its ``sample_batch`` returned) the
+        ``device_sample`` = (the store, what its ``sample`` returned) the
         losses and totals stay on the device (``_finish_device``) and the loss
         is weighted by the sample's importance weights when
         ``importance_beta`` > 0."""

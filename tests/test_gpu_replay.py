@@ -333,26 +333,39 @@ def test_refusals():
                factor=torch.zeros(2, K + 1, dtype=torch.float64, device=dev),
                has_boot=torch.zeros(2, K + 1, dtype=torch.uint8, device=dev))
 
-    def call(handle=rp.handle, idx=(0, 1), starts=(0, 1), syms=None, B=2, unroll=K, drop=None):
+    items = torch.zeros(2, 3, dtype=torch.int32, device=dev)
+
+    # the samples' checks are mzgo_replay_items', the outputs' mzgo_replay_batch_items'
+    def upload(handle=rp.handle, idx=(0, 1), starts=(0, 1), syms=None, B=2, it=items):
         i32 = lambda x: None if x is None else np.array(x, np.int32)
         a, b, c = i32(idx), i32(starts), i32(syms)
-        o = {k: (None if k == drop else ptr(v)) for k, v in out.items()}
-        rc = lib.mzgo_replay_batch(handle, ptr(a), ptr(b), ptr(c), B, unroll, 0.99, o["obs0"], o["boot_obs"],
-                                   o["acts"], o["t_rew"], o["t_pol"], o["val"], o["factor"], o["has_boot"],
-                                   stream_of(dev))
+        rc = lib.mzgo_replay_items(handle, ptr(a), ptr(b), ptr(c), B, ptr(it), stream_of(dev))
         torch.cuda.synchronize()
         return rc, lib.mzgo_last_error().decode()
 
-    assert call()[0] == MZGO_OK
+    def call(handle=rp.handle, it=items, B=2, unroll=K, drop=None):
+        o = {k: (None if k == drop else ptr(v)) for k, v in out.items()}
+        rc = lib.mzgo_replay_batch_items(handle, ptr(it), B, unroll, 0.99, o["obs0"], o["boot_obs"], o["acts"],
+                                         o["t_rew"], o["t_pol"], o["val"], o["factor"], o["has_boot"], stream_of(dev))
+        torch.cuda.synchronize()
+        return rc, lib.mzgo_last_error().decode()
+
+    assert upload()[0] == MZGO_OK and call()[0] == MZGO_OK
+    assert items.cpu().tolist() == [[0, 0, 0], [1, 1, 0]]
     for kwargs, word in ((dict(handle=None), "null replay"), (dict(B=0), "B must be >= 1"),
                          (dict(idx=None), "null indices"), (dict(starts=None), "null starts"),
-                         (dict(drop="t_pol"), "null t_pol"), (dict(drop="has_boot"), "null has_boot"),
+                         (dict(it=None), "null items"),
                          (dict(idx=(0, 2)), "game 2 is not in the store"), (dict(idx=(-1, 0)), "game -1"),
                          (dict(starts=(T0, 0)), f"start {T0} outside"), (dict(starts=(0, -1)), "start -1 outside"),
-                         (dict(syms=(0, 8)), "symmetry 8"), (dict(syms=(-1, 0)), "symmetry -1"),
+                         (dict(syms=(0, 8)), "symmetry 8"), (dict(syms=(-1, 0)), "symmetry -1")):
+        rc, msg = upload(**kwargs)
+        assert rc == MZGO_EINVAL and "mzgo_replay_items" in msg and word in msg, (kwargs, rc, msg)
+    for kwargs, word in ((dict(handle=None), "null replay"), (dict(B=0), "B must be >= 1"),
+                         (dict(it=None), "null items"),
+                         (dict(drop="t_pol"), "null t_pol"), (dict(drop="has_boot"), "null has_boot"),
                          (dict(unroll=0), "unroll_steps 0"), (dict(unroll=64), "unroll_steps 64")):
         rc, msg = call(**kwargs)
-        assert rc == MZGO_EINVAL and word in msg, (kwargs, rc, msg)
+        assert rc == MZGO_EINVAL and "mzgo_replay_batch_items" in msg and word in msg, (kwargs, rc, msg)
     with pytest.raises((mzgo.MzgoError, IndexError)):
         rp.batch([0, 5], [0, 0], K, 0.99)
     # ingest: engines the store cannot take

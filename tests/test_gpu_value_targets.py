@@ -287,26 +287,25 @@ def test_refusals():
     items = torch.tensor([[0, 0, 0], [1, 2, 3]], dtype=torch.int32, device=dev)
     T0 = len(trajs[0]["actions"])
 
-    def host(handle=rp.handle, idx=(0, 1), starts=(0, 1), syms=None, B=2, unroll=K, td=K, drop=None):
+    # host samples: the samples' checks are mzgo_replay_items', the rest mzgo_replay_batch_items_values' (below)
+    up = torch.zeros(2, 3, dtype=torch.int32, device=dev)
+
+    def host(handle=rp.handle, idx=(0, 1), starts=(0, 1), syms=None, B=2, it=up):
         i32 = lambda x: None if x is None else np.array(x, np.int32)
         a, b, c = i32(idx), i32(starts), i32(syms)
-        o = {k: (None if k == drop else ptr(v)) for k, v in out.items()}
-        rc = lib.mzgo_replay_batch_values(handle, ptr(a), ptr(b), ptr(c), B, unroll, td, 0.99, o["obs0"], o["acts"],
-                                          o["t_rew"], o["t_pol"], o["t_val"], s)
+        rc = lib.mzgo_replay_items(handle, ptr(a), ptr(b), ptr(c), B, ptr(it), s)
         torch.cuda.synchronize()
         return rc, lib.mzgo_last_error().decode()
 
-    assert host()[0] == MZGO_OK
+    assert host()[0] == MZGO_OK and up.cpu().tolist() == [[0, 0, 0], [1, 1, 0]]
     for kwargs, word in ((dict(handle=None), "null replay"), (dict(B=0), "B must be >= 1"),
                          (dict(idx=None), "null indices"), (dict(starts=None), "null starts"),
-                         (dict(drop="t_pol"), "null t_pol"), (dict(drop="t_val"), "null t_val"),
+                         (dict(it=None), "null items"),
                          (dict(idx=(0, 2)), "game 2 is not in the store"), (dict(idx=(-1, 0)), "game -1"),
                          (dict(starts=(T0, 0)), f"start {T0} outside"), (dict(starts=(0, -1)), "start -1 outside"),
-                         (dict(syms=(0, 8)), "symmetry 8"), (dict(unroll=0), "unroll_steps 0"),
-                         (dict(unroll=64), "unroll_steps 64"), (dict(td=0), "td_steps must be >= 1"),
-                         (dict(td=-3), "td_steps must be >= 1")):
+                         (dict(syms=(0, 8)), "symmetry 8")):
         rc, msg = host(**kwargs)
-        assert rc == MZGO_EINVAL and "mzgo_replay_batch_values" in msg and word in msg, (kwargs, rc, msg)
+        assert rc == MZGO_EINVAL and "mzgo_replay_items" in msg and word in msg, (kwargs, rc, msg)
 
     def dev_items(handle=rp.handle, it=items, B=2, unroll=K, td=K, drop=None):
         o = {k: (None if k == drop else ptr(v)) for k, v in out.items()}
@@ -319,27 +318,26 @@ def test_refusals():
     for kwargs, word in ((dict(handle=None), "null replay"), (dict(it=None), "null items"),
                          (dict(B=0), "B must be >= 1"), (dict(unroll=0), "unroll_steps 0"),
                          (dict(unroll=64), "unroll_steps 64"), (dict(td=0), "td_steps must be >= 1"),
-                         (dict(drop="obs0"), "null obs0"), (dict(drop="t_val"), "null t_val")):
+                         (dict(td=-3), "td_steps must be >= 1"), (dict(drop="obs0"), "null obs0"),
+                         (dict(drop="t_pol"), "null t_pol"), (dict(drop="t_rew"), "null t_rew"),
+                         (dict(drop="t_val"), "null t_val")):
         rc, msg = dev_items(**kwargs)
         assert rc == MZGO_EINVAL and "mzgo_replay_batch_items_values" in msg and word in msg, (kwargs, rc, msg)
 
     so = rp._sample_out(2)
 
-    def sampled(handle=rp.handle, B=2, unroll=K, td=K, beta=0.0, drop=None):
-        o = {k: (None if k == drop else ptr(v)) for k, v in {**out, **so}.items()}
-        rc = lib.mzgo_replay_sample_batch_values(handle, B, unroll, td, 0.99, 1, 0, 0, beta, o["items"], o["index"],
-                                                 o["gen"], o["weight"], o["obs0"], o["acts"], o["t_rew"], o["t_pol"],
-                                                 o["t_val"], s)
+    # a sampled batch: the draw's checks are mzgo_replay_sample's, the assembly's are dev_items' above
+    def sampled(handle=rp.handle, B=2, beta=0.0, drop=None):
+        o = {k: (None if k == drop else ptr(v)) for k, v in so.items()}
+        rc = lib.mzgo_replay_sample(handle, B, 1, 0, 0, beta, o["items"], o["index"], o["gen"], o["weight"], s)
         torch.cuda.synchronize()
         return rc, lib.mzgo_last_error().decode()
 
-    assert sampled()[0] == MZGO_OK
+    assert sampled()[0] == MZGO_OK and dev_items(it=so["items"])[0] == MZGO_OK
     for kwargs, word in ((dict(handle=None), "null replay"), (dict(B=0), "B must be >= 1"), (dict(B=3), "B 3 exceeds"),
-                         (dict(unroll=64), "unroll_steps 64"), (dict(td=0), "td_steps must be >= 1"),
-                         (dict(beta=-1.0), "beta"), (dict(drop="items"), "null items"),
-                         (dict(drop="t_rew"), "null t_rew")):
+                         (dict(beta=-1.0), "beta"), (dict(drop="items"), "null items")):
         rc, msg = sampled(**kwargs)
-        assert rc == MZGO_EINVAL and "mzgo_replay_sample_batch_values" in msg and word in msg, (kwargs, rc, msg)
+        assert rc == MZGO_EINVAL and "mzgo_replay_sample" in msg and word in msg, (kwargs, rc, msg)
 
     ra = _reanalyser(_net(N, C))
     count = torch.zeros(1, dtype=torch.int32, device=dev)

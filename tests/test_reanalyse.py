@@ -33,6 +33,35 @@ def test_positions_from_planes_inverts_planes(N):
         positions_from_planes(obs[:, :5])
 
 
+def test_observation_planes_and_positions_from_planes_invert_each_other():
+    """One random 5x5 position under every combination of the three flag bits:
+    record -> observation -> record and observation -> record -> observation
+    are the identity, and each plane is what the record says."""
+    from mzgo.reanalyse import observation_planes, positions_from_planes
+    from mzgo.trainer import _planes
+    assert _planes is observation_planes                        # the one Python plane builder
+    N = 5
+    rng = np.random.default_rng(50)
+    stones = rng.integers(0, 3, size=N * N).astype(np.int8)
+    invd = rng.integers(0, 2, size=N * N).astype(np.uint8)
+    assert set(stones) == {0, 1, 2} and set(invd) == {0, 1}
+    for flags in range(8):
+        obs = observation_planes(stones, invd, flags, N)
+        assert obs.dtype == np.float64 and obs.shape == (6, N, N)
+        np.testing.assert_array_equal(obs[0].reshape(-1), stones == 1)
+        np.testing.assert_array_equal(obs[1].reshape(-1), stones == 2)
+        np.testing.assert_array_equal(obs[3].reshape(-1), invd)
+        for plane, bit in ((2, 0), (4, 1), (5, 2)):
+            np.testing.assert_array_equal(obs[plane], np.full((N, N), (flags >> bit) & 1))
+        s, i, f = positions_from_planes(obs[None])
+        np.testing.assert_array_equal(s[0].numpy(), stones)
+        np.testing.assert_array_equal(i[0].numpy(), invd)
+        assert int(f[0]) == flags
+        np.testing.assert_array_equal(observation_planes(s[0].numpy(), i[0].numpy(), f[0], N), obs)
+        # bit 3 (the fast-search bit of a stored row's flags) shows in no plane
+        np.testing.assert_array_equal(observation_planes(stones, invd, np.uint8(flags | 8), N), obs)
+
+
 def _move_key_id(game_base, g, epoch):
     """csrc/mzgo_move.hpp move_key: (uint32_t)(game_base + g) ^ ((uint32_t)epoch << 24), as the int32 the ABI takes."""
     u = ((game_base + g) & 0xFFFFFFFF) ^ ((epoch << 24) & 0xFFFFFFFF)

@@ -3,7 +3,10 @@
 // the position ledger's two, mzgo_replay_sample_positions_host and
 // mzgo_replay_position_priorities_host, and the game sampler's,
 // mzgo_replay_sample_host
-// (csrc/mzgo_replay.hip), called from a stand-alone host program so that the C
+// (csrc/mzgo_replay.hip), and the item list's decode, its two row predicates and
+// the plane rule the assembly kernels run (csrc/mzgo_replay.hpp: sample_window,
+// window_position, window_move, observation_plane, host and device functions),
+// called from a stand-alone host program so that the C
 // wrappers themselves -- their vectors, the index clamp, the writes into the
 // caller's buffers -- can run under AddressSanitizer and UBSan on a machine
 // without a GPU.  The program links the replay unit alone: what that unit takes
@@ -258,7 +261,86 @@ int main() {
     CHECK(mzgo_replay_position_priorities_host(r, nu, 1, 1, 0.99, 0.0, 0.0, out) == MZGO_EINVAL);
     CHECK(mzgo_replay_position_priorities_host(r, nu, 1, 1, 0.99, 1.0, -1.0, out) == MZGO_EINVAL);
   }
-  printf("ok: %ld targets, %ld pairs, %ld draws, %ld game draws, %ld weights\n", targets, pairs, draws, game_draws,
-         weights);
+  // ---- sample_window, window_position, window_move, observation_plane on a store image in host memory ----
+  long decoded = 0, rows_read = 0;
+  {
+    using namespace mzgo;
+    const int N = 5, C = N * N, A = C + 1, M = 6, cap = 2;
+    // exactly the ring's arrays for two slots
+    std::vector<int8_t> stones((size_t)cap * (M + 1) * C);
+    std::vector<uint8_t> invd((size_t)cap * (M + 1) * C), flags((size_t)cap * (M + 1));
+    std::vector<int> action((size_t)cap * M), length(cap), key_gid(cap, 0);
+    std::vector<double> policy((size_t)cap * M * A), reward((size_t)cap * (M + 1)), root_value((size_t)cap * M);
+    for (auto& x : stones) x = (int8_t)(rand() % 3);
+    for (auto& x : invd) x = (uint8_t)(rand() % 2);
+    for (auto& x : flags) x = (uint8_t)(rand() % 16);
+    for (auto& x : reward) x = unit();
+    const Store R{N, C, A, M, cap, stones.data(), invd.data(), flags.data(), action.data(), policy.data(),
+                  reward.data(), root_value.data(), length.data(), key_gid.data()};
+    // two games of 4 and M moves; then lengths a store never holds, which the decode clamps to 0..M
+    for (int pass = 0; pass < 2; ++pass) {
+      length[0] = pass == 0 ? 4 : -2;
+      length[1] = pass == 0 ? M : M + 3;
+      for (int slot : {-1, 0, cap - 1, cap})
+        for (int sym : {0, 7, 8, -1}) {
+          // the rule restated
+          const bool held = slot >= 0 && slot < cap;
+          const int L = !held ? 0 : std::min(std::max(length[slot], 0), M);
+          for (int start : {-1, 0, L - 1, L, L + 1}) {
+            const int32_t items[6] = {77, 77, 77, slot, start, sym};     // sample b = 1
+            const SampleWindow w = sample_window(R, items, 1);
+            CHECK(w.slot == slot && w.start == start && w.held == held && w.L == L);
+            CHECK(w.sym == (sym == 8 ? 0 : sym == -1 ? 7 : sym));
+            CHECK(w.pos == (held ? (size_t)slot * (M + 1) : 0) && w.mv == (held ? (size_t)slot * M : 0));
+            ++decoded;
+            for (long long at = (long long)start - 2; at <= (long long)start + 66; ++at) {
+              CHECK(window_position(w, at) == (held && at >= 0 && at <= L));
+              CHECK(window_move(w, at) == (held && at >= 0 && at < L));
+              // every row a predicate allows lies inside the image (a read past it is a report)
+              if (window_position(w, at)) {
+                const size_t q = w.pos + (size_t)at;
+                float sum = (float)reward[q];
+                for (int p = 0; p < 6; ++p)
+                  for (int c = 0; c < C; ++c)
+                    sum += observation_plane(R.stones + q * C, R.invd + q * C, R.flags[q], p, sym_src(N, w.sym, c));
+                CHECK(sum == sum);
+                ++rows_read;
+              }
+              if (window_move(w, at)) {
+                const size_t q = w.mv + (size_t)at;
+                CHECK(root_value[q] + policy[q * A + A - 1] + action[q] == 0.0);
+              }
+            }
+          }
+        }
+    }
+    for (long long at : {(long long)INT_MIN - 1, (long long)INT_MAX + 1, -1LL}) {
+      const int32_t items[3] = {0, 0, 0};
+      length[0] = M;
+      const SampleWindow w = sample_window(R, items, 0);
+      CHECK(!window_position(w, at) && !window_move(w, at));
+    }
+    // the six planes of one row under symmetry 0 (src = the cell itself), written out by hand
+    const int8_t row_stones[25] = {0, 1, 2, 0, 0,  1, 1, 0, 2, 0,  0, 0, 0, 0, 2,  2, 0, 1, 0, 0,  0, 2, 2, 1, 1};
+    const uint8_t row_invd[25] = {0, 1, 1, 0, 0,  1, 1, 0, 1, 1,  0, 0, 0, 0, 1,  1, 0, 1, 0, 0,  0, 1, 1, 1, 1};
+    const float black[25] = {0, 1, 0, 0, 0,  1, 1, 0, 0, 0,  0, 0, 0, 0, 0,  0, 0, 1, 0, 0,  0, 0, 0, 1, 1};
+    const float white[25] = {0, 0, 1, 0, 0,  0, 0, 0, 1, 0,  0, 0, 0, 0, 1,  1, 0, 0, 0, 0,  0, 1, 1, 0, 0};
+    const float inval[25] = {0, 1, 1, 0, 0,  1, 1, 0, 1, 1,  0, 0, 0, 0, 1,  1, 0, 1, 0, 0,  0, 1, 1, 1, 1};
+    for (int fl : {0, 1, 2, 4, 5, 8 | 2, 15}) {               // (bit 3, the fast-search bit, shows in no plane)
+      const float turn = fl & 1 ? 1.f : 0.f, passed = fl & 2 ? 1.f : 0.f, done = fl & 4 ? 1.f : 0.f;
+      for (int c = 0; c < 25; ++c) {
+        const int src = sym_src(5, 0, c);
+        CHECK(src == c);
+        CHECK(observation_plane(row_stones, row_invd, fl, 0, src) == black[c]);
+        CHECK(observation_plane(row_stones, row_invd, fl, 1, src) == white[c]);
+        CHECK(observation_plane(row_stones, row_invd, fl, 2, src) == turn);
+        CHECK(observation_plane(row_stones, row_invd, fl, 3, src) == inval[c]);
+        CHECK(observation_plane(row_stones, row_invd, fl, 4, src) == passed);
+        CHECK(observation_plane(row_stones, row_invd, fl, 5, src) == done);
+      }
+    }
+  }
+  printf("ok: %ld targets, %ld pairs, %ld draws, %ld game draws, %ld weights, %ld decodes, %ld rows\n", targets, pairs,
+         draws, game_draws, weights, decoded, rows_read);
   return 0;
 }
